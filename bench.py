@@ -11,7 +11,8 @@ seeded procedural 2048x1024 HDR env map (the reference's envmap.hdr is missing f
 frame k uses angle 0.01*(k+1) like the reference's `angle += 0.01f`.
 
 Run: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver launches it through
-torch.distributed.run (one rank per GPU, backend nccl = RCCL over xGMI).
+torch.distributed.run (one rank per GPU, backend nccl = RCCL over xGMI).  --dump-outputs DIR writes the last timed
+frame to DIR for comparing two builds output for output.
 """
 import argparse
 import json
@@ -274,6 +275,28 @@ def cpu_baseline(mesh, env, budget_s=12.0):
                       "median-split BVH; D3D12 WARP is Windows-only and cannot run here" % (frames, el)}
 
 
+def load_native(rr):
+    """The library build() made.  rr.lib() rebuilds librrdxr.so when it is missing or stale and may rewrite its build stamp; in
+    a tree that has been built and that this user cannot write (a read-only checkout), the library is loaded as it is."""
+    from refraction_raytracing_dxr_amd import _build, _capi
+    so = _capi.lib_path()
+    stamp = os.path.join(os.path.dirname(so), "build", "flags.txt")
+    if os.path.exists(so) and not os.access(stamp if os.path.exists(stamp) else os.path.dirname(so), os.W_OK):
+        build, _build.build = _build.build, lambda *a, **k: so
+        try:
+            rr.lib()
+        finally:
+            _build.build = build
+    return rr.lib()
+
+
+def dump_outputs(out_dir, frame_rgba8):
+    """--dump-outputs: the timed path's last frame as float32 (exact for 8-bit values)"""
+    os.makedirs(out_dir, exist_ok=True)
+    assert frame_rgba8.shape == (H, W, 4) and frame_rgba8.dtype == np.uint8, (frame_rgba8.shape, frame_rgba8.dtype)
+    np.save(os.path.join(out_dir, "last_frame_rgba8.npy"), frame_rgba8.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -296,11 +319,18 @@ def main():
                          "the tiles that touch the scene's screen rectangle")
     ap.add_argument("--frames-per-dispatch", type=int, default=64,
                     help="depth slices per launch (DispatchRays(W,H,Depth)); N>1: also frames per RCCL gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last of them rendered (the RGBA8 image a caller of the "
+                         "timed path reads back) as DIR/last_frame_rgba8.npy, float32 [1080, 1920, 4] (33 MB), so that two "
+                         "builds can be compared output for output; the inputs depend on the arguments alone")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
 
     import torch
     import refraction_raytracing_dxr_amd as rr
     from refraction_raytracing_dxr_amd.synth import asset, procedural_env
+    load_native(rr)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -376,6 +406,10 @@ def main():
         timed_kernel_name = st.render_kernel_name.decode()     # the kernel that rendered the (last launch of the) timed steps
         total_rays = st.rays
         overflow = st.traversal_overflow
+        if args.dump_outputs is not None:
+            # untimed: the last of the K frames is the last depth slice of the last launch (render_orbit issues ceil(K / F)
+            # launches of F slices, the last one of what remains), read back before anything else renders into the buffers
+            dump_outputs(args.dump_outputs, r.read_frame(slice=K - F * ((K - 1) // F) - 1))
     else:
         # a rank's share of a launch has 1/world of the blocks: keep launches long enough for their tails not to show
         # (tools/exp_lanes.py, world 8: 113 us/frame-equivalent at 64 frames per launch, 108 at 256)
@@ -398,6 +432,10 @@ def main():
         elapsed = time.perf_counter() - t0
         gathered_bytes = sf.gathered_bytes
         region_ms = None
+        # untimed: the last of the K frames, on the rank its batch was assembled on (rank 0 unless --rotate-root)
+        last_root = ((K + Fn - 1) // Fn - 1) % world if sf.rotate_root else 0
+        if args.dump_outputs is not None and rank == last_root:
+            dump_outputs(args.dump_outputs, sf.frames_host()[-1])
         # attribution of the N-GPU figure (untimed extra): every rank's share of the same frames rendered without the gather
         # and the de-interleave -- if the end-to-end time is far above the slowest rank's render time, the rest is rank 0's
         # ingest (7/8 of every frame crosses xGMI into one GPU) and its assemble launches, not the render kernel

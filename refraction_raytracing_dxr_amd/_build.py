@@ -61,8 +61,9 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
-    with open(stamp, "w") as f:
-        f.write(flags)
+    if force:                                           # an up-to-date tree is not written to (it may be read-only)
+        with open(stamp, "w") as f:
+            f.write(flags)
     demo_src = os.path.join(CSRC, "tools", "rrdemo.cpp")
     if force or _stale(DEMO, [demo_src, LIB]):
         cmd = [hipcc, demo_src, "-o", DEMO, "-O2", "-std=c++17", "-L" + PKG, "-lrrdxr", "-Wl,-rpath,$ORIGIN"]

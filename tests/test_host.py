@@ -142,33 +142,31 @@ def test_camera_matches_oracle_and_kats():
 
 
 # ---------------------------------------------------------------------------------- stbi_loadf stand-in
-REF_STB = os.path.join(ROOT, "oracle", "_ref", "libstb_ref.so")
+# What the reference's own stb_image.h (v2.28, built by oracle/Makefile where the reference tree is present) returns for every
+# file the three *_vs_reference_stb tests below write, stored by tests/golden/make_stb_goldens.py: the tests compare against
+# it bit for bit without needing the reference.  Arrays are stored whole; envmap.png's decodes (1.2 M floats each) by FNV-1a 64.
+STB_GOLD = os.path.join(ROOT, "tests", "golden", "stb_decode.npz")
+_stb_gold = None
 
 
-def have_ref_stb():
-    """the reference's stb_image.h compiled in place (oracle/Makefile); only looked for here -- it is loaded by the two tests
-    that check against it, when they run, never at collection time (a `-m gpu` run does not map it)"""
-    return os.path.exists(REF_STB)
+def stb_gold():
+    global _stb_gold
+    if _stb_gold is None:
+        _stb_gold = dict(np.load(STB_GOLD))
+    return _stb_gold
 
 
-def ref_stb():
-    L = C.CDLL(REF_STB)
-    L.stbi_loadf.restype = C.POINTER(C.c_float)
-    L.stbi_loadf.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    L.stbi_image_free.argtypes = [C.c_void_p]
-    return L
-
-
-def ref_loadf(path, req):
-    L = ref_stb()
-    x, y, n = C.c_int(), C.c_int(), C.c_int()
-    p = L.stbi_loadf(str(path).encode(), C.byref(x), C.byref(y), C.byref(n), req)
-    if not p:
-        return None, 0
-    oc = req if req else n.value
-    a = np.ctypeslib.as_array(p, shape=(y.value, x.value, oc)).copy()
-    L.stbi_image_free(p)
-    return a, n.value
+def assert_matches_reference_stb(key, mine, n):
+    """mine / n: rr.load_texture's result for the file stored under `key`; equal bit for bit to stbi_loadf's"""
+    g = stb_gold()
+    assert n == int(g[key + "/n"]), key
+    if key in g:
+        ref = g[key]
+        assert mine.shape == ref.shape, key
+        assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), key
+    else:
+        assert mine.shape == tuple(g[key + "/shape"]), key
+        assert O.fnv1a64(mine) == int(g[key + "/fnv1a64"]), key
 
 
 def test_envmap_png_golden():
@@ -184,9 +182,9 @@ def _write_png(path, arr, mode):
     Image.fromarray(arr, mode).save(path)
 
 
-@pytest.mark.skipif(not have_ref_stb(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("req", [0, 1, 2, 3, 4])
-def test_png_decode_bit_exact_vs_reference_stb(tmp_path, req):
+def png_decode_cases(tmp_path, req):
+    """the PNG files test_png_decode_bit_exact_vs_reference_stb decodes -> [(name, path)]"""
+    from PIL import Image
     rng = np.random.default_rng(req)
     cases = {
         "rgb.png": (rng.integers(0, 256, (37, 53, 3), dtype=np.uint8), "RGB"),
@@ -195,24 +193,22 @@ def test_png_decode_bit_exact_vs_reference_stb(tmp_path, req):
         "la.png": (rng.integers(0, 256, (16, 16, 2), dtype=np.uint8), "LA"),
         "smooth.png": (np.tile(np.arange(256, dtype=np.uint8), (64, 1)), "L"),     # exercises the PNG filters
     }
+    out = []
     for name, (arr, mode) in cases.items():
-        p = tmp_path / name
-        _write_png(p, arr, mode)
-        mine, n1 = rr.load_texture(p, req)
-        ref, n2 = ref_loadf(p, req)
-        assert n1 == n2 and mine.shape == ref.shape, name
-        assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), name
+        _write_png(tmp_path / name, arr, mode)
+        out.append((name, tmp_path / name))
     # palette and 16-bit
-    from PIL import Image
     Image.fromarray(cases["rgb.png"][0], "RGB").quantize(17).save(tmp_path / "pal.png")
     Image.fromarray(rng.integers(0, 65536, (9, 11), dtype=np.uint16)).save(tmp_path / "g16.png")
-    for name in ("pal.png", "g16.png"):
-        mine, n1 = rr.load_texture(tmp_path / name, req)
-        ref, n2 = ref_loadf(tmp_path / name, req)
-        assert n1 == n2 and np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), name
-    mine, _ = rr.load_texture(O.asset("envmap.png"), req)
-    ref, _ = ref_loadf(O.asset("envmap.png"), req)
-    assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32))
+    out += [("pal.png", tmp_path / "pal.png"), ("g16.png", tmp_path / "g16.png")]
+    return out + [("envmap.png", O.asset("envmap.png"))]
+
+
+@pytest.mark.parametrize("req", [0, 1, 2, 3, 4])
+def test_png_decode_bit_exact_vs_reference_stb(tmp_path, req):
+    for name, p in png_decode_cases(tmp_path, req):
+        mine, n = rr.load_texture(p, req)
+        assert_matches_reference_stb("png/%d/%s" % (req, name), mine, n)
 
 
 def test_hdr_write_read_roundtrip(tmp_path):
@@ -237,16 +233,23 @@ def test_hdr_write_read_roundtrip(tmp_path):
     assert np.array_equal(again, back)
 
 
-@pytest.mark.skipif(not have_ref_stb(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("req", [0, 1, 3, 4])
-def test_hdr_decode_bit_exact_vs_reference_stb(tmp_path, req):
+def hdr_decode_cases(tmp_path):
+    """the Radiance files test_hdr_decode_bit_exact_vs_reference_stb decodes -> [(name, path)]"""
     from conftest import procedural_env
+    out = []
     for w, h in ((96, 48), (5, 7), (8, 3)):
         p = tmp_path / ("e%dx%d.hdr" % (w, h))
         rr.write_hdr(p, procedural_env(w, h, seed=w))
-        mine, n1 = rr.load_texture(p, req)
-        ref, n2 = ref_loadf(p, req)
-        assert n1 == n2 == 3 and np.array_equal(mine.view(np.uint32), ref.view(np.uint32))
+        out.append((p.name, p))
+    return out
+
+
+@pytest.mark.parametrize("req", [0, 1, 3, 4])
+def test_hdr_decode_bit_exact_vs_reference_stb(tmp_path, req):
+    for name, p in hdr_decode_cases(tmp_path):
+        mine, n = rr.load_texture(p, req)
+        assert n == 3
+        assert_matches_reference_stb("hdr/%d/%s" % (req, name), mine, n)
 
 
 def _write_adam7_png(path, arr, depth=8, palette=None):
@@ -337,16 +340,21 @@ def test_adam7_png_decodes_to_the_image_it_was_made_from(tmp_path):
         assert np.allclose(mine, want, rtol=2e-6, atol=1e-7), name
 
 
-@pytest.mark.skipif(not have_ref_stb(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("req", [0, 3])
-def test_adam7_png_bit_exact_vs_reference_stb(tmp_path, req):
+def adam7_decode_cases(tmp_path):
+    """the interlaced PNGs test_adam7_png_bit_exact_vs_reference_stb decodes -> [(name, path)]"""
     rng = np.random.default_rng(8)
+    out = []
     for name, (arr, depth, pal) in _adam7_cases(rng).items():
         _write_adam7_png(tmp_path / name, arr, depth, pal)
-        mine, n1 = rr.load_texture(tmp_path / name, req)
-        ref, n2 = ref_loadf(tmp_path / name, req)
-        assert n1 == n2 and mine.shape == ref.shape, name
-        assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), name
+        out.append((name, tmp_path / name))
+    return out
+
+
+@pytest.mark.parametrize("req", [0, 3])
+def test_adam7_png_bit_exact_vs_reference_stb(tmp_path, req):
+    for name, p in adam7_decode_cases(tmp_path):
+        mine, n = rr.load_texture(p, req)
+        assert_matches_reference_stb("adam7/%d/%s" % (req, name), mine, n)
 
 
 def test_formats_outside_the_asset_surface_are_refused(tmp_path):

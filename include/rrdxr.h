@@ -180,6 +180,31 @@ int  rr_build_blas_ex(rr_context* ctx, uint32_t mesh_id, uint32_t flags);
  * reference's scene is one identity instance with mask 1 and flags 0. */
 int  rr_build_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n);
 
+/* ---- update builds (present from this version of the library, ABI version 3) ---------------
+ * D3D12_RAYTRACING_ACCELERATION_STRUCTURE_BUILD_FLAG_ALLOW_UPDATE / _PERFORM_UPDATE (same bit values).
+ * rr_build_blas_ex(ALLOW_UPDATE) builds the same nodes as without the flag and also keeps what a refit needs (a parent link
+ * per node and an arrival counter per internal node, 12 bytes per triangle).  rr_build_blas_ex(PERFORM_UPDATE) refits that
+ * hierarchy over the mesh's current vertices: boxes, triangle and normal records, bounds and the fp16 grid are recomputed, child
+ * refs and depth stay; RR_ERR_STATE if the BLAS was not built with ALLOW_UPDATE.  Either kind of BLAS build leaves the scene
+ * unbuilt: dispatches return RR_ERR_STATE until rr_build_tlas_ex builds or updates it.
+ * rr_build_tlas_ex(ALLOW_UPDATE) keeps the top level refittable; rr_build_tlas_ex(PERFORM_UPDATE) takes the same n and the
+ * same blas in every slot as that build (RR_ERR_INVALID_ARGUMENT otherwise; RR_ERR_STATE without an ALLOW_UPDATE build):
+ * transforms, masks and flags may change.  It refits the top level over the new instance boxes and re-pools only the BLASes
+ * built or updated since the scene was last built or updated.  rr_build_tlas == rr_build_tlas_ex(flags = 0). */
+#define RR_BUILD_ALLOW_UPDATE   0x1u
+#define RR_BUILD_PERFORM_UPDATE 0x20u
+int  rr_build_tlas_ex(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, uint32_t flags);
+/* Overwrite a mesh's vertex buffer in place (the index buffer, the topology, never changes).  n_verts must be the uploaded
+ * count; positions are validated as in rr_upload_mesh, and on failure the mesh is left untouched.  The mesh's BLAS is then out
+ * of date: rr_build_tlas_ex refuses it (RR_ERR_STATE) until rr_build_blas_ex rebuilds or updates it.  The mesh id and its
+ * device buffers stay the same.  The host array is copied before the call returns. */
+int  rr_update_mesh_vertices(rr_context* ctx, uint32_t mesh_id, const rr_vertex* verts, uint32_t n_verts);
+/* The same from device memory (n_verts 32-byte vertices at a 4-byte aligned device pointer), stream-ordered on the context's
+ * stream (rr_set_stream): the copy runs after the work queued on that stream before the call, and nothing is synchronised.
+ * A kernel checks the positions; if one is non-finite or huge nothing is copied, and the next rr_build_blas_ex of the mesh
+ * returns RR_ERR_INVALID_ARGUMENT with the mesh and its BLAS as they were. */
+int  rr_update_mesh_vertices_device(rr_context* ctx, uint32_t mesh_id, const void* d_verts, uint32_t n_verts);
+
 /* ---- per frame ----------------------------------------------------------------------------- */
 /* copy_to_buffer(cameraConstantBuffer, ...), RefractionDemo.cpp:566 */
 int  rr_set_camera(rr_context* ctx, const rr_scene_constants* constants);

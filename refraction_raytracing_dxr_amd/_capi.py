@@ -20,6 +20,8 @@ DISPATCH_TONEMAP_REINHARD = 0x20
 DISPATCH_DEBUG_NO_CULL = 0x40
 BUILD_PREFER_FAST_TRACE = 0x4
 BUILD_PREFER_FAST_BUILD = 0x8
+BUILD_ALLOW_UPDATE = 0x1
+BUILD_PERFORM_UPDATE = 0x20
 RAY_FLAG_CULL_BACK = 0x10
 RAY_FLAG_CULL_FRONT = 0x20
 INSTANCE_FLAG_CULL_DISABLE = 0x1
@@ -90,6 +92,9 @@ SYMBOLS = {
     "rr_build_blas": (C.c_int, [_P, C.c_uint32]),
     "rr_build_blas_ex": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "rr_build_tlas": (C.c_int, [_P, _P, C.c_uint32]),
+    "rr_build_tlas_ex": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
+    "rr_update_mesh_vertices": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
+    "rr_update_mesh_vertices_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     "rr_set_camera": (C.c_int, [_P, C.POINTER(SceneConstants)]),
     "rr_set_tile_partition": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "rr_dispatch_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(DispatchParams)]),

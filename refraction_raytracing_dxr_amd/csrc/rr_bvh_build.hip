@@ -69,6 +69,29 @@ __global__ __launch_bounds__(256) void k_tri_boxes(const float* __restrict__ ver
 }
 
 // instance world box = box of the 8 transformed BLAS-bounds corners (object->world 3x4)
+__device__ __forceinline__ void inst_world_box(const InstDev* __restrict__ insts, const float* __restrict__ xforms,
+                                               const float* __restrict__ blas_bounds, uint32_t p, float lo[3], float hi[3])
+{
+    const float inf = __builtin_huge_valf();
+    for (int k = 0; k < 3; ++k) { lo[k] = inf; hi[k] = -inf; }
+    const float* m = xforms + (size_t)p * 12;
+    const float* bb = blas_bounds + (size_t)p * 6;
+    const bool ident = insts[p].identity != 0u;
+    for (int c = 0; c < 8; ++c) {
+        float x = (c & 1) ? bb[3] : bb[0], y = (c & 2) ? bb[4] : bb[1], z = (c & 4) ? bb[5] : bb[2];
+        float wx = x, wy = y, wz = z;
+        if (!ident) {
+            wx = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+            wy = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+            wz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        }
+        lo[0] = fminf(lo[0], wx); lo[1] = fminf(lo[1], wy); lo[2] = fminf(lo[2], wz);
+        hi[0] = fmaxf(hi[0], wx); hi[1] = fmaxf(hi[1], wy); hi[2] = fmaxf(hi[2], wz);
+    }
+    // the corners were rounded by the transform: grow the box a little so it still contains the instance
+    for (int k = 0; k < 3; ++k) { lo[k] -= fmaf(fabsf(lo[k]), 1e-5f, 1e-7f); hi[k] += fmaf(fabsf(hi[k]), 1e-5f, 1e-7f); }
+}
+
 __global__ __launch_bounds__(256) void k_inst_boxes(const InstDev* __restrict__ insts, const float* __restrict__ xforms,
                                                     const float* __restrict__ blas_bounds, uint32_t n, BuildBuffers b)
 {
@@ -77,25 +100,8 @@ __global__ __launch_bounds__(256) void k_inst_boxes(const InstDev* __restrict__ 
     const float inf = __builtin_huge_valf();
     float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
     if (valid) {
-        const float* m = xforms + (size_t)p * 12;
-        const float* bb = blas_bounds + (size_t)p * 6;
-        const bool ident = insts[p].identity != 0u;
-        for (int c = 0; c < 8; ++c) {
-            float x = (c & 1) ? bb[3] : bb[0], y = (c & 2) ? bb[4] : bb[1], z = (c & 4) ? bb[5] : bb[2];
-            float wx = x, wy = y, wz = z;
-            if (!ident) {
-                wx = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-                wy = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-                wz = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-            }
-            lo[0] = fminf(lo[0], wx); lo[1] = fminf(lo[1], wy); lo[2] = fminf(lo[2], wz);
-            hi[0] = fmaxf(hi[0], wx); hi[1] = fmaxf(hi[1], wy); hi[2] = fmaxf(hi[2], wz);
-        }
-        // the corners were rounded by the transform: grow the box a little so it still contains the instance
-        for (int k = 0; k < 3; ++k) {
-            lo[k] -= fmaf(fabsf(lo[k]), 1e-5f, 1e-7f); hi[k] += fmaf(fabsf(hi[k]), 1e-5f, 1e-7f);
-            b.prim_box[(size_t)p * 6 + k] = lo[k]; b.prim_box[(size_t)p * 6 + 3 + k] = hi[k];
-        }
+        inst_world_box(insts, xforms, blas_bounds, p, lo, hi);
+        for (int k = 0; k < 3; ++k) { b.prim_box[(size_t)p * 6 + k] = lo[k]; b.prim_box[(size_t)p * 6 + 3 + k] = hi[k]; }
     }
     reduce_scene_box(lo, hi, valid, b.scene_box);
 }
@@ -476,6 +482,139 @@ __global__ __launch_bounds__(256) void k_quantize_nodes(QNode* __restrict__ dst,
     dst[i] = q;
 }
 
+// ---- update builds (DXR ALLOW_UPDATE / PERFORM_UPDATE): the kept topology refitted over new primitive boxes -------
+// What an ALLOW_UPDATE build keeps (RefitLinks): one link per node, internal nodes [0, n-1) then leaves [n-1, 2n-1) -- a BLAS
+// leaf by its leaf position, a TLAS leaf by its instance -- holding (parent << 1 | which child of the parent it is), -1 at
+// the root; and one arrival counter per internal node.  A counter takes exactly two tickets per refit and is never reset:
+// the first arrival draws an even ticket, the second an odd one.
+__global__ __launch_bounds__(256) void k_keep_links(BuildBuffers b, int32_t* __restrict__ links)
+{
+    const int n = (int)b.n;
+    const int x = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (n < 2 || x >= 2 * n - 1) return;
+    const int p = b.parent[x];
+    const int ref = x < n - 1 ? x : ~(x - (n - 1));             // how the parent's child[] names this node
+    int dst = x;
+    if (x >= n - 1 && b.leaf_ref_prim) dst = (n - 1) + (int)(uint32_t)(b.keys[x - (n - 1)] & 0xffffffffull);
+    links[dst] = p < 0 ? -1 : (p << 1) | (b.child[2 * p] == ref ? 0 : 1);
+}
+
+// Write this subtree's box into its slot of the parent node, take a ticket; the second arrival owns the parent: it reads the
+// sibling's slot and climbs on with the union (fminf(child 0, child 1), the order of k_refit and k_ploc, so that an unchanged
+// input refits to the same bytes).  Release / ticket / acquire at agent scope, as k_refit: the sibling may be on another XCD.
+__device__ __forceinline__ void refit_climb(BvhNode* __restrict__ nodes, const int32_t* __restrict__ links, uint32_t* visit, int link,
+                                            float box[6])
+{
+    while (link >= 0) {
+        const int cur = link >> 1, side = link & 1;
+        BvhNode* nd = nodes + cur;
+        nd->lox[side] = box[0]; nd->loy[side] = box[1]; nd->loz[side] = box[2];
+        nd->hix[side] = box[3]; nd->hiy[side] = box[4]; nd->hiz[side] = box[5];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t ticket = __hip_atomic_fetch_add(&visit[cur], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((ticket & 1u) == 0u) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const int o = side ^ 1;
+        float other[6];
+        other[0] = __builtin_nontemporal_load(&nd->lox[o]); other[1] = __builtin_nontemporal_load(&nd->loy[o]);
+        other[2] = __builtin_nontemporal_load(&nd->loz[o]); other[3] = __builtin_nontemporal_load(&nd->hix[o]);
+        other[4] = __builtin_nontemporal_load(&nd->hiy[o]); other[5] = __builtin_nontemporal_load(&nd->hiz[o]);
+        const float* l = side == 0 ? box : other;
+        const float* r = side == 0 ? other : box;
+        float u[6];
+        for (int k = 0; k < 3; ++k) { u[k] = fminf(l[k], r[k]); u[3 + k] = fmaxf(l[3 + k], r[3 + k]); }
+        for (int k = 0; k < 6; ++k) box[k] = u[k];
+        link = links[cur];
+    }
+}
+
+// BLAS refit, one thread per leaf in leaf order: the leaf's triangle from the new vertices (its TriRec / NrmRec, as
+// k_pack_tris writes them; TriRec.prim keeps leaf -> primitive), its box (k_tri_boxes' arithmetic) into the bounds reduction,
+// then the climb.  Child refs, pads and depth are never written.
+__global__ __launch_bounds__(256) void k_refit_blas(const float* __restrict__ verts, const uint32_t* __restrict__ idx, uint32_t n,
+                                                    TriRec* tris, NrmRec* __restrict__ nrms, BvhNode* nodes,
+                                                    const int32_t* __restrict__ links, uint32_t* visit, uint32_t* scene_box)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = i < n;
+    float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
+    if (valid) {
+        const uint32_t prim = tris[i].prim;
+        const float* A = verts + (size_t)idx[3 * prim + 0] * 8;
+        const float* B = verts + (size_t)idx[3 * prim + 1] * 8;
+        const float* C = verts + (size_t)idx[3 * prim + 2] * 8;
+        TriRec t;
+        NrmRec m;
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = fminf(A[k], fminf(B[k], C[k]));
+            hi[k] = fmaxf(A[k], fmaxf(B[k], C[k]));
+            t.v0[k] = A[k]; t.e1[k] = B[k] - A[k]; t.e2[k] = C[k] - A[k];
+            m.nA[k] = A[3 + k]; m.nB[k] = B[3 + k]; m.nC[k] = C[3 + k];
+        }
+        t.prim = prim; t.pad1 = 0; t.pad2 = 0;
+        m.pad0 = 0; m.pad1 = 0; m.pad2 = 0;
+        tris[i] = t;
+        nrms[i] = m;
+    }
+    reduce_scene_box(lo, hi, valid, scene_box);
+    if (!valid) return;
+    float box[6] = { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2] };
+    if (n == 1u) {                                       // node 0 = {leaf 0, empty}: only slot 0 moves
+        nodes[0].lox[0] = box[0]; nodes[0].loy[0] = box[1]; nodes[0].loz[0] = box[2];
+        nodes[0].hix[0] = box[3]; nodes[0].hiy[0] = box[4]; nodes[0].hiz[0] = box[5];
+        return;
+    }
+    refit_climb(nodes, links, visit, links[n - 1u + i], box);
+}
+
+// TLAS refit, one thread per instance: k_inst_boxes' world box of the instance, then the climb
+__global__ __launch_bounds__(256) void k_refit_tlas(const InstDev* __restrict__ insts, const float* __restrict__ xforms,
+                                                    const float* __restrict__ blas_bounds, uint32_t n, BvhNode* nodes,
+                                                    const int32_t* __restrict__ links, uint32_t* visit)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n) return;
+    float lo[3], hi[3];
+    inst_world_box(insts, xforms, blas_bounds, p, lo, hi);
+    float box[6] = { lo[0], lo[1], lo[2], hi[0], hi[1], hi[2] };
+    if (n == 1u) {
+        nodes[0].lox[0] = box[0]; nodes[0].loy[0] = box[1]; nodes[0].loz[0] = box[2];
+        nodes[0].hix[0] = box[3]; nodes[0].hiy[0] = box[4]; nodes[0].hiz[0] = box[5];
+        return;
+    }
+    refit_climb(nodes, links, visit, links[n - 1u + p], box);
+}
+
+__global__ void k_refit_init(uint32_t* scene_box)
+{
+    if (threadIdx.x < 3u) { scene_box[threadIdx.x] = 0xffffffffu; scene_box[3 + threadIdx.x] = 0u; }
+}
+
+// device-side vertex update: every position must be finite and |x| <= 1e18 (rr_host_validate_positions).  k_check_verts ORs
+// the verdict into st[0] (zeroed in front of it); k_copy_verts copies only if it stayed 0 and leaves it in st[1] (sticky,
+// read and cleared by the next build of the mesh), so a rejected update leaves the mesh as it was.
+__global__ __launch_bounds__(256) void k_check_verts(const float* __restrict__ src, uint32_t n_verts, uint32_t* st)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    if (v < n_verts)
+        for (int k = 0; k < 3; ++k) { const float x = src[(size_t)v * 8 + k]; bad |= !(fabsf(x) <= 1e18f); }
+    if (__any(bad) && (threadIdx.x & 63u) == 0u) atomicOr(&st[0], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_copy_verts(const float* __restrict__ src, float* __restrict__ dst, uint32_t n_verts, uint32_t* st)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t bad = __hip_atomic_load(&st[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bad) {
+        if (v == 0u) st[1] = 1u;
+        return;
+    }
+    if (v < n_verts)
+        for (int k = 0; k < 8; ++k) dst[(size_t)v * 8 + k] = src[(size_t)v * 8 + k];
+}
+
 __global__ __launch_bounds__(256) void k_env_pad(const float* __restrict__ rgb, float4* __restrict__ out, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -557,6 +696,39 @@ hipError_t launch_quantize_nodes(QNode* dst, const BvhNode* src, uint32_t n_node
 hipError_t launch_env_pad(const float* rgb, float4* out, uint32_t n_texels, hipStream_t s)
 {
     hipLaunchKernelGGL(k_env_pad, dim3(cdiv(n_texels, 256u)), dim3(256), 0, s, rgb, out, n_texels);
+    return hipGetLastError();
+}
+
+hipError_t launch_keep_links(const BuildBuffers& b, int32_t* links, hipStream_t s)
+{
+    if (b.n < 2u) return hipSuccess;
+    hipLaunchKernelGGL(k_keep_links, dim3(cdiv(2u * b.n - 1u, 256u)), dim3(256), 0, s, b, links);
+    return hipGetLastError();
+}
+
+hipError_t launch_refit_blas(const void* verts, const uint32_t* idx, uint32_t n_tris, TriRec* tris, NrmRec* nrms, BvhNode* nodes,
+                             const int32_t* links, uint32_t* visit, uint32_t* scene_box, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, scene_box);
+    hipLaunchKernelGGL(k_refit_blas, dim3(cdiv(n_tris, 256u)), dim3(256), 0, s, (const float*)verts, idx, n_tris, tris, nrms, nodes,
+                       links, visit, scene_box);
+    return hipGetLastError();
+}
+
+hipError_t launch_refit_tlas(const InstDev* insts, const float* xforms_and_bounds, uint32_t n, BvhNode* nodes, const int32_t* links,
+                             uint32_t* visit, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_refit_tlas, dim3(cdiv(n, 256u)), dim3(256), 0, s, insts, xforms_and_bounds, xforms_and_bounds + (size_t)n * 12,
+                       n, nodes, links, visit);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_verts(const void* d_src, void* d_dst, uint32_t n_verts, uint32_t* st, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(st, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_check_verts, dim3(cdiv(n_verts, 256u)), dim3(256), 0, s, (const float*)d_src, n_verts, st);
+    hipLaunchKernelGGL(k_copy_verts, dim3(cdiv(n_verts, 256u)), dim3(256), 0, s, (const float*)d_src, (float*)d_dst, n_verts, st);
     return hipGetLastError();
 }
 

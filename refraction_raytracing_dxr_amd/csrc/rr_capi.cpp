@@ -72,6 +72,14 @@ struct MeshRes {
     float     bounds[6] = { 0, 0, 0, 0, 0, 0 };
     float     scale = 1.0f;          // max |bounds|
     uint32_t  depth = 0;
+    // update builds (RR_BUILD_ALLOW_UPDATE / PERFORM_UPDATE)
+    int32_t*  links = nullptr;       // ALLOW_UPDATE builds: (parent << 1 | child slot) of every node (launch_keep_links)
+    uint32_t* visit = nullptr;       // ALLOW_UPDATE builds: n_tris-1 arrival counters of the refit
+    uint32_t* d_upd = nullptr;       // 8 words: refit bounds (ordered uints) [0,6), device vertex check [6] scratch, [7] sticky reject
+    bool      allow_update = false;
+    bool      stale = false;         // vertices replaced since the last build: the BLAS must be rebuilt or updated before a TLAS build
+    bool      dev_pending = false;   // a device vertex update whose verdict (d_upd[7]) the next build reads
+    uint64_t  version = 0;           // bumped by every successful build or update of the BLAS
 };
 
 // device block zeroed before every dispatch: counters, ray shards, error flag
@@ -111,6 +119,13 @@ struct rr_context {
     bool single_identity = false;
     float scene_scale = 1.0f;
     float scene_bounds[6] = { 0, 0, 0, 0, 0, 0 };   // world-space box of the whole scene (the TLAS root)
+    // where each mesh sits in the pools (0xffffffff: not in the scene) and the BLAS version pooled there (TLAS updates re-pool
+    // only what changed); TLAS ALLOW_UPDATE builds also keep the links and counters of the top level
+    std::vector<uint32_t> pool_node_off, pool_tri_off;
+    std::vector<uint64_t> pool_version;
+    int32_t*  d_tlas_links = nullptr;
+    uint32_t* d_tlas_visit = nullptr;
+    bool tlas_refittable = false;
 
     float*   d_screen = nullptr;     // GenerateCameraRay's screen coordinates for frames of screen_w x screen_h: sx[W], sy[H]
     uint32_t screen_w = 0, screen_h = 0;
@@ -446,7 +461,8 @@ int rr_destroy(rr_context* ctx)
         (void)hipEventDestroy(ctx->lane_done[l]);
         dfree(ctx->lane_cams[l]);
     }
-    for (MeshRes& m : ctx->meshes) { dfree(m.d_verts); dfree(m.d_idx); dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms); }
+    for (MeshRes& m : ctx->meshes) { dfree(m.d_verts); dfree(m.d_idx); dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms); dfree(m.links); dfree(m.visit); dfree(m.d_upd); }
+    dfree(ctx->d_tlas_links); dfree(ctx->d_tlas_visit);
     dfree(ctx->d_env); dfree(ctx->d_insts); dfree(ctx->d_pool_nodes); dfree(ctx->d_pool_qnodes); dfree(ctx->d_pool_tris); dfree(ctx->d_pool_nrms); dfree(ctx->d_rgba8); dfree(ctx->d_f32);
     for (StreamDev& sd : ctx->strm) { dfree(sd.q[0]); dfree(sd.q[1]); dfree(sd.fill[0]); dfree(sd.fill[1]); dfree(sd.heads); dfree(sd.slots); dfree(sd.pending); }
     for (hipEvent_t e : ctx->ch_ev) if (e) (void)hipEventDestroy(e);
@@ -565,72 +581,157 @@ int rr_upload_envmap(rr_context* ctx, const float* rgb, int32_t w, int32_t h)
 
 int rr_build_blas(rr_context* ctx, uint32_t mesh_id) { return rr_build_blas_ex(ctx, mesh_id, RR_BUILD_PREFER_FAST_TRACE); }
 
+} // extern "C"
+
+namespace {
+
+int ensure_upd(rr_context* ctx, MeshRes& m)
+{
+    if (m.d_upd) return RR_OK;
+    RR_HIP(hipMalloc(&m.d_upd, 8 * sizeof(uint32_t)));
+    RR_HIP(hipMemsetAsync(m.d_upd, 0, 8 * sizeof(uint32_t), ctx->stream));
+    return RR_OK;
+}
+
+// the verdict of the device vertex updates since the last build (rr_update_mesh_vertices_device); clears it
+int take_device_verdict(rr_context* ctx, MeshRes& m)
+{
+    if (!m.dev_pending) return RR_OK;
+    uint32_t rejected = 0;
+    RR_HIP(hipMemcpyAsync(&rejected, m.d_upd + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemsetAsync(m.d_upd + 7, 0, 4, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    m.dev_pending = false;
+    if (rejected)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_build_blas: a device vertex update held a non-finite or huge (> 1e18) position and was not applied");
+    return RR_OK;
+}
+
+void set_bounds(MeshRes& m, const uint32_t sb[6])
+{
+    for (int k = 0; k < 6; ++k) m.bounds[k] = ord2f_host(sb[k]);
+    m.scale = 0.0f;
+    for (int k = 0; k < 6; ++k) m.scale = std::max(m.scale, std::fabs(m.bounds[k]));
+    m.grid = make_grid(m.bounds);
+}
+
+// PERFORM_UPDATE: the kept hierarchy over the mesh's current vertices -- one refit launch (leaf records, boxes, bounds), the
+// bounds read back for the grid, one quantize launch.  Child refs and depth stay.
+int refit_blas(rr_context* ctx, MeshRes& m)
+{
+    if (!m.built || !m.allow_update)
+        return fail(ctx, RR_ERR_STATE, "rr_build_blas: PERFORM_UPDATE needs a BLAS built with RR_BUILD_ALLOW_UPDATE");
+    const uint32_t n = m.n_tris;
+    ctx->tlas_built = false;      // the pooled copies of this BLAS are stale until the TLAS is rebuilt or updated
+    RR_HIP(launch_refit_blas(m.d_verts, m.d_idx, n, m.tris, m.nrms, m.nodes, m.links, m.visit, m.d_upd, ctx->stream));
+    uint32_t sb[6];
+    RR_HIP(hipMemcpyAsync(sb, m.d_upd, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    set_bounds(m, sb);
+    RR_HIP(launch_quantize_nodes(m.qnodes, m.nodes, n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
+    m.stale = false;
+    ++m.version;
+    return RR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int rr_build_blas_ex(rr_context* ctx, uint32_t mesh_id, uint32_t flags)
 {
     const Range range_("rr_build_blas");
     if (int r = use_device(ctx)) return r;
     if (mesh_id >= ctx->meshes.size()) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_blas: unknown mesh id");
     MeshRes& m = ctx->meshes[mesh_id];
+    if (int r = take_device_verdict(ctx, m)) return r;
+    if (flags & RR_BUILD_PERFORM_UPDATE) return refit_blas(ctx, m);
     const uint32_t n = m.n_tris;
     if ((uint64_t)n * sizeof(QNode) >= 0x7fffffffull) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_blas: mesh too large for 31-bit node refs");
+    const bool keep = (flags & RR_BUILD_ALLOW_UPDATE) != 0;
     BuildScratch s;
     if (int r = alloc_build(ctx, n, s)) return r;
-    dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms);
+    dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms); dfree(m.links); dfree(m.visit);
     m.built = false;
+    m.allow_update = false;
     RR_HIP(hipMalloc(&m.nodes, (size_t)(n > 1 ? n - 1 : 1) * sizeof(BvhNode)));
     RR_HIP(hipMalloc(&m.qnodes, (size_t)(n > 1 ? n - 1 : 1) * sizeof(QNode)));
     RR_HIP(hipMalloc(&m.tris, (size_t)n * sizeof(TriRec)));
     RR_HIP(hipMalloc(&m.nrms, (size_t)n * sizeof(NrmRec)));
+    if (keep) {
+        if (int r = ensure_upd(ctx, m)) return r;
+        if (n > 1) {
+            RR_HIP(hipMalloc(&m.links, (size_t)(2 * (size_t)n - 1) * sizeof(int32_t)));
+            RR_HIP(hipMalloc(&m.visit, (size_t)(n - 1) * sizeof(uint32_t)));
+            RR_HIP(hipMemsetAsync(m.visit, 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
+        }
+    }
     s.b.nodes = m.nodes;
     RR_HIP(launch_tri_setup(m.d_verts, m.d_idx, n, s.b, ctx->stream));
     if ((flags & RR_BUILD_PREFER_FAST_TRACE) && !(flags & RR_BUILD_PREFER_FAST_BUILD) && n > 1 && n <= PLOC_MAX_PRIMS)
         RR_HIP(launch_ploc(s.b, ctx->stream));          // clustered hierarchy (fewer node visits)
     else
         RR_HIP(launch_lbvh(s.b, ctx->stream));          // Karras radix tree (fastest build, any size)
+    if (keep) RR_HIP(launch_keep_links(s.b, m.links, ctx->stream));
     RR_HIP(launch_pack_tris(m.d_verts, m.d_idx, s.b, m.tris, m.nrms, ctx->stream));
     uint32_t sb[6], depth = 0;
     RR_HIP(hipMemcpyAsync(sb, s.b.scene_box, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 6; ++k) m.bounds[k] = ord2f_host(sb[k]);
-    m.scale = 0.0f;
-    for (int k = 0; k < 6; ++k) m.scale = std::max(m.scale, std::fabs(m.bounds[k]));
+    set_bounds(m, sb);
     m.depth = depth;
-    m.grid = make_grid(m.bounds);
     RR_HIP(launch_quantize_nodes(m.qnodes, m.nodes, n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
     if (depth > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_blas: LBVH deeper than the 64-entry traversal stack");
     m.built = true;
+    m.allow_update = keep;
+    m.stale = false;
+    ++m.version;
     ctx->tlas_built = false;      // any TLAS built before refers to the old BLAS
     return RR_OK;
 }
 
-int rr_build_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n)
+int rr_update_mesh_vertices(rr_context* ctx, uint32_t mesh_id, const rr_vertex* verts, uint32_t n_verts)
 {
-    const Range range_("rr_build_tlas");
     if (int r = use_device(ctx)) return r;
-    if (!instances || n == 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: need >= 1 instance");
-    for (uint32_t i = 0; i < n; ++i) {
-        if (instances[i].blas >= ctx->meshes.size()) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: unknown BLAS");
-        if (!ctx->meshes[(size_t)instances[i].blas].built) return fail(ctx, RR_ERR_STATE, "rr_build_tlas: BLAS not built");
-    }
+    if (mesh_id >= ctx->meshes.size()) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices: unknown mesh id");
+    MeshRes& m = ctx->meshes[mesh_id];
+    if (!verts || n_verts != m.n_verts)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices: need the uploaded vertex count");
+    if (rr_host_validate_positions(verts, n_verts, nullptr) != RR_OK)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices: non-finite or huge (> 1e18) vertex position");
+    RR_HIP(hipMemcpyAsync(m.d_verts, verts, (size_t)n_verts * sizeof(rr_vertex), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));   // caller keeps ownership of the host array
+    m.stale = true;
+    return RR_OK;
+}
+
+int rr_update_mesh_vertices_device(rr_context* ctx, uint32_t mesh_id, const void* d_verts, uint32_t n_verts)
+{
+    if (int r = use_device(ctx)) return r;
+    if (mesh_id >= ctx->meshes.size()) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices_device: unknown mesh id");
+    MeshRes& m = ctx->meshes[mesh_id];
+    if (!d_verts || ((uintptr_t)d_verts & 3u) != 0 || n_verts != m.n_verts)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices_device: need a 4-byte aligned pointer and the uploaded vertex count");
+    if (int r = ensure_upd(ctx, m)) return r;
+    RR_HIP(launch_update_verts(d_verts, m.d_verts, n_verts, m.d_upd + 6, ctx->stream));
+    m.stale = true;
+    m.dev_pending = true;
+    return RR_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// per-instance device records, transforms + BLAS bounds (launch_inst_setup's layout) and the world-space scale of a scene
+int tlas_inputs(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, const std::vector<uint32_t>& node_off,
+                std::vector<InstDev>& host, std::vector<float>& xb, float& scene_scale)
+{
     static const float ident[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
-    // pool layout: nodes [0, n_tlas) TLAS, then each distinct BLAS; triangles / normals concatenated
-    const uint32_t n_tlas = n > 1 ? n - 1 : 1;
-    std::vector<uint32_t> node_off(ctx->meshes.size(), 0xffffffffu), tri_off(ctx->meshes.size(), 0);
-    uint32_t n_pool_nodes = n_tlas, n_pool_tris = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const size_t mi = (size_t)instances[i].blas;
-        if (node_off[mi] != 0xffffffffu) continue;
-        const MeshRes& m = ctx->meshes[mi];
-        node_off[mi] = n_pool_nodes; tri_off[mi] = n_pool_tris;
-        n_pool_nodes += m.n_tris > 1 ? m.n_tris - 1 : 1;
-        n_pool_tris += m.n_tris;
-    }
-    if ((uint64_t)n_pool_tris + n >= 0x7fffffffull || (uint64_t)n_pool_nodes * sizeof(QNode) >= 0x7fffffffull)
-        return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: scene too large for 31-bit node / leaf refs");
-    std::vector<InstDev> host(n);
-    float scene_scale = 0.0f;
-    std::vector<float> xb((size_t)n * 18);
+    host.assign(n, InstDev());
+    xb.assign((size_t)n * 18, 0.0f);
+    scene_scale = 0.0f;
     for (uint32_t i = 0; i < n; ++i) {
         const rr_instance_desc& d = instances[i];
         const MeshRes& m = ctx->meshes[(size_t)d.blas];
@@ -656,13 +757,141 @@ int rr_build_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n
         memcpy(&xb[(size_t)i * 12], d.transform, 48);
         memcpy(&xb[(size_t)n * 12 + (size_t)i * 6], m.bounds, 24);
     }
+    return RR_OK;
+}
+
+// scene grid = the box of the TLAS root (node 0 holds the boxes of its two children)
+void scene_from_root(rr_context* ctx, const BvhNode& root)
+{
+    float sb[6] = { 3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f };
+    for (int k = 0; k < 2; ++k) {
+        if (!(root.lox[k] <= root.hix[k])) continue;           // the empty second child of a one-instance TLAS
+        sb[0] = std::min(sb[0], root.lox[k]); sb[1] = std::min(sb[1], root.loy[k]); sb[2] = std::min(sb[2], root.loz[k]);
+        sb[3] = std::max(sb[3], root.hix[k]); sb[4] = std::max(sb[4], root.hiy[k]); sb[5] = std::max(sb[5], root.hiz[k]);
+    }
+    ctx->scene_grid = make_grid(sb);
+    memcpy(ctx->scene_bounds, sb, sizeof sb);
+}
+
+// quantize + copy into the pools every BLAS of the scene whose version differs from the pooled one (all of them after a build)
+hipError_t repool(rr_context* ctx)
+{
+    hipError_t e = hipSuccess;
+    // (pool_node_off covers the meshes that existed at the TLAS build; later uploads are not in the scene)
+    for (size_t mi = 0; mi < ctx->pool_node_off.size() && e == hipSuccess; ++mi) {
+        if (ctx->pool_node_off[mi] == 0xffffffffu) continue;
+        const MeshRes& m = ctx->meshes[mi];
+        if (ctx->pool_version[mi] == m.version) continue;
+        const uint32_t no = ctx->pool_node_off[mi], to = ctx->pool_tri_off[mi];
+        e = launch_quantize_nodes(ctx->d_pool_qnodes + no, m.nodes, m.n_tris > 1 ? m.n_tris - 1 : 1, m.grid, no, to, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_tris + to, m.tris, (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_nrms + to, m.nrms, (size_t)m.n_tris * sizeof(NrmRec), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) ctx->pool_version[mi] = m.version;
+    }
+    return e;
+}
+
+// what a successful TLAS build or update leaves in the context
+int finish_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, const InstDev& inst0, float scene_scale)
+{
+    ctx->inst_host.assign(instances, instances + n);
+    ctx->n_insts = n;
+    ctx->scene_scale = scene_scale;
+    const rr_instance_desc& d0 = instances[0];
+    ctx->single_identity = n == 1 && inst0.identity && (d0.hitgroup_flags >> 24) == 0 && ((d0.instance_id_mask >> 24) & 0xffu) != 0;
+    if (scene_stack_need(ctx) > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: TLAS+BLAS deeper than the 64-entry stack");
+    ctx->tlas_built = true;
+    ctx->ch_tlas = rr_context::ChoiceClass(); ctx->ch_many = rr_context::ChoiceClass(); ctx->ch_few = rr_context::ChoiceClass();      // a new scene: the kernels are chosen afresh
+    return RR_OK;
+}
+
+// PERFORM_UPDATE of the top level: same instance count, same BLAS per slot; transforms, masks and flags may change
+int refit_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n)
+{
+    if (!ctx->tlas_refittable) return fail(ctx, RR_ERR_STATE, "rr_build_tlas: PERFORM_UPDATE needs a TLAS built with RR_BUILD_ALLOW_UPDATE");
+    if (n != ctx->n_insts) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: PERFORM_UPDATE needs the instance count of the build");
+    for (uint32_t i = 0; i < n; ++i)
+        if (instances[i].blas != ctx->inst_host[i].blas)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: PERFORM_UPDATE needs the same BLAS in every instance slot");
+    std::vector<InstDev> host;
+    std::vector<float> xb;
+    float scene_scale = 0.0f;
+    if (int r = tlas_inputs(ctx, instances, n, ctx->pool_node_off, host, xb, scene_scale)) return r;
     ctx->tlas_built = false;
+    float* d_xb = nullptr;
+    RR_HIP(hipMalloc(&d_xb, xb.size() * 4));
+    const uint32_t n_tlas = n > 1 ? n - 1 : 1;
+    BvhNode root;
+    hipError_t e = hipMemcpyAsync(ctx->d_insts, host.data(), (size_t)n * sizeof(InstDev), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_xb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = launch_refit_tlas(ctx->d_insts, d_xb, n, ctx->d_pool_nodes, ctx->d_tlas_links, ctx->d_tlas_visit, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&root, ctx->d_pool_nodes, sizeof root, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
+        scene_from_root(ctx, root);
+        e = launch_quantize_nodes(ctx->d_pool_qnodes, ctx->d_pool_nodes, n_tlas, ctx->scene_grid, 0, 0, ctx->stream);
+    }
+    if (e == hipSuccess) e = repool(ctx);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_xb);
+    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "TLAS update", e);
+    return finish_tlas(ctx, instances, n, host[0], scene_scale);
+}
+
+} // namespace
+
+extern "C" {
+
+int rr_build_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n) { return rr_build_tlas_ex(ctx, instances, n, 0u); }
+
+int rr_build_tlas_ex(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, uint32_t flags)
+{
+    const Range range_("rr_build_tlas");
+    if (int r = use_device(ctx)) return r;
+    if (!instances || n == 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: need >= 1 instance");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (instances[i].blas >= ctx->meshes.size()) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_build_tlas: unknown BLAS");
+        const MeshRes& m = ctx->meshes[(size_t)instances[i].blas];
+        if (!m.built) return fail(ctx, RR_ERR_STATE, "rr_build_tlas: BLAS not built");
+        if (m.stale) return fail(ctx, RR_ERR_STATE, "rr_build_tlas: BLAS out of date (its vertices changed): rebuild or update it first");
+    }
+    if (flags & RR_BUILD_PERFORM_UPDATE) return refit_tlas(ctx, instances, n);
+    const bool keep = (flags & RR_BUILD_ALLOW_UPDATE) != 0;
+    // pool layout: nodes [0, n_tlas) TLAS, then each distinct BLAS; triangles / normals concatenated
+    const uint32_t n_tlas = n > 1 ? n - 1 : 1;
+    std::vector<uint32_t> node_off(ctx->meshes.size(), 0xffffffffu), tri_off(ctx->meshes.size(), 0);
+    uint32_t n_pool_nodes = n_tlas, n_pool_tris = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const size_t mi = (size_t)instances[i].blas;
+        if (node_off[mi] != 0xffffffffu) continue;
+        const MeshRes& m = ctx->meshes[mi];
+        node_off[mi] = n_pool_nodes; tri_off[mi] = n_pool_tris;
+        n_pool_nodes += m.n_tris > 1 ? m.n_tris - 1 : 1;
+        n_pool_tris += m.n_tris;
+    }
+    if ((uint64_t)n_pool_tris + n >= 0x7fffffffull || (uint64_t)n_pool_nodes * sizeof(QNode) >= 0x7fffffffull)
+        return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: scene too large for 31-bit node / leaf refs");
+    std::vector<InstDev> host;
+    std::vector<float> xb;
+    float scene_scale = 0.0f;
+    if (int r = tlas_inputs(ctx, instances, n, node_off, host, xb, scene_scale)) return r;
+    ctx->tlas_built = false;
+    ctx->tlas_refittable = false;
     dfree(ctx->d_insts); dfree(ctx->d_pool_nodes); dfree(ctx->d_pool_qnodes); dfree(ctx->d_pool_tris); dfree(ctx->d_pool_nrms);
+    dfree(ctx->d_tlas_links); dfree(ctx->d_tlas_visit);
     RR_HIP(hipMalloc(&ctx->d_insts, (size_t)n * sizeof(InstDev)));
     RR_HIP(hipMalloc(&ctx->d_pool_nodes, (size_t)n_tlas * sizeof(BvhNode)));
     RR_HIP(hipMalloc(&ctx->d_pool_qnodes, (size_t)n_pool_nodes * sizeof(QNode)));
     RR_HIP(hipMalloc(&ctx->d_pool_tris, (size_t)n_pool_tris * sizeof(TriRec)));
     RR_HIP(hipMalloc(&ctx->d_pool_nrms, (size_t)n_pool_tris * sizeof(NrmRec)));
+    if (keep && n > 1) {
+        RR_HIP(hipMalloc(&ctx->d_tlas_links, (size_t)(2 * (size_t)n - 1) * sizeof(int32_t)));
+        RR_HIP(hipMalloc(&ctx->d_tlas_visit, (size_t)(n - 1) * sizeof(uint32_t)));
+        RR_HIP(hipMemsetAsync(ctx->d_tlas_visit, 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
+    }
+    ctx->pool_node_off = node_off;
+    ctx->pool_tri_off = tri_off;
+    ctx->pool_version.assign(ctx->meshes.size(), ~0ull);     // nothing pooled yet: repool copies every BLAS of the scene
     float* d_xb = nullptr;
     RR_HIP(hipMalloc(&d_xb, xb.size() * 4));
     BuildScratch s;
@@ -679,45 +908,25 @@ int rr_build_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n
         // (the top level keeps the Karras hierarchy: the clustered builder, tried on it in round 3, makes the 1 024-instance grid
         // 5 % slower on both renderers -- on a regular lattice every merged-box area ties)
         if (e == hipSuccess) e = launch_lbvh(s.b, ctx->stream);
+        if (e == hipSuccess && keep) e = launch_keep_links(s.b, ctx->d_tlas_links, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream);
-        // scene grid = the box of the TLAS root (node 0 holds the boxes of its two children)
         BvhNode root;
         if (e == hipSuccess) e = hipMemcpyAsync(&root, ctx->d_pool_nodes, sizeof root, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) {
-            float sb[6] = { 3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f };
-            for (int k = 0; k < 2; ++k) {
-                if (!(root.lox[k] <= root.hix[k])) continue;           // the empty second child of a one-instance TLAS
-                sb[0] = std::min(sb[0], root.lox[k]); sb[1] = std::min(sb[1], root.loy[k]); sb[2] = std::min(sb[2], root.loz[k]);
-                sb[3] = std::max(sb[3], root.hix[k]); sb[4] = std::max(sb[4], root.hiy[k]); sb[5] = std::max(sb[5], root.hiz[k]);
-            }
-            ctx->scene_grid = make_grid(sb);
-            memcpy(ctx->scene_bounds, sb, sizeof sb);
+            scene_from_root(ctx, root);
             e = launch_quantize_nodes(ctx->d_pool_qnodes, ctx->d_pool_nodes, n_tlas, ctx->scene_grid, 0, 0, ctx->stream);
         }
-        for (size_t mi = 0; mi < ctx->meshes.size() && e == hipSuccess; ++mi) {
-            if (node_off[mi] == 0xffffffffu) continue;
-            const MeshRes& m = ctx->meshes[mi];
-            e = launch_quantize_nodes(ctx->d_pool_qnodes + node_off[mi], m.nodes, m.n_tris > 1 ? m.n_tris - 1 : 1, m.grid, node_off[mi], tri_off[mi], ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_tris + tri_off[mi], m.tris, (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_nrms + tri_off[mi], m.nrms, (size_t)m.n_tris * sizeof(NrmRec), hipMemcpyDeviceToDevice, ctx->stream);
-        }
+        if (e == hipSuccess) e = repool(ctx);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
     (void)hipFree(d_xb);
     if (rc != RR_OK) return rc;
     if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "TLAS build", e);
     ctx->n_pool_tris = n_pool_tris;
-    ctx->inst_host.assign(instances, instances + n);
-    ctx->n_insts = n;
-    ctx->scene_scale = scene_scale;
     ctx->tlas_depth = depth;
-    const rr_instance_desc& d0 = instances[0];
-    ctx->single_identity = n == 1 && host[0].identity && (d0.hitgroup_flags >> 24) == 0 && ((d0.instance_id_mask >> 24) & 0xffu) != 0;
-    if (scene_stack_need(ctx) > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: TLAS+BLAS deeper than the 64-entry stack");
-    ctx->tlas_built = true;
-    ctx->ch_tlas = rr_context::ChoiceClass(); ctx->ch_many = rr_context::ChoiceClass(); ctx->ch_few = rr_context::ChoiceClass();      // a new scene: the kernels are chosen afresh
-    return RR_OK;
+    ctx->tlas_refittable = keep;
+    return finish_tlas(ctx, instances, n, host[0], scene_scale);
 }
 
 int rr_set_camera(rr_context* ctx, const rr_scene_constants* constants)

@@ -72,6 +72,17 @@ hipError_t launch_inst_setup(const InstDev* insts, const float* blas_bounds, uin
 // copy a BLAS into the scene pool: internal refs += node_off, leaf refs ~l -> ~(l + tri_off)
 hipError_t launch_quantize_nodes(QNode* dst, const BvhNode* src, uint32_t n_nodes, const QGrid& g, uint32_t node_off, uint32_t tri_off,
                                  hipStream_t s);
+// update builds (DXR ALLOW_UPDATE / PERFORM_UPDATE): after launch_lbvh / launch_ploc, links[2n-1] = (parent << 1 | child slot) of
+// every node, -1 at the root (leaves of a TLAS, leaf_ref_prim = 1, by instance); then a refit rewrites the boxes of `nodes` in
+// place over new primitives (visit: n-1 arrival counters, zero after the build, never reset)
+hipError_t launch_keep_links(const BuildBuffers& b, int32_t* links, hipStream_t s);
+hipError_t launch_refit_blas(const void* verts, const uint32_t* idx, uint32_t n_tris, TriRec* tris, NrmRec* nrms, BvhNode* nodes,
+                             const int32_t* links, uint32_t* visit, uint32_t* scene_box, hipStream_t s);
+hipError_t launch_refit_tlas(const InstDev* insts, const float* xforms_and_bounds, uint32_t n, BvhNode* nodes, const int32_t* links,
+                             uint32_t* visit, hipStream_t s);
+// device-side vertex update: copies n_verts 32-byte vertices d_src -> d_dst unless a position is non-finite or > 1e18, in which
+// case nothing is copied and st[1] becomes 1 (st[0] is scratch)
+hipError_t launch_update_verts(const void* d_src, void* d_dst, uint32_t n_verts, uint32_t* st, hipStream_t s);
 hipError_t launch_env_pad(const float* rgb, float4* out, uint32_t n_texels, hipStream_t s);
 
 } // namespace rr

@@ -172,14 +172,50 @@ class Renderer:
         assert c == 3
         self._ck(self._L.rr_upload_envmap(self._h, rgb.ctypes.data, w, h), "rr_upload_envmap")
 
-    def build_blas(self, mesh_id, fast_build=False):
-        """BuildRaytracingAccelerationStructure (bottom level); fast_build=True forces the plain Morton LBVH"""
-        self._ck(self._L.rr_build_blas_ex(self._h, mesh_id, _capi.BUILD_PREFER_FAST_BUILD if fast_build
-                                          else _capi.BUILD_PREFER_FAST_TRACE), "rr_build_blas")
+    def build_blas(self, mesh_id, fast_build=False, allow_update=False, update=False):
+        """BuildRaytracingAccelerationStructure (bottom level); fast_build=True forces the plain Morton LBVH.
+        allow_update=True keeps what a refit needs (DXR ALLOW_UPDATE); update=True refits the hierarchy of such a build over
+        the mesh's current vertices (DXR PERFORM_UPDATE) instead of building a new one."""
+        if update:
+            flags = _capi.BUILD_PERFORM_UPDATE
+        else:
+            flags = _capi.BUILD_PREFER_FAST_BUILD if fast_build else _capi.BUILD_PREFER_FAST_TRACE
+            if allow_update:
+                flags |= _capi.BUILD_ALLOW_UPDATE
+        self._ck(self._L.rr_build_blas_ex(self._h, mesh_id, flags), "rr_build_blas")
 
-    def build_tlas(self, instances=None):
+    def build_tlas(self, instances=None, allow_update=False, update=False):
+        """BuildRaytracingAccelerationStructure (top level).  update=True refits a TLAS built with allow_update=True over new
+        transforms / masks / flags of the same instances (same count, same BLAS per slot) and re-pools the updated BLASes."""
         inst = make_instances() if instances is None else np.ascontiguousarray(instances, INSTANCE_DTYPE)
-        self._ck(self._L.rr_build_tlas(self._h, inst.ctypes.data, len(inst)), "rr_build_tlas")
+        flags = (_capi.BUILD_ALLOW_UPDATE if allow_update else 0) | (_capi.BUILD_PERFORM_UPDATE if update else 0)
+        self._ck(self._L.rr_build_tlas_ex(self._h, inst.ctypes.data, len(inst), flags), "rr_build_tlas")
+
+    def update_mesh_vertices(self, mesh_id, verts):
+        """Replace a mesh's vertices in place (same count; the indices never change); the mesh id stays.  Then
+        build_blas(mesh_id, update=True) (or a full build) and build_tlas(...) before the next dispatch.
+
+        verts: a VERTEX_DTYPE numpy array (or [n, 8] float32), copied from the host before this returns; or a contiguous
+        float32 torch tensor of shape [n, 8] on this renderer's GPU, copied on the renderer's stream without passing through
+        the host.  The copy is ordered after the work already queued on that stream only: a tensor produced on another stream
+        (torch's current stream, say) must be finished or ordered first -- call set_stream(torch.cuda.current_stream()
+        .cuda_stream) once, or torch.cuda.current_stream().synchronize() before the call.  A non-finite position in a tensor is
+        reported by the next build_blas of the mesh (RR_ERR_INVALID_ARGUMENT), which leaves the mesh as it was."""
+        if type(verts).__module__.startswith("torch"):
+            t = verts
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("update_mesh_vertices: the tensor must live on GPU %d" % self.device)
+            import torch
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 8 or not t.is_contiguous():
+                raise ValueError("update_mesh_vertices: need a contiguous [n, 8] float32 tensor")
+            self._ck(self._L.rr_update_mesh_vertices_device(self._h, mesh_id, C.c_void_p(t.data_ptr()), len(t)),
+                     "rr_update_mesh_vertices_device")
+            return
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 8)
+        assert verts.dtype.itemsize * (verts.size // len(verts)) == 32
+        self._ck(self._L.rr_update_mesh_vertices(self._h, mesh_id, verts.ctypes.data, len(verts)), "rr_update_mesh_vertices")
 
     def set_camera(self, sc):
         self._ck(self._L.rr_set_camera(self._h, C.byref(sc)), "rr_set_camera")

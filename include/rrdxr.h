@@ -129,10 +129,20 @@ typedef struct rr_ray {
     float origin[3]; float tmin;
     float dir[3];    float tmax;
     uint32_t flags;               /* RR_RAY_FLAG_* */
-    uint32_t pad[3];
+    uint32_t instance_mask;       /* DXR InstanceInclusionMask (low 8 bits): an instance is visited only if
+                                     (instance_mask & InstanceMask) != 0, so 0 hits nothing.  rr_query_rays[_device] only;
+                                     rr_trace_rays treats every ray as 0xff */
+    uint32_t pad[2];
 } rr_ray;
 
-#define RR_RAY_FLAG_CULL_BACK_FACING_TRIANGLES  0x10u   /* DXR RAY_FLAG values */
+/* DXR RAY_FLAG values.  Every other bit is ignored.  With both cull bits set CULL_BACK wins. */
+#define RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH 0x4u  /* rr_query_rays[_device] only: return SOME accepted intersection in
+                                                             (tmin, tmax) under the ray's cull flags and stop there.  Which one is
+                                                             unspecified (as in DXR) but the same for the same inputs and build;
+                                                             hit is always the closest-hit query's hit, and t, u, v, prim, inst
+                                                             describe the returned triangle as for a closest hit */
+#define RR_RAY_FLAG_SKIP_CLOSEST_HIT_SHADER         0x8u  /* accepted, no effect: the attributes are still returned */
+#define RR_RAY_FLAG_CULL_BACK_FACING_TRIANGLES  0x10u
 #define RR_RAY_FLAG_CULL_FRONT_FACING_TRIANGLES 0x20u
 
 typedef struct rr_hit {
@@ -361,6 +371,19 @@ int  rr_host_unregister(rr_context* ctx, void* p);
 /* TraceRay on caller-supplied rays (host arrays), same traversal code as the render path.
  * Stands for RayTracing.hlsl:60,106,121 in isolation; used by the parity tests. */
 int  rr_trace_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits);
+
+/* ---- ray queries (present from this version of the library, ABI version 3) -------------------
+ * TraceRay(Scene, flags, instance_mask, 0, 0, 0, ray, payload) on caller rays: the traversal of the render path with the ray's
+ * InstanceInclusionMask (rr_ray.instance_mask) and RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH; rays of one batch may mix
+ * first-hit and closest-hit.  A closest-hit query with instance_mask 0xff gives what rr_trace_rays gives.  Both return
+ * RR_ERR_STATE until the scene is built, and after a BLAS build or update until rr_build_tlas_ex follows it.
+ * rr_query_rays: host arrays, blocking (like rr_trace_rays). */
+int  rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits);
+/* The same from device memory: n rays at a 16-byte aligned device pointer, n hits to a 4-byte aligned one
+ * (RR_ERR_INVALID_ARGUMENT otherwise; n == 0 is RR_OK).  Stream-ordered on the context's stream (rr_set_stream): the kernel
+ * reads the rays after the work queued on that stream before the call, nothing is synchronised and nothing allocated.  The
+ * rays must stay valid, and the hits must not be read, until that stream has run the query. */
+int  rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void* d_hits);
 
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel

@@ -22,6 +22,8 @@ BUILD_PREFER_FAST_TRACE = 0x4
 BUILD_PREFER_FAST_BUILD = 0x8
 BUILD_ALLOW_UPDATE = 0x1
 BUILD_PERFORM_UPDATE = 0x20
+RAY_FLAG_ACCEPT_FIRST_HIT = 0x4          # RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH (query_rays only)
+RAY_FLAG_SKIP_CLOSEST_HIT_SHADER = 0x8   # accepted, no effect
 RAY_FLAG_CULL_BACK = 0x10
 RAY_FLAG_CULL_FRONT = 0x20
 INSTANCE_FLAG_CULL_DISABLE = 0x1
@@ -31,7 +33,7 @@ VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("norm", "<f4", 3), ("uv", "<f4
 INSTANCE_DTYPE = np.dtype([("transform", "<f4", 12), ("instance_id_mask", "<u4"), ("hitgroup_flags", "<u4"),
                            ("blas", "<u8")])
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4"),
-                      ("flags", "<u4"), ("pad", "<u4", 3)])
+                      ("flags", "<u4"), ("instance_mask", "<u4"), ("pad", "<u4", 2)])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("inst", "<u4"), ("hit", "<u4")])
 # 64-byte BVH2 node: per plane the pair (child 0, child 1); c = child refs (>= 0 node, < 0 leaf ~ref)
 NODE_DTYPE = np.dtype([("lox", "<f4", 2), ("loy", "<f4", 2), ("loz", "<f4", 2), ("hix", "<f4", 2),
@@ -39,6 +41,7 @@ NODE_DTYPE = np.dtype([("lox", "<f4", 2), ("loy", "<f4", 2), ("loz", "<f4", 2), 
 TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("prim", "<u4"), ("e1", "<f4", 3), ("pad1", "<u4"),
                       ("e2", "<f4", 3), ("pad2", "<u4")])
 assert VERTEX_DTYPE.itemsize == 32 and INSTANCE_DTYPE.itemsize == 64 and RAY_DTYPE.itemsize == 48
+assert RAY_DTYPE.fields["instance_mask"][1] == 36
 QNODE_DTYPE = np.dtype([("lox", "<f2", 2), ("loy", "<f2", 2), ("loz", "<f2", 2), ("hix", "<f2", 2),
                         ("hiy", "<f2", 2), ("hiz", "<f2", 2), ("c", "<i4", 2)])
 assert QNODE_DTYPE.itemsize == 32
@@ -132,6 +135,8 @@ SYMBOLS = {
     "rr_timing_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "rr_kernel_time": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rr_trace_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "rr_query_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "rr_query_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

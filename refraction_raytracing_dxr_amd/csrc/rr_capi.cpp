@@ -26,6 +26,7 @@ static_assert(sizeof(rr_vertex) == 32, "Vertex stride (Mesh.cpp:45)");
 static_assert(sizeof(rr_instance_desc) == 64, "D3D12_RAYTRACING_INSTANCE_DESC");
 static_assert(sizeof(rr_scene_constants) == 80, "SceneConstants");
 static_assert(sizeof(rr_ray) == sizeof(rr_ray_dev) && sizeof(rr_hit) == sizeof(rr_hit_dev), "ray/hit ABI");
+static_assert(offsetof(rr_ray, instance_mask) == 36 && offsetof(rr_ray_dev, instance_mask) == 36, "rr_ray.instance_mask");
 
 // Optional roctx ranges around the coarse steps (build, dispatch, assemble) so that `rocprofv3 --marker-trace`
 // shows them next to the kernels.  The marker library is looked up at run time; without it the calls are no-ops.
@@ -376,6 +377,12 @@ void fill_scene(const rr_context* ctx, SceneDev& sc)
     sc.scale = ctx->scene_scale;
     sc.env = ctx->d_env;
     sc.env_w = ctx->env_w; sc.env_h = ctx->env_h;
+}
+
+// InstanceMask of a single-identity scene's instance (the query kernels test it per ray before the walk)
+uint32_t inst0_mask(const rr_context* ctx)
+{
+    return ctx->single_identity ? (ctx->inst_host[0].instance_id_mask >> 24) & 0xffu : 0xffu;
 }
 
 // deepest traversal stack the scene can need (near child followed, far child pushed)
@@ -2086,6 +2093,43 @@ int rr_trace_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
     RR_HIP(hipMemcpyAsync(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     if (err) return fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, "traversal stack overflow");
+    return RR_OK;
+}
+
+int rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!rays || !hits) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays: null arrays");
+    if (n > ctx->ray_cap) {
+        RR_HIP(hipStreamSynchronize(ctx->stream));
+        dfree(ctx->d_rays); dfree(ctx->d_hits);
+        ctx->ray_cap = 0;
+        RR_HIP(hipMalloc(&ctx->d_rays, (size_t)n * sizeof(rr_ray_dev)));
+        RR_HIP(hipMalloc(&ctx->d_hits, (size_t)n * sizeof(rr_hit_dev)));
+        ctx->ray_cap = n;
+    }
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(hipMemcpyAsync(ctx->d_rays, rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(launch_query_rays(sc, ctx->d_rays, n, ctx->d_hits, inst0_mask(ctx), scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
+    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits, (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void* d_hits)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_device: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!d_rays || !d_hits || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_device: need a 16-byte aligned ray and a 4-byte aligned hit pointer");
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(launch_query_rays(sc, static_cast<const rr_ray_dev*>(d_rays), n, static_cast<rr_hit_dev*>(d_hits), inst0_mask(ctx),
+                             scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
     return RR_OK;
 }
 

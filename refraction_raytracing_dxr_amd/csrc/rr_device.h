@@ -115,6 +115,7 @@ __device__ __forceinline__ bool first_active_lane()
 }
 
 constexpr uint32_t CULL_BACK = 0x10u, CULL_FRONT = 0x20u;
+constexpr uint32_t RAY_FLAG_ACCEPT_FIRST_HIT = 0x4u;      // RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH (the query kernels)
 
 // ---- box-test ray setup ----------------------------------------------------------------------------
 // The box test is exempt from the arithmetic contract: it only has to be CONSERVATIVE (never cull a
@@ -339,10 +340,13 @@ __device__ __forceinline__ bool leaf_phase_due(int n_in)
 // "while-while" form: the lanes descend internal nodes (near child first, far child pushed) until enough of
 // them hold a leaf or have finished (leaf_phase_due); then the (expensive) triangle test is executed once for
 // all lanes that hold a leaf.
-template <bool STATS, class E, class NS = GlobalNodes>
+// ANY (the query kernels): a lane with any_lane set ends its walk at the first triangle it accepts (DXR
+// RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH); ANY = false is the closest-hit loop of the render and trace kernels.
+template <bool STATS, class E, class NS = GlobalNodes, bool ANY = false>
 __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const TriRec* __restrict__ tris, int root, const BoxRay& br,
                                           f3 O, f3 D, float tmin, uint32_t cull, uint32_t inst, HitRec& best, E* stk,
-                                          TravCounters& cnt, const Diag dg = Diag{ nullptr }, const NS ns = NS{})
+                                          TravCounters& cnt, const Diag dg = Diag{ nullptr }, const NS ns = NS{},
+                                          bool any_lane = false)
 {
     E* top = stk;
     int node = root;
@@ -369,7 +373,8 @@ __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const
             diag_trip(dg, 1);
             if (STATS) { cnt.tris++; if (first_active_lane()) cnt.leaf_trips++; }
             tri_test(tris, (uint32_t)~node, O, D, tmin, cull, inst, best);
-            if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
+            if (ANY && any_lane && best.hit) { top = stk; node = TRAV_DONE; }
+            else if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
         }
         if (__ballot(node != TRAV_DONE) == 0ull) break;
     }
@@ -518,13 +523,26 @@ __device__ __forceinline__ InstDev inst_record(const InstDev* __restrict__ insts
 // primitive), so the order instances are visited in does not matter.  (Rounds 1-2 walked both levels in ONE loop over the
 // flattened pool, so that a lane leaving an instance need not wait for the others; with a leaf part that tests triangles,
 // enters and leaves instances it cost more than the waiting: C4 0.96 -> 0.90 ms, C5 on this kernel 6.8 -> 6.1.)
-template <bool STATS, bool TLAS, class E = uint32_t, class NS = GlobalNodes>
+//
+// QUERY (the query kernels, rr_query_rays): TraceRay(Scene, flags, ray_mask, ...).  An instance is visited only if
+// (InstanceMask & ray_mask) != 0; with TLAS = false the caller has already tested the one instance's mask, and ray_mask == 0
+// means the lane's ray passes nothing.  any_lane: the lane ends its walk, both levels, at the first triangle it accepts.
+// QUERY = false is the render and trace kernels' code (mask 0xff, closest hit).
+template <bool STATS, bool TLAS, class E = uint32_t, class NS = GlobalNodes, bool QUERY = false>
 __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, float tmin, float tmax, uint32_t flags,
                                             HitRec& best, E* stk_e, TravCounters& cnt,
-                                            const Diag dg = Diag{ nullptr }, const NS ns = NS{})
+                                            const Diag dg = Diag{ nullptr }, const NS ns = NS{},
+                                            uint32_t ray_mask = 0xffu, bool any_lane = false)
 {
     best.t = tmax; best.hit = false; best.prim = 0; best.leaf = 0; best.inst = 0; best.U = 0.0f; best.V = 0.0f;
     best.ad = 1.0f;
+    if (!TLAS && QUERY) {
+        const BoxRay br = box_ray(O, D, sc.blas0.scale, sc.blas0.grid);
+        walk_blas<STATS, E, NS, true>(sc.blas0.nodes, sc.blas0.tris, (ray_mask & 0xffu) ? 0 : TRAV_DONE, br, O, D, tmin, flags, 0u,
+                                      best, stk_e, cnt, dg, ns, any_lane);
+        if (best.hit) hit_attributes(sc.blas0.tris, O, D, best);
+        return;
+    }
     if (!TLAS) {      // the reference's scene: one identity instance, mask 1, flags 0 (RefractionDemo.cpp:324-334)
         trace_blas<STATS, E, NS>(sc.blas0, O, D, tmin, flags, 0u, best, stk_e, cnt, dg, ns);
         return;
@@ -544,7 +562,7 @@ __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, floa
         if (STATS && first_active_lane()) cnt.leaf_trips++;
         const uint32_t ii = (uint32_t)~node - sc.n_pool_tris;               // a leaf of the top level is an instance
         const InstDev in = inst_record(sc.insts, ii);
-        if (in.mask & 0xffu) {
+        if (in.mask & (QUERY ? ray_mask : 0xffu)) {
             uint32_t f = flags;
             if (in.flags & 0x1u) f &= ~(CULL_BACK | CULL_FRONT);
             else if (in.flags & 0x2u) {
@@ -554,9 +572,11 @@ __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, floa
             f3 Oc = O, Dc = D;
             if (!in.identity) { Oc = xform_point(in.inv, O); Dc = xform_dir(in.inv, D); }
             const BoxRay bi = box_ray(Oc, Dc, in.scale, in.grid);
-            walk_blas<STATS, E, GlobalNodes>(nodes, sc.pool_tris, (int)in.root, bi, Oc, Dc, tmin, f, ii, best, top, cnt);
+            walk_blas<STATS, E, GlobalNodes, QUERY>(nodes, sc.pool_tris, (int)in.root, bi, Oc, Dc, tmin, f, ii, best, top, cnt,
+                                                    Diag{ nullptr }, GlobalNodes{}, any_lane);
         }
-        if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
+        if (QUERY && any_lane && best.hit) node = TRAV_DONE;
+        else if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
     }
     if (best.hit) {
         const InstDev in = inst_record(sc.insts, best.inst);

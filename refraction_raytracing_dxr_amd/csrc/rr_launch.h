@@ -6,7 +6,7 @@
 namespace rr {
 
 // device twins of rr_ray / rr_hit (include/rrdxr.h), same layout
-struct alignas(16) rr_ray_dev { float origin[3]; float tmin; float dir[3]; float tmax; uint32_t flags; uint32_t pad[3]; };
+struct alignas(16) rr_ray_dev { float origin[3]; float tmin; float dir[3]; float tmax; uint32_t flags; uint32_t instance_mask; uint32_t pad[2]; };
 struct rr_hit_dev { float t, u, v; uint32_t prim, inst, hit; };
 static_assert(sizeof(rr_ray_dev) == 48 && sizeof(rr_hit_dev) == 24, "ABI layout");
 
@@ -29,6 +29,10 @@ const char* last_stream_kernel_name();
 const char* last_render_kernel_name();
 hipError_t launch_trace_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t* err,
                              int stack, hipStream_t s);
+// the query kernels (rr_query_rays[_device]): instance masks and per-lane first-hit termination; inst0_mask: the InstanceMask of
+// a single-identity scene's instance
+hipError_t launch_query_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t inst0_mask, int stack,
+                             hipStream_t s);
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

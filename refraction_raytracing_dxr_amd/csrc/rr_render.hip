@@ -530,6 +530,39 @@ __global__ __launch_bounds__(256) void k_trace_rays(SceneDev sc, const rr_ray_de
     if (err) atomicOr(error_flag, 1u);
 }
 
+// TraceRay(Scene, flags, instance_mask, ...) on caller rays (rr_query_rays, rr_query_rays_device): the trace kernel with the
+// ray's InstanceInclusionMask and RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH read per lane, so one launch may mix first-hit and
+// closest-hit rays (an instantiation without the per-lane test was measured no faster on closest-hit batches: DESIGN 5.4).
+// inst0_mask: the InstanceMask of the one instance of a TLAS = false scene (a kernel argument rather than a SceneDev field:
+// the render kernels' register allocation follows SceneDev's layout).
+template <int STACK, bool TLAS>
+__global__ __launch_bounds__(256) void k_query_rays(SceneDev sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t inst0_mask)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    uint32_t* stk = lds + wave * (STACK * 64) + lane;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4* q = reinterpret_cast<const uint4*>(rays + i);
+    const uint4 o = q[0], d = q[1], f = q[2];                   // f: flags, instance_mask, pad[2]
+    const uint32_t flags = f.x;
+    const uint32_t mask = TLAS ? f.y : (f.y & inst0_mask);
+    const bool any = (flags & RAY_FLAG_ACCEPT_FIRST_HIT) != 0u;
+    HitRec h;
+    TravCounters cnt; cnt.nodes = 0; cnt.tris = 0;
+    trace_scene<false, TLAS, uint32_t, GlobalNodes, true>(sc, mk3(__uint_as_float(o.x), __uint_as_float(o.y), __uint_as_float(o.z)),
+                                                          mk3(__uint_as_float(d.x), __uint_as_float(d.y), __uint_as_float(d.z)),
+                                                          __uint_as_float(o.w), __uint_as_float(d.w), flags, h, stk, cnt,
+                                                          Diag{ nullptr }, GlobalNodes{}, mask, any);
+    rr_hit_dev r;
+    r.hit = h.hit ? 1u : 0u;
+    r.t = h.hit ? h.t : __uint_as_float(d.w);
+    r.u = h.hit ? h.U / h.ad : 0.0f;
+    r.v = h.hit ? h.V / h.ad : 0.0f;
+    r.prim = h.prim; r.inst = h.inst;
+    hits[i] = r;
+}
+
 // rank 0 after the RCCL gather: [world][max_tiles][32*32] RGBA8 -> W*H raster
 __global__ __launch_bounds__(256) void k_assemble_tiles(const uint32_t* __restrict__ gathered, uint32_t* __restrict__ frame,
                                                         uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles,
@@ -811,6 +844,21 @@ hipError_t launch_trace_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_
     if (n == 0) return hipSuccess;
     if (stack <= 31) { if (sc.single_identity) launch_trace_st<31, false>(sc, rays, n, hits, err, s); else launch_trace_st<31, true>(sc, rays, n, hits, err, s); }
     else             { if (sc.single_identity) launch_trace_st<64, false>(sc, rays, n, hits, err, s); else launch_trace_st<64, true>(sc, rays, n, hits, err, s); }
+    return hipGetLastError();
+}
+
+template <int STACK, bool TLAS>
+static void launch_query_st(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t inst0_mask, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_query_rays<STACK, TLAS>), dim3((n + 255u) / 256u), dim3(256), 4 * STACK * 64 * 4, s, sc, rays, n, hits, inst0_mask);
+}
+
+hipError_t launch_query_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t inst0_mask, int stack,
+                             hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    if (stack <= 31) { if (sc.single_identity) launch_query_st<31, false>(sc, rays, n, hits, inst0_mask, s); else launch_query_st<31, true>(sc, rays, n, hits, inst0_mask, s); }
+    else             { if (sc.single_identity) launch_query_st<64, false>(sc, rays, n, hits, inst0_mask, s); else launch_query_st<64, true>(sc, rays, n, hits, inst0_mask, s); }
     return hipGetLastError();
 }
 

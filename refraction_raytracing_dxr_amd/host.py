@@ -81,6 +81,38 @@ def make_instances(transforms=None, meshes=None, masks=None, flags=None):
     return inst
 
 
+def pack_rays(origin, dir, tmin, tmax, flags=0, instance_mask=0xff):
+    """Ray records for Renderer.query_rays / trace_rays.  origin, dir: [n, 3]; tmin, tmax, flags, instance_mask: [n] or
+    scalars.  numpy inputs give a RAY_DTYPE array; torch tensors give a contiguous [n, 12] int32 tensor holding the raw
+    48-byte records (the float fields as their bits) on the inputs' device.  The default mask, 0xff, passes every instance."""
+    if type(origin).__module__.startswith("torch"):
+        import torch
+        o = origin.to(torch.float32).reshape(-1, 3)
+        n, dev = o.shape[0], o.device
+        out = torch.zeros((n, 12), dtype=torch.int32, device=dev)
+        f = out.view(torch.float32)
+
+        def col(x, dt):
+            return torch.as_tensor(x, dtype=dt, device=dev).expand(n) if not torch.is_tensor(x) or x.dim() == 0 \
+                else x.to(device=dev, dtype=dt).reshape(n)
+        f[:, 0:3] = o
+        f[:, 3] = col(tmin, torch.float32)
+        f[:, 4:7] = dir.to(device=dev, dtype=torch.float32).reshape(n, 3)
+        f[:, 7] = col(tmax, torch.float32)
+        out[:, 8] = col(flags, torch.int64).to(torch.int32)
+        out[:, 9] = col(instance_mask, torch.int64).to(torch.int32)
+        return out
+    o = np.asarray(origin, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"] = o
+    rays["dir"] = np.asarray(dir, np.float32).reshape(-1, 3)
+    rays["tmin"] = tmin
+    rays["tmax"] = tmax
+    rays["flags"] = np.asarray(flags, np.int64) & 0xffffffff
+    rays["instance_mask"] = np.asarray(instance_mask, np.int64) & 0xffffffff
+    return rays
+
+
 class Mesh:
     """Mesh.hpp:14-25.  verts: structured array of 32-byte Vertex; indices: uint32."""
 
@@ -366,6 +398,33 @@ class Renderer:
         rays = np.ascontiguousarray(rays, RAY_DTYPE)
         hits = np.zeros(len(rays), HIT_DTYPE)
         self._ck(self._L.rr_trace_rays(self._h, rays.ctypes.data, len(rays), hits.ctypes.data), "rr_trace_rays")
+        return hits
+
+    def query_rays(self, rays):
+        """TraceRay(Scene, flags, instance_mask, ...) on caller rays: the ray's InstanceInclusionMask (RAY_DTYPE's instance_mask)
+        and RAY_FLAG_ACCEPT_FIRST_HIT are honoured (trace_rays ignores both).  Build rays with pack_rays.
+
+        rays: a RAY_DTYPE numpy array -> a HIT_DTYPE array (host arrays, blocking); or a contiguous [n, 12] int32 or float32
+        torch tensor of raw ray records on this renderer's GPU -> a new [n, 6] tensor of the same dtype and device holding the
+        raw hit records (t, u, v as float bits, then prim, inst, hit), computed on the renderer's stream without passing
+        through the host and without waiting for it.  The query is ordered after the work already queued on that stream only:
+        rays produced on another stream (torch's current stream, say) must be finished or ordered first -- call
+        set_stream(torch.cuda.current_stream().cuda_stream) once, or torch.cuda.current_stream().synchronize() before the call
+        -- and the hits are ready once that stream has run the query."""
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("query_rays: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("query_rays: need a contiguous [n, 12] int32 or float32 tensor")
+            hits = torch.empty((t.shape[0], 6), dtype=t.dtype, device=t.device)
+            self._ck(self._L.rr_query_rays_device(self._h, C.c_void_p(t.data_ptr()), t.shape[0], C.c_void_p(hits.data_ptr())),
+                     "rr_query_rays_device")
+            return hits
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        self._ck(self._L.rr_query_rays(self._h, rays.ctypes.data, len(rays), hits.ctypes.data), "rr_query_rays")
         return hits
 
     def env_lookup(self, dirs):

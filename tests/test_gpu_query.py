@@ -1,0 +1,427 @@
+"""GPU: ray queries (rr_query_rays / rr_query_rays_device, Renderer.query_rays) -- DXR TraceRay's InstanceInclusionMask and
+RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH -- against rr_trace_rays and the CPU oracle.
+
+Closest-hit queries are compared bit for bit with the oracle's brute force (masks: an oracle scene holding only the instances the
+ray's mask selects).  A first-hit query may return any accepted triangle, so it is checked by what the contract fixes: the same
+`hit` as the closest-hit query, t no smaller, and t/u/v bit-identical to the oracle's trace of a scene made of the one reported
+triangle (same instance transform and flags, same tmin/tmax/cull).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle as O
+import refraction_raytracing_dxr_amd as rr
+from conftest import procedural_env
+
+pytestmark = pytest.mark.gpu
+
+RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE = 1, 5
+ANY = rr.RAY_FLAG_ACCEPT_FIRST_HIT
+CULLS = [rr.RAY_FLAG_CULL_BACK, rr.RAY_FLAG_CULL_FRONT, 0]
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    r = rr.Renderer(0)
+    yield r
+    r.close()
+
+
+def load(name):
+    m = rr.Mesh()
+    assert m.load(O.asset(name))
+    return m.verts, m.indices
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def oracle_scene(meshes, instances=None):
+    s = O.Scene()
+    for verts, idx in meshes:
+        s.add_mesh(verts, idx)
+    if instances is not None:
+        inst = np.zeros(len(instances), O.INSTANCE_DTYPE)
+        inst["transform"] = instances["transform"]
+        inst["id_mask"] = instances["instance_id_mask"]
+        inst["hitgroup_flags"] = instances["hitgroup_flags"]
+        inst["blas"] = instances["blas"]
+        s.set_instances(inst)
+    return s
+
+
+def gpu_scene(gpu, meshes, instances=None):
+    """uploads + builds; instances["blas"] index `meshes`; -> mesh ids"""
+    ids = []
+    for verts, idx in meshes:
+        mid = gpu.upload_mesh(verts, idx)
+        gpu.build_blas(mid)
+        ids.append(mid)
+    if instances is None:
+        instances = rr.make_instances(meshes=[ids[0]])
+    else:
+        instances = instances.copy()
+        instances["blas"] = [ids[int(b)] for b in instances["blas"]]
+    gpu.build_tlas(instances)
+    return ids
+
+
+def random_rays(n, seed, radius=4.0, extent=1.2, masks=(0xff,), any_frac=0.0):
+    rng = np.random.default_rng(seed)
+    o = rng.normal(size=(n, 3))
+    o = o / np.linalg.norm(o, axis=1, keepdims=True) * rng.uniform(0.0, radius, (n, 1))
+    d = rng.uniform(-extent, extent, (n, 3)) - o
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    tmin = np.where(rng.random(n) < 0.5, 1e-4, 1e-3)
+    tmax = rng.choice([100.0, 1000.0, 3.0], n)
+    flags = rng.choice(CULLS, n, p=[0.35, 0.35, 0.3]) | np.where(rng.random(n) < any_frac, ANY, 0)
+    return rr.pack_rays(o, d, tmin, tmax, flags=flags, instance_mask=rng.choice(list(masks), n))
+
+
+def oracle_trace(s, rays, k):
+    return s.trace(rays["origin"][k], rays["dir"][k], float(rays["tmin"][k]), float(rays["tmax"][k]), int(rays["flags"][k]) & 0x30,
+                   use_bvh=0)
+
+
+def check_closest(hits, s, rays, sel=None, inst_map=None):
+    """hits[k] == the oracle's brute-force closest hit for every k in sel; inst_map: oracle instance -> GPU instance"""
+    n_hit = 0
+    for k in (range(len(rays)) if sel is None else sel):
+        h = oracle_trace(s, rays, k)
+        g = hits[k]
+        assert bool(g["hit"]) == bool(h.hit), "ray %d" % k
+        if h.hit:
+            n_hit += 1
+            assert g["prim"] == h.prim, "ray %d" % k
+            assert g["inst"] == (h.inst if inst_map is None else inst_map[h.inst]), "ray %d" % k
+            assert bits(g["t"]) == bits(h.t) and bits(g["u"]) == bits(h.u) and bits(g["v"]) == bits(h.v), "ray %d" % k
+    return n_hit
+
+
+def check_first_hits(first, closest, rays, meshes, instances=None, sample=300, seed=0):
+    """first: a first-hit query of `rays`, closest: the closest-hit query of the same rays.  -> rays where first.t > closest.t"""
+    assert np.array_equal(first["hit"], closest["hit"])
+    miss = first["hit"] == 0
+    assert first[miss].tobytes() == closest[miss].tobytes()
+    hit = ~miss
+    assert np.all(first["t"][hit] >= closest["t"][hit])
+    assert np.all(first["t"][hit] < rays["tmax"][hit])
+    ks = np.flatnonzero(hit)
+    rng = np.random.default_rng(seed)
+    for k in rng.choice(ks, min(sample, len(ks)), replace=False):
+        g = first[k]
+        if instances is None:
+            verts, idx = meshes[0]
+            inst = None
+        else:
+            verts, idx = meshes[int(instances["blas"][g["inst"]])]
+            inst = instances[g["inst"]:g["inst"] + 1].copy()
+            inst["blas"] = 0
+            inst["instance_id_mask"] = 1 << 24
+        tri = np.ascontiguousarray(verts[idx[3 * int(g["prim"]):3 * int(g["prim"]) + 3]])
+        s = oracle_scene([(tri, np.arange(3, dtype=np.uint32))], inst)
+        h = oracle_trace(s, rays, k)
+        assert h.hit, "ray %d" % k
+        assert bits(g["t"]) == bits(h.t) and bits(g["u"]) == bits(h.u) and bits(g["v"]) == bits(h.v), "ray %d" % k
+    return int(np.sum(first["t"][hit] > closest["t"][hit]))
+
+
+def _soup(kind, n, seed):
+    rng = np.random.default_rng(seed)
+    if kind == "flat":
+        P = rng.uniform(-2, 2, (n, 3, 3)); P[..., 2] = 0.25
+    elif kind == "mixed":
+        c = rng.uniform(-3, 3, (n, 1, 3))
+        P = c + rng.normal(size=(n, 3, 3)) * rng.choice([1e-4, 1e-2, 0.3, 2.0], (n, 1, 1))
+        P[::17, 1] = P[::17, 0]
+    else:                                  # "line"
+        t = rng.uniform(-2, 2, (n, 1, 1))
+        P = t * np.array([1.0, 1.0, 1.0]) + rng.normal(size=(n, 3, 3)) * 0.01
+    v = np.zeros(n * 3, rr.VERTEX_DTYPE)
+    v["position"] = P.reshape(-1, 3).astype(np.float32)
+    v["norm"] = (0, 0, 1)
+    return v, np.arange(n * 3, dtype=np.uint32)
+
+
+def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
+    c, sn = np.cos(rot), np.sin(rot)
+    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
+    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
+
+
+MASKED_INSTANCES = dict(
+    transforms=[xf(0, 0, 0), xf(0, 0, -2.5, (0.5, 0.8, 0.5), 0.4), xf(0.3, 0.2, 2.4, (0.7, 0.7, 0.7), -1.0),
+                xf(0, 1.9, 0, (0.4, 0.4, 0.4), 0.2), xf(0, 0, 0, (1, 1, 1), 0.9), xf(0, -1.8, 0.5, (0.5, 0.5, 0.5)),
+                xf(-2.2, 0, 0, (0.6, 0.6, 0.6))],
+    meshes=[1, 0, 1, 0, 1, 0, 0], masks=[1, 2, 4, 0x80, 0x81, 0x06, 0], flags=[0, 0, 0, 1, 0, 2, 0])
+# instance 4 is a rotated copy of instance 0 at the same place; instance 6 has InstanceMask 0 and is never visited
+RAY_MASKS = [0xff, 1, 2, 4, 0x80, 0x81, 0x7f, 0x06, 0x102, 0]
+
+
+def masked_scene(gpu):
+    meshes = [load("cube.obj"), load("monkey.obj")]
+    inst = rr.make_instances(**MASKED_INSTANCES)
+    gpu_scene(gpu, meshes, inst)
+    return meshes, inst
+
+
+# ------------------------------------------------------------------------------------------------- 1. closest hit, mask 0xff
+@pytest.mark.parametrize("name,n", [("cube.obj", 3000), ("sphere.obj", 3000), ("monkey.obj", 3000), ("shell.obj", 3000),
+                                    ("ott.obj", 2000)])
+def test_closest_query_equals_trace_rays_and_brute_force(gpu, name, n):
+    m = load(name)
+    gpu_scene(gpu, [m])
+    rays = random_rays(n, seed=len(name))
+    q = gpu.query_rays(rays)
+    assert q.tobytes() == gpu.trace_rays(rays).tobytes()
+    assert check_closest(q, oracle_scene([m]), rays) > n // 20
+
+
+@pytest.mark.parametrize("kind,n", [("flat", 300), ("mixed", 700), ("line", 500), ("mixed", 9)])
+def test_closest_query_on_awkward_soups(gpu, kind, n):
+    verts, idx = _soup(kind, n, seed=n + len(kind))
+    gpu_scene(gpu, [(verts, idx)])
+    P = verts["position"].astype(np.float64)
+    ctr, ext = (P.min(0) + P.max(0)) / 2, max(float((P.max(0) - P.min(0)).max()), 1e-3)
+    rng = np.random.default_rng(3)
+    o = ctr + rng.normal(size=(1200, 3)) * ext
+    d = P[rng.integers(0, len(P), 1200)] + rng.normal(size=(1200, 3)) * ext * 0.02 - o
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    rays = rr.pack_rays(o, d, 1e-4, 1e6, flags=rng.choice(CULLS, 1200))
+    q = gpu.query_rays(rays)
+    assert q.tobytes() == gpu.trace_rays(rays).tobytes()
+    assert check_closest(q, oracle_scene([(verts, idx)]), rays) >= (20 if n >= 100 else 0)
+
+
+# ------------------------------------------------------------------------------------------------- 2. instance masks
+def test_instance_masks_select_instances_like_dxr(gpu):
+    meshes, inst = masked_scene(gpu)
+    rays = random_rays(6000, seed=21, radius=5.0, extent=2.5, masks=RAY_MASKS)
+    q = gpu.query_rays(rays)
+    inst_masks = inst["instance_id_mask"] >> 24
+    seen = set()
+    for rm in RAY_MASKS:
+        sel = np.flatnonzero(rays["instance_mask"] == rm)
+        keep = np.flatnonzero(inst_masks & rm & 0xff)
+        if len(keep) == 0:
+            assert not q["hit"][sel].any(), hex(rm)
+            continue
+        s = oracle_scene(meshes, inst[keep])
+        n_hit = check_closest(q, s, rays, sel=sel, inst_map=keep)
+        assert n_hit > 0, hex(rm)
+        seen |= set(int(i) for i in q["inst"][sel][q["hit"][sel] != 0])
+    assert seen == {0, 1, 2, 3, 4, 5}
+    # rr_trace_rays keeps treating every ray as 0xff
+    full = rays.copy()
+    full["instance_mask"] = 0xff
+    assert gpu.trace_rays(rays).tobytes() == gpu.query_rays(full).tobytes()
+
+
+@pytest.mark.parametrize("inst_mask", [1, 0x80])
+def test_single_instance_scene_masks(gpu, inst_mask):
+    m = load("monkey.obj")
+    mid = gpu.upload_mesh(*m)
+    gpu.build_blas(mid)
+    gpu.build_tlas(rr.make_instances(meshes=[mid], masks=[inst_mask]))
+    rays = random_rays(3000, seed=5)
+    closest = gpu.trace_rays(rays)
+    assert closest["hit"].sum() > 300
+    for rm in (0xff, inst_mask, inst_mask | 0x100, 0xff ^ inst_mask, 0):
+        r = rays.copy()
+        r["instance_mask"] = rm
+        q = gpu.query_rays(r)
+        if rm & inst_mask & 0xff:
+            assert q.tobytes() == closest.tobytes(), hex(rm)
+        else:
+            assert not q["hit"].any(), hex(rm)
+            assert np.array_equal(bits(q["t"]), bits(r["tmax"]))
+        r["flags"] |= ANY
+        assert np.array_equal(gpu.query_rays(r)["hit"], q["hit"]), hex(rm)
+
+
+# ------------------------------------------------------------------------------------------------- 3. first hit
+@pytest.mark.parametrize("name", ["monkey.obj", "ott.obj", "instanced"])
+def test_first_hit_query(gpu, name):
+    if name == "instanced":
+        meshes, inst = masked_scene(gpu)
+        rays = random_rays(5000, seed=31, radius=5.0, extent=2.5, masks=RAY_MASKS)
+    else:
+        meshes, inst = [load(name)], None
+        gpu_scene(gpu, meshes)
+        rays = random_rays(5000, seed=32)
+    closest = gpu.query_rays(rays)
+    any_rays = rays.copy()
+    any_rays["flags"] |= ANY
+    first = gpu.query_rays(any_rays)
+    further = check_first_hits(first, closest, any_rays, meshes, inst, seed=len(name))
+    assert further > 0                     # first-hit termination does return non-closest triangles
+    # deterministic
+    assert gpu.query_rays(any_rays).tobytes() == first.tobytes()
+    # SKIP_CLOSEST_HIT_SHADER (0x8) changes nothing
+    r8 = any_rays.copy()
+    r8["flags"] |= 0x8
+    assert gpu.query_rays(r8).tobytes() == first.tobytes()
+    # mixed batches: per ray what the pure batches give
+    mixed = rays.copy()
+    pick = np.random.default_rng(1).random(len(rays)) < 0.5
+    mixed["flags"][pick] |= ANY
+    m = gpu.query_rays(mixed)
+    assert m[pick].tobytes() == first[pick].tobytes()
+    assert m[~pick].tobytes() == closest[~pick].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------- 4. device path
+def to_dev(rays, gpu, dtype="int32"):
+    import torch
+    a = rays.view(np.int32).reshape(-1, 12).copy()
+    t = torch.from_numpy(a).to("cuda:%d" % gpu.device)
+    return t.view(torch.float32) if dtype == "float32" else t
+
+
+def from_dev(t):
+    return np.ascontiguousarray(t.cpu().numpy()).view(np.uint32).view(rr.HIT_DTYPE).reshape(-1)
+
+
+def test_device_query_equals_host_query(gpu):
+    import torch
+    masked_scene(gpu)
+    rays = random_rays(20000, seed=41, radius=5.0, extent=2.5, masks=RAY_MASKS, any_frac=0.5)
+    host = gpu.query_rays(rays)
+    for dt in ("int32", "float32"):
+        t = to_dev(rays, gpu, dt)
+        torch.cuda.synchronize()
+        out = gpu.query_rays(t)
+        gpu.wait()
+        assert out.dtype == t.dtype and out.device == t.device and tuple(out.shape) == (len(rays), 6)
+        assert from_dev(out).tobytes() == host.tobytes(), dt
+    e = gpu.query_rays(torch.empty((0, 12), dtype=torch.int32, device="cuda:%d" % gpu.device))
+    assert tuple(e.shape) == (0, 6)
+
+
+def test_device_query_of_4m_rays(gpu):
+    import torch
+    gpu_scene(gpu, [load("monkey.obj")])
+    n = 4 * 1024 * 1024 + 17
+    rays = random_rays(n, seed=42, masks=(0xff, 1, 2), any_frac=0.5)
+    host = gpu.query_rays(rays)
+    assert host["hit"].sum() > n // 10
+    t = to_dev(rays, gpu)
+    torch.cuda.synchronize()
+    out = gpu.query_rays(t)
+    gpu.wait()
+    assert from_dev(out).tobytes() == host.tobytes()
+
+
+def test_device_query_is_ordered_on_torch_stream(gpu):
+    import torch
+    masked_scene(gpu)
+    dev = "cuda:%d" % gpu.device
+    gpu.set_stream(torch.cuda.current_stream().cuda_stream)
+    try:
+        torch.cuda.synchronize()
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        n = 1 << 20
+        big = torch.randn((4096, 4096), device=dev, generator=g)
+        big = big @ big                                     # queue work ahead of the rays on the same stream
+        o = torch.randn((n, 3), device=dev, generator=g) * 3.0 + big[0, 0] * 0.0
+        d = torch.rand((n, 3), device=dev, generator=g) * 2.4 - 1.2 - o
+        d = d / d.norm(dim=1, keepdim=True)
+        masks = torch.tensor(RAY_MASKS, device=dev)[torch.randint(0, len(RAY_MASKS), (n,), device=dev, generator=g)]
+        flags = torch.where(torch.rand(n, device=dev, generator=g) < 0.5, ANY, 0) | rr.RAY_FLAG_CULL_BACK
+        t = rr.pack_rays(o, d, 1e-4, 100.0, flags=flags, instance_mask=masks)
+        out = gpu.query_rays(t)                             # no synchronisation between producing the rays and the query
+        torch.cuda.current_stream().synchronize()
+        rays = np.ascontiguousarray(t.cpu().numpy()).view(rr.RAY_DTYPE).reshape(-1)
+        assert np.all(rays["tmin"] == np.float32(1e-4)) and np.all(rays["instance_mask"] <= 0x102)
+        host = gpu.query_rays(rays)
+        assert host["hit"].sum() > n // 20
+        assert from_dev(out).tobytes() == host.tobytes()
+    finally:
+        gpu.reset_stream()
+
+
+def test_device_query_errors(gpu):
+    import torch
+    dev = "cuda:%d" % gpu.device
+    fresh = rr.Renderer(gpu.device)
+    try:
+        rays = random_rays(64, seed=1)
+        t = to_dev(rays, fresh)
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(rays)                                              # nothing built
+        assert e.value.status == RR_ERR_STATE
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(t)
+        assert e.value.status == RR_ERR_STATE
+        verts, idx = load("cube.obj")
+        mid = fresh.upload_mesh(verts, idx)
+        fresh.build_blas(mid, allow_update=True)
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(t)                                                 # BLAS built, no TLAS yet
+        assert e.value.status == RR_ERR_STATE
+        fresh.build_tlas(rr.make_instances(meshes=[mid]), allow_update=True)
+        fresh.query_rays(t)
+        fresh.update_mesh_vertices(mid, verts)
+        fresh.build_blas(mid, update=True)
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(t)                                                 # BLAS updated, TLAS not
+        assert e.value.status == RR_ERR_STATE
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(rays)
+        assert e.value.status == RR_ERR_STATE
+        fresh.build_tlas(rr.make_instances(meshes=[mid]), update=True)
+        ok = from_dev(fresh.query_rays(t))
+        fresh.wait()
+        assert ok.tobytes() == fresh.query_rays(rays).tobytes()
+        # misaligned pointers
+        flat = torch.zeros(64 * 12 + 4, dtype=torch.int32, device=dev)
+        flat[1:1 + 64 * 12] = t.reshape(-1)
+        mis = flat[1:1 + 64 * 12].view(64, 12)
+        assert mis.is_contiguous() and mis.data_ptr() % 16 == 4
+        with pytest.raises(rr.RRError) as e:
+            fresh.query_rays(mis)
+        assert e.value.status == RR_ERR_INVALID_ARGUMENT
+        hits = torch.zeros(64 * 6 + 1, dtype=torch.int32, device=dev)
+        L = rr.lib()
+        assert L.rr_query_rays_device(fresh._h, C.c_void_p(t.data_ptr()), 64, C.c_void_p(hits.data_ptr() + 2)) == RR_ERR_INVALID_ARGUMENT
+        assert L.rr_query_rays_device(fresh._h, C.c_void_p(t.data_ptr()), 0, C.c_void_p(hits.data_ptr() + 2)) == 0
+        # wrong device, shape, dtype, layout
+        for bad in (t.cpu(), t[:, :8].contiguous(), t.reshape(-1), t.to(torch.float64),
+                    torch.zeros((64, 16), dtype=torch.int32, device=dev)[:, :12]):
+            with pytest.raises(ValueError):
+                fresh.query_rays(bad)
+    finally:
+        fresh.close()
+
+
+# ------------------------------------------------------------------------------------------------- 5. after a refit
+def test_queries_after_refit_equal_a_fresh_build(gpu):
+    verts, idx = load("monkey.obj")
+    P = verts["position"].astype(np.float64)
+    dv = verts.copy()
+    P[:, 1] += 0.15 * np.sin(4.0 * P[:, 0]) * np.cos(3.0 * P[:, 2])
+    dv["position"] = P.astype(np.float32)
+    inst = rr.make_instances(transforms=[xf(0, 0, 0), xf(0.4, 0.1, -2.2, (0.6, 0.6, 0.6), 0.7)], meshes=[0, 0], masks=[1, 2])
+    mid = gpu.upload_mesh(verts, idx)
+    gpu.build_blas(mid, allow_update=True)
+    ii = inst.copy()
+    ii["blas"] = mid
+    gpu.build_tlas(ii, allow_update=True)
+    gpu.update_mesh_vertices(mid, dv)
+    gpu.build_blas(mid, update=True)
+    gpu.build_tlas(ii, update=True)
+    rays = random_rays(6000, seed=51, radius=5.0, extent=2.0, masks=(0xff, 1, 2, 3, 0))
+    first_rays = rays.copy()
+    first_rays["flags"] |= ANY
+    refit_closest, refit_first = gpu.query_rays(rays), gpu.query_rays(first_rays)
+    gpu_scene(gpu, [(dv, idx)], inst)
+    fresh_closest, fresh_first = gpu.query_rays(rays), gpu.query_rays(first_rays)
+    assert refit_closest.tobytes() == fresh_closest.tobytes()
+    assert refit_closest["hit"].sum() > 600
+    # a first hit depends on the hierarchy (a refit keeps the old one), so each is checked against the contract
+    check_first_hits(refit_first, refit_closest, first_rays, [(dv, idx)], inst, seed=1)
+    check_first_hits(fresh_first, fresh_closest, first_rays, [(dv, idx)], inst, seed=2)

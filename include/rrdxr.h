@@ -309,7 +309,12 @@ typedef struct rr_mesh_partition {
  * their cameras; the same on every rank), so that the caller can size its buffers: frame f's mesh tiles of this rank go to
  * d_mesh_tiles + f * mesh_stride_bytes (slot s at s * 3072: RGB8, max_mesh_tiles_per_rank slots, unused ones zeroed) -- the send
  * buffer of the gather --, and on rank 0 its background tiles to d_bg_tiles + f * bg_stride_bytes (n_bg_tiles slots; other
- * ranks pass NULL).  rr_assemble_frames_mesh_rgb8 puts gathered mesh tiles and rank 0's background tiles back into rasters. */
+ * ranks pass NULL).  rr_assemble_frames_mesh_rgb8 puts gathered mesh tiles and rank 0's background tiles back into rasters.
+ * RR_DISPATCH_DEBUG_NO_CULL is honoured here too: the launch then renders the whole-frame partition, the one
+ * rr_host_mesh_partition(bounds, NULL, ...) returns (rect_w == 0, no background tiles, every tile a mesh tile), so the caller
+ * sizes its buffers from that partition and passes it to rr_assemble_frames_mesh_rgb8.  The buffers are checked against the
+ * partition the launch renders: ones sized from rr_mesh_partition_for_orbit are refused (RR_ERR_INVALID_ARGUMENT) wherever the
+ * two differ, before anything is launched. */
 int  rr_mesh_partition_for_orbit(rr_context* ctx, uint32_t width, uint32_t height, float angle, float angle_step, uint32_t n_frames,
                                  float fov_y, float aspect, float zn, float zf, rr_mesh_partition* out);
 int  rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispatch_params* params,

@@ -1148,8 +1148,9 @@ int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uin
     return RR_OK;
 }
 
-// mesh-tile partition (rr_mesh_partition): where rank 0's background tiles of a dispatch go
-struct MeshOut { uint32_t* bg; size_t bg_stride_elems; };
+// mesh-tile partition (rr_mesh_partition): the partition the caller's tile buffers were checked against, and where rank 0's
+// background tiles of a dispatch go
+struct MeshOut { const rr_mesh_partition* part; uint32_t* bg; size_t bg_stride_elems; };
 
 inline bool timed_request(const rr_dispatch_params& p) { return (p.flags & RR_DISPATCH_TIME_KERNEL) != 0; }
 
@@ -1173,9 +1174,10 @@ int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t dep
     memset(&part, 0, sizeof part);
     uint32_t n_mesh_local = 0;
     if (mesh) {         // mesh tiles dealt round robin, background tiles to rank 0: this rank's tiles are its mesh tiles, then those
-        if (!ext_tiles || !(p.flags & RR_DISPATCH_TILES_RGB8) || !h_cams) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: RGB8 tile buffers and host constants");
-        if (rr_host_mesh_partition(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : h_cams, depth, width, height, ctx->tile_world, &part) != RR_OK)
-            return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition");
+        if (!ext_tiles || !(p.flags & RR_DISPATCH_TILES_RGB8) || !h_cams || !mesh->part) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: RGB8 tile buffers and host constants");
+        // the partition is the caller's (its buffers were sized and checked against it), never recomputed here
+        part = *mesh->part;
+        if (part.world != ctx->tile_world || part.tiles_x != tiles_x || part.n_tiles != n_tiles) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: not one of this launch");
         n_mesh_local = rr_host_mesh_tiles_of_rank(&part, ctx->tile_rank);
         if (ctx->tile_rank == 0 && part.n_bg_tiles && !mesh->bg) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: rank 0 needs the background tile buffer");
         local = n_mesh_local + (ctx->tile_rank == 0 ? part.n_bg_tiles : 0);
@@ -1801,8 +1803,11 @@ int rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t 
         if (rc != RR_OK) return fail(ctx, rc, "render_orbit: camera");
         *angle += angle_step;
     }
+    // the one partition of this launch: its buffers are checked against it and the kernel renders it (DEBUG_NO_CULL: the whole
+    // frame is mesh tiles, as rr_host_mesh_partition(bounds, NULL, ...) says)
     rr_mesh_partition part;
-    if (rr_host_mesh_partition(ctx->scene_bounds, cams.data(), n_frames, width, height, ctx->tile_world, &part) != RR_OK)
+    if (rr_host_mesh_partition(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : cams.data(), n_frames, width, height,
+                               ctx->tile_world, &part) != RR_OK)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition");
     if (mesh_stride_bytes < (uint64_t)part.max_mesh_tiles_per_rank * TILE * TILE * 3 ||
         (ctx->tile_rank == 0 && part.n_bg_tiles && (!d_bg_tiles || bg_stride_bytes < (uint64_t)part.n_bg_tiles * TILE * TILE * 3)))
@@ -1823,7 +1828,7 @@ int rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t 
     ctx->d_cams = ctx->lane_cams[lane];
     ctx->cams_cap = ctx->lane_cams_cap[lane];
     int rc = upload_cams(ctx, cams.data(), n_frames);
-    const MeshOut mo = { (uint32_t*)d_bg_tiles, (size_t)(bg_stride_bytes / 4) };
+    const MeshOut mo = { &part, (uint32_t*)d_bg_tiles, (size_t)(bg_stride_bytes / 4) };
     if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, n_frames, ctx->d_cams, cams.data(), p, (uint32_t*)d_mesh_tiles, (size_t)(mesh_stride_bytes / 4), true, 0, 0, &mo);
     hipError_t e = rc == RR_OK ? hipEventRecord(ctx->lane_done[lane], ctx->stream) : hipSuccess;
     ctx->lane_cams[lane] = ctx->d_cams;

@@ -1,0 +1,628 @@
+"""Every render kernel, forced one at a time, against the CPU oracle.
+
+The dispatch code picks one of four kernels for a launch (rr_stats.render_kernel): 0 k_render_fused, 1 k_render_lds,
+2 k_render_paths, 7 k_stream_*.  The measured choice renders the first dispatch of a shape with k_render_fused, so tests that
+dispatch each shape once only ever reach that kernel.  Here RR_DEBUG_KERNEL (read at rr_create) forces each kernel in turn and
+every dispatch asserts which kernel rendered it: the forced one wherever it can render the launch, k_render_fused where it
+cannot (the fall-back is silent).  Each compared frame is then held against the oracle's path-weight mode (the kernels'
+summation order):
+  * the float accumulator bit for bit (as uint32), the RGBA8 frame byte for byte;
+  * the recursion's counters (rays, hits, misses, terminal hits, TIR) equal.  node_visits / tri_tests count visits of the
+    GPU's own hierarchy, which the oracle does not build, so they are not compared here.
+Batches are also checked slice by slice against single dispatches of the same kernel, and their counters against the sum.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle as O
+import refraction_raytracing_dxr_amd as rr
+from conftest import procedural_env
+from test_gpu_parity import CULL_KINDS, CULL_SIZES, FRAME_CASES, adversarial_constants
+
+pytestmark = pytest.mark.gpu
+
+FUSED, LDS, PATHS, STREAM = 0, 1, 2, 7
+KERNEL_ID = {"fused": FUSED, "lds": LDS, "paths": PATHS, "stream": STREAM}
+COUNTERS = ("rays", "hits", "misses", "terminal_hits", "tir")
+DEBUG_VARS = ("RR_DEBUG_KERNEL", "RR_DEBUG_SHAPE", "RR_DEBUG_TICKET", "RR_DEBUG_GROUP_TRACE", "RR_DEBUG_STACK", "RR_DEBUG_TLAS32",
+              "RR_DEBUG_TILE_ORDER", "RR_DEBUG_ASYNC", "RR_DEBUG_DIAG")
+TALLY = collections.Counter()           # oracle comparisons per asserted render_kernel, over the module (printed by each test)
+
+
+@pytest.fixture
+def make_renderer(monkeypatch):
+    """make(kernel, **env) -> a Renderer created with RR_DEBUG_KERNEL=kernel (and the given RR_DEBUG_* switches), closed at
+    teardown"""
+    made = []
+
+    def make(kernel, **env):
+        for k in DEBUG_VARS:
+            monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv("RR_DEBUG_KERNEL", kernel)
+        for k, v in env.items():
+            monkeypatch.setenv(k, str(v))
+        r = rr.Renderer(0)
+        made.append(r)
+        return r
+    yield make
+    for r in made:
+        r.close()
+
+
+# ------------------------------------------------------------------------------------------------------- scenes
+def load(name):
+    m = rr.Mesh()
+    assert m.load(O.asset(name))
+    return m.verts, m.indices
+
+
+def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
+    c, sn = np.cos(rot), np.sin(rot)
+    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
+    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
+
+
+class Scene:
+    """meshes [(verts, indices)], instances (blas = index into meshes; None: the reference's one identity instance), env"""
+
+    def __init__(self, key, meshes, env, instances=None):
+        self.key, self.meshes, self.env, self.instances = key, meshes, env, instances
+        self._oracle = None
+        self.single = instances is None
+        lo, hi = [], []
+        for k in range(1 if instances is None else len(instances)):
+            P = meshes[0 if instances is None else int(instances["blas"][k])][0]["position"].astype(np.float64)
+            if instances is not None:
+                T = instances["transform"][k].reshape(3, 4).astype(np.float64)
+                P = P @ T[:, :3].T + T[:, 3]
+            lo.append(P.min(axis=0)); hi.append(P.max(axis=0))
+        self.bounds = (C.c_float * 6)(*[float(v) for v in np.min(lo, axis=0)], *[float(v) for v in np.max(hi, axis=0)])
+
+    def load_gpu(self, r):
+        ids = []
+        for v, i in self.meshes:
+            mid = r.upload_mesh(v, i)
+            r.build_blas(mid)
+            ids.append(mid)
+        if self.instances is None:
+            inst = rr.make_instances(meshes=[ids[0]])
+        else:
+            inst = self.instances.copy()
+            inst["blas"] = [ids[int(b)] for b in inst["blas"]]
+        r.build_tlas(inst)
+        r.upload_envmap(self.env)
+        r.set_tile_partition(0, 1)
+
+    def oracle(self):
+        if self._oracle is None:
+            s = O.Scene()
+            for v, i in self.meshes:
+                s.add_mesh(v, i)
+            if self.instances is not None:
+                inst = np.zeros(len(self.instances), O.INSTANCE_DTYPE)
+                inst["transform"] = self.instances["transform"]
+                inst["id_mask"] = self.instances["instance_id_mask"]
+                inst["hitgroup_flags"] = self.instances["hitgroup_flags"]
+                inst["blas"] = self.instances["blas"]
+                s.set_instances(inst)
+            s.set_envmap(self.env)
+            self._oracle = s
+        return self._oracle
+
+    def n_tris(self):
+        return len(self.meshes[0][1]) // 3
+
+
+_ORACLE_CACHE = {}
+
+
+def oracle_frame(scene, sc, W, H, kw, tonemap=0, region=None):
+    """the oracle's path-weight render of one slice, cached across kernels (same scene, constants, size and parameters)"""
+    M, cam = np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
+    key = (scene.key, M.tobytes(), cam.tobytes(), W, H, tuple(sorted(kw.items())), tonemap, region)
+    if key not in _ORACLE_CACHE:
+        if len(_ORACLE_CACHE) > 400:
+            _ORACLE_CACHE.clear()
+        _ORACLE_CACHE[key] = scene.oracle().render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, tonemap=tonemap, **kw),
+                                                   region=region)
+    return _ORACLE_CACHE[key]
+
+
+def orbit(angle, n, step=0.13, radius=1.0, height=None):
+    """n distinct orbit constants starting at `angle` (a batch's slices each get their own camera)"""
+    out = []
+    for f in range(n):
+        sc = rr.camera_orbit(angle + step * f)
+        sc.camera_loc[0] *= radius
+        sc.camera_loc[2] *= radius
+        if height is not None:
+            sc.camera_loc[1] = height
+        out.append(sc)
+    return out
+
+
+# ------------------------------------------------------------------------------------ which kernel can render a launch
+def _lds_shape_fits(node_bytes, stack_entries, min_shape):
+    """rr_render.hip lds_kernel_shape: 12x2, 16x2, 16x1 waves x workgroups per CU within 160 KiB of LDS per CU"""
+    for nw, wgs in ((12, 2), (16, 2), (16, 1))[min_shape:]:
+        if node_bytes + nw * stack_entries * 64 * 2 <= 160 * 1024 // wgs - 512:
+            return True
+        if min_shape <= 0:
+            return False
+    return False
+
+
+def screen_rect(scene, cams, W, H):
+    arr = (rr._capi.SceneConstants * len(cams))(*cams)
+    rect = (C.c_uint32 * 4)()
+    assert rr.lib().rr_host_screen_rect(scene.bounds, arr, len(cams), W, H, rect) == 0
+    return list(rect)
+
+
+def expected_kernel(kernel, scene, W, H, cams, kw, need, flags=0, shape=0, sharded=False):
+    """the kernel the forced switch must have rendered the launch with (rr_capi.cpp dispatch_impl, "the candidates")"""
+    depth = len(cams)
+    refl = kw.get("max_reflect", 2)
+    if kernel == "lds":
+        n = scene.n_tris()
+        n_tiles = ((W + 31) // 32) * ((H + 31) // 32)
+        ok = (scene.single and n < 32768 and _lds_shape_fits(max(n - 1, 1) * 32, need + 1, shape) and n_tiles * depth * depth < 1 << 30
+              and not sharded)
+        return LDS if ok else FUSED
+    if kernel == "paths":
+        r = [0, 0, W, H] if flags & rr.DISPATCH_DEBUG_NO_CULL else screen_rect(scene, cams, W, H)
+        ok = not sharded and refl <= 2 and need <= 39 and r[2] > r[0] and r[3] > r[1] and depth <= 2
+        return PATHS if ok else FUSED
+    if kernel == "stream":
+        ok = not scene.single and refl <= 2 and kw.get("max_refract", 5) <= 62 and need <= 39
+        return STREAM if ok else FUSED
+    return FUSED
+
+
+# ------------------------------------------------------------------------------------------------- dispatch + compare
+def dispatch(r, W, H, cams, kw, flags):
+    p = rr.default_params(flags=flags | rr.DISPATCH_COLLECT_STATS, **kw)
+    if len(cams) == 1:
+        r.set_camera(cams[0])
+        r.dispatch_rays(W, H, p)
+    else:
+        r.dispatch_rays_batch(W, H, cams, p)
+    want_f = bool(flags & rr.DISPATCH_FLOAT_OUTPUT)
+    frames = []
+    for f in range(len(cams)):
+        got = r.read_frame(want_float=want_f, slice=f)
+        frames.append(got if want_f else (got, None))
+    st = r.stats()
+    assert st.traversal_overflow == 0 and st.stats_valid
+    return frames, st
+
+
+def counters(st):
+    return tuple(int(getattr(st, k)) for k in COUNTERS)
+
+
+def check_slice(rgba, f32, ref, tag):
+    assert np.all(rgba[..., 3] == 255), tag
+    if f32 is not None:
+        assert np.all(f32[..., 3] == 1.0), tag
+        d = np.argwhere(f32[..., :3].view(np.uint32) != ref["rgb"].view(np.uint32))
+        assert len(d) == 0, "%s: %d float channels differ, first at %s: %r / %r" % (tag, len(d), d[0], f32[tuple(d[0])], ref["rgb"][tuple(d[0])])
+    d = np.argwhere(rgba != ref["rgba8"])
+    assert len(d) == 0, "%s: %d RGBA8 bytes differ, first at %s: %r / %r" % (tag, len(d), d[0], rgba[tuple(d[0])], ref["rgba8"][tuple(d[0])])
+
+
+def check_launch(r, kernel, scene, W, H, cams, kw, flags, tally, shape=0, oracle_slices=None, tag=""):
+    """One launch of len(cams) slices on the forced kernel, asserted to have rendered it, against the oracle:
+    depth 1 -- the frame and the counters; depth > 1 -- every slice and the counter sum against single dispatches of the same
+    kernel, the oracle on oracle_slices (default: first, middle, last) with those singles' counters."""
+    depth = len(cams)
+    tm = 1 if flags & rr.DISPATCH_TONEMAP_REINHARD else 0
+    frames, st = dispatch(r, W, H, cams, kw, flags)
+    want = expected_kernel(kernel, scene, W, H, cams, kw, st.bvh_depth, flags, shape)
+    assert st.render_kernel == want, "%s: rendered by kernel %d, expected %d" % (tag, st.render_kernel, want)
+    if depth == 1:
+        ref = oracle_frame(scene, cams[0], W, H, kw, tm)
+        check_slice(frames[0][0], frames[0][1], ref, tag)
+        assert counters(st) == counters(ref["stats"]), (tag, counters(st), counters(ref["stats"]))
+        tally[st.render_kernel] += 1
+        return st.render_kernel
+    if oracle_slices is None:
+        oracle_slices = sorted({0, depth // 2, depth - 1})
+    total = np.zeros(len(COUNTERS), np.int64)
+    for f in range(depth):
+        one, s1 = dispatch(r, W, H, [cams[f]], kw, flags)
+        assert s1.render_kernel == expected_kernel(kernel, scene, W, H, [cams[f]], kw, s1.bvh_depth, flags, shape), (tag, f, s1.render_kernel)
+        assert np.array_equal(frames[f][0], one[0][0]), "%s: slice %d of the batch != its single dispatch" % (tag, f)
+        if frames[f][1] is not None:
+            assert np.array_equal(frames[f][1].view(np.uint32), one[0][1].view(np.uint32)), "%s: slice %d (float)" % (tag, f)
+        total += counters(s1)
+        if f in oracle_slices:
+            ref = oracle_frame(scene, cams[f], W, H, kw, tm)
+            check_slice(frames[f][0], frames[f][1], ref, "%s slice %d" % (tag, f))
+            assert counters(s1) == counters(ref["stats"]), (tag, f, counters(s1), counters(ref["stats"]))
+            tally[st.render_kernel] += 1
+    assert tuple(total) == counters(st), (tag, tuple(total), counters(st))
+    return st.render_kernel
+
+
+def report(name, tally):
+    TALLY.update(tally)
+    print("%s: oracle comparisons by render_kernel %s; module so far %s" % (name, dict(tally), dict(TALLY)))
+
+
+# --------------------------------------------------------------------------------- 1. single-mesh scenes (fused, lds, paths)
+FLAG_CASES = [rr.DISPATCH_FLOAT_OUTPUT, 0, rr.DISPATCH_FLOAT_OUTPUT | rr.DISPATCH_TONEMAP_REINHARD]
+SINGLE_MESH_VARIANTS = [("fused", {}), ("lds", {}), ("lds", {"RR_DEBUG_SHAPE": 1}), ("lds", {"RR_DEBUG_SHAPE": 2}),
+                        ("lds", {"RR_DEBUG_TICKET": 19}), ("paths", {}), ("paths", {"RR_DEBUG_GROUP_TRACE": 0})]
+
+
+@pytest.mark.parametrize("kernel,env", SINGLE_MESH_VARIANTS,
+                         ids=["%s%s" % (k, "".join("-%s=%s" % (n[9:].lower(), v) for n, v in e.items())) for k, e in SINGLE_MESH_VARIANTS])
+def test_single_mesh_frames_match_the_oracle(make_renderer, kernel, env):
+    """FRAME_CASES (ragged sizes, parked rays, TIR on entry, no refraction, ...) plus float / RGBA8-only / tone-mapped output:
+    24-slice batches on fused and LDS (every workgroup shape and ticket order), Depth 1 and 2 on paths (with and without
+    group tracing)."""
+    r = make_renderer(kernel, **env)
+    shape = int(env.get("RR_DEBUG_SHAPE", 0))
+    tally = collections.Counter()
+    depths = (1, 2) if kernel == "paths" else (24,)
+    cases = [(name, W, H, a, kw, rr.DISPATCH_FLOAT_OUTPUT) for name, W, H, a, kw in FRAME_CASES]
+    cases += [("monkey.obj", 256, 192, 0.3, dict(max_refract=8), fl) for fl in FLAG_CASES[1:]]
+    cases += [("sphere.obj", 160, 120, 0.9, dict(max_refract=6, max_reflect=1), FLAG_CASES[2])]
+    scenes = {}
+    n_forced = 0
+    for name, W, H, angle, kw, flags in cases:
+        if name not in scenes:
+            scenes[name] = Scene(name, [load(name)], procedural_env(256, 128, seed=3))
+        sc = scenes[name]
+        sc.load_gpu(r)
+        for depth in depths:
+            got = check_launch(r, kernel, sc, W, H, orbit(angle, depth), kw, flags, tally, shape=shape,
+                               tag="%s %s %dx%d depth %d %s flags %#x" % (kernel, name, W, H, depth, kw, flags))
+            n_forced += got == KERNEL_ID[kernel]
+    report("single mesh %s %s" % (kernel, env), tally)
+    # the forced kernel really rendered the matrix: every case it supports (paths: all but max_reflect 3; lds: all but ott.obj
+    # and meshes whose tree leaves no room beside the stacks)
+    assert n_forced >= {"fused": len(cases), "lds": len(cases) - 4, "paths": 2 * (len(cases) - 1)}[kernel], (n_forced, len(cases), dict(tally))
+    if kernel == "paths":
+        assert tally[FUSED] >= 2          # max_reflect 3: the fall-back, asserted
+
+
+def test_lds_does_not_render_what_it_cannot_hold(make_renderer):
+    """the 15 472-triangle subdivided monkey does not fit LDS: forcing LDS renders it with k_render_fused (asserted), which
+    still matches the oracle"""
+    from refraction_raytracing_dxr_amd.synth import subdivide
+    v, i = load("monkey.obj")
+    v16, i16 = subdivide(v, 2)
+    r = make_renderer("lds")
+    sc = Scene("monkey16k", [(v16, i16)], procedural_env(128, 64, seed=5))
+    sc.load_gpu(r)
+    tally = collections.Counter()
+    assert check_launch(r, "lds", sc, 128, 96, orbit(0.4, 3), dict(max_refract=8), rr.DISPATCH_FLOAT_OUTPUT, tally, tag="monkey16k") == FUSED
+    report("lds monkey16k", tally)
+
+
+# ------------------------------------------------------------------------------------ 2. two-level scenes (fused, stream)
+def c4_scene():
+    meshes = [load("shell.obj"), load("cube.obj"), load("ott.obj")]
+    inst = rr.make_instances(transforms=[xf(0, 0, 0), xf(0, 0, -4.0), xf(0, 0, 4.0)], meshes=[0, 1, 2])
+    return Scene("c4", meshes, procedural_env(256, 128, seed=4), inst)
+
+
+def c5_scene(n_side=8, pitch=3.0, scale=0.9, key="c5"):
+    xs = [xf(pitch * (i - (n_side - 1) / 2), 0, pitch * (j - (n_side - 1) / 2), (scale,) * 3) for i in range(n_side) for j in range(n_side)]
+    return Scene(key, [load("monkey.obj")], procedural_env(256, 128, seed=5), rr.make_instances(transforms=xs, meshes=[0] * len(xs)))
+
+
+def mixed_scene():
+    """test_stream_renderer_renders_the_same_frames' first scene: rotations, non-uniform scale, cull flags, a zero mask"""
+    meshes = [load("cube.obj"), load("monkey.obj"), load("sphere.obj")]
+    inst = rr.make_instances(transforms=[xf(0, 0, 0), xf(0, 0, -2.5, (0.5, 0.8, 0.5), 0.4), xf(0.3, 0.2, 2.4, (0.7, 0.7, 0.7), -1.0),
+                                         xf(0, 1.9, 0, (0.4, 0.4, 0.4), 0.2), xf(0, -1.8, 0.5, (0.5, 0.5, 0.5))],
+                             meshes=[1, 0, 1, 2, 0], masks=[1, 1, 0xff, 1, 0], flags=[0, 0, 2, 1, 0])
+    return Scene("mixed", meshes, procedural_env(256, 128, seed=9), inst)
+
+
+def dense_scene():
+    """the 100-monkey grid filling the frame"""
+    xs = [xf(1.1 * (i - 4.5), 0.3 * ((i + j) % 3), 1.1 * (j - 4.5), (0.4, 0.4, 0.4), 0.3 * i) for i in range(10) for j in range(10)]
+    return Scene("dense", [load("monkey.obj")], procedural_env(256, 128, seed=9), rr.make_instances(transforms=xs, meshes=[0] * 100))
+
+
+def small_scene():
+    """two small instances near the origin: a small screen rectangle, most tiles background"""
+    inst = rr.make_instances(transforms=[xf(0.1, 0.05, 0, (0.12, 0.12, 0.12), 0.5), xf(-0.1, 0, 0.1, (0.08, 0.1, 0.08), 2.0)], meshes=[0, 1])
+    return Scene("small", [load("monkey.obj"), load("sphere.obj")], procedural_env(256, 128, seed=9), inst)
+
+
+# scene -> (W, H, start angle, orbit radius factor)
+TWO_LEVEL = {"c4": (c4_scene, 240, 135, 0.01, 1.6), "c5": (c5_scene, 200, 112, 0.7, 5.0), "mixed": (mixed_scene, 211, 149, 0.3, 1.0),
+             "dense": (dense_scene, 256, 192, 0.2, 1.0)}
+BOUNCES = [(0, 0), (3, 0), (1, 2), (12, 2), (16, 2), (4, 3)]          # (max_refract, max_reflect); 4/3: stream cannot, fused renders
+
+
+@pytest.mark.parametrize("scene_name", list(TWO_LEVEL))
+@pytest.mark.parametrize("kernel", ["fused", "stream"])
+def test_two_level_scenes_match_the_oracle(make_renderer, kernel, scene_name):
+    """C4, the C5 8x8 grid, the mixed instanced scene and the dense 100-monkey grid at Depth 1, 3 and 16, every bounce limit,
+    float / RGBA8-only / tone-mapped output; every stream pass without a queue overflow (dispatch() asserts
+    traversal_overflow == 0 on each launch)"""
+    make, W, H, angle, radius = TWO_LEVEL[scene_name]
+    sc = make()
+    r = make_renderer(kernel)
+    sc.load_gpu(r)
+    tally = collections.Counter()
+    n_forced = n = 0
+    for depth in (1, 3, 16):
+        for bi, (refr, refl) in enumerate(BOUNCES):
+            kw = dict(max_refract=refr, max_reflect=refl)
+            flags = FLAG_CASES[(bi + depth) % 3]
+            cams = orbit(angle + 0.05 * bi, depth, step=0.09, radius=radius)
+            got = check_launch(r, kernel, sc, W, H, cams, kw, flags, tally,
+                               tag="%s %s depth %d %s flags %#x" % (kernel, scene_name, depth, kw, flags))
+            n += 1
+            n_forced += got == KERNEL_ID[kernel]
+    report("two-level %s %s" % (kernel, scene_name), tally)
+    if kernel == "stream":
+        assert n_forced == n - 3 and tally[FUSED] >= 3, (n_forced, n, dict(tally))   # all but the three 4/3 launches
+    else:
+        assert n_forced == n
+
+
+@pytest.mark.parametrize("kernel", ["fused", "stream"])
+def test_full_size_config5_window_matches_the_oracle(make_renderer, kernel):
+    """C5 at full size (1 024 monkeys, 3840x2160, 16 bounces) on the forced kernel: an oracle window in the grid"""
+    sc = c5_scene(n_side=32, scale=1.0, key="c5full")
+    sc.env = procedural_env(512, 256, seed=6)
+    r = make_renderer(kernel)
+    sc.load_gpu(r)
+    cam = rr.camera_orbit(0.4)
+    for k in (0, 2):
+        cam.camera_loc[k] *= 14.0
+    cam.camera_loc[1] = 12.0
+    W, H, kw = 3840, 2160, dict(max_refract=16)
+    (frame, _), = dispatch(r, W, H, [cam], kw, 0)[0]
+    st = r.stats()
+    assert st.render_kernel == KERNEL_ID[kernel] and st.pixels == W * H
+    for x0, y0 in ((1592, 1440), (2072, 1376)):         # windows on the grid's monkeys (the frame's centre falls between them)
+        ref = oracle_frame(sc, cam, W, H, kw, region=(x0, y0, x0 + 48, y0 + 32))
+        check_slice(frame[y0:y0 + 32, x0:x0 + 48], None, dict(rgba8=ref["rgba8"][y0:y0 + 32, x0:x0 + 48]), "c5 full %s (%d, %d)" % (kernel, x0, y0))
+        assert ref["stats"].hits > 48 * 32 and ref["stats"].tir > 0
+    report("c5 full %s" % kernel, collections.Counter({st.render_kernel: 2}))
+
+
+# ----------------------------------------------------------------------------------------------- 3. sharded stream launches
+def _alloc(n):
+    import torch
+    return torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+
+
+def _orbit_angles(angle, n, step=0.01):
+    """the angles rr_render_orbit* give its frames (float accumulation, as the C loop does)"""
+    out, a = [], np.float32(angle)
+    for _ in range(n):
+        out.append(float(a))
+        a = np.float32(a + np.float32(step))
+    return out
+
+
+@pytest.mark.parametrize("kernel", ["fused", "stream"])
+def test_sharded_tile_partition_assembles_to_the_oracle(make_renderer, kernel):
+    """world 3, round-robin tiles: every rank on the forced kernel (asserted), the gathered tiles assembled == the oracle, the
+    ranks' counters summed == the oracle's"""
+    import torch
+    sc = mixed_scene()
+    r = make_renderer(kernel)
+    sc.load_gpu(r)
+    W, H, world, kw = 211, 149, 3, dict(max_refract=6)
+    cam = rr.camera_orbit(0.45)
+    mx = rr.dist.max_local_tiles(W, H, world)
+    gathered = _alloc(world * mx * 4096)
+    total = np.zeros(len(COUNTERS), np.int64)
+    r.set_camera(cam)
+    for rank in range(world):
+        r.set_tile_partition(rank, world)
+        r.dispatch_rays(W, H, rr.default_params(flags=rr.DISPATCH_COLLECT_STATS, **kw))
+        r.export_tiles(gathered.data_ptr() + rank * mx * 4096)
+        r.wait()
+        st = r.stats()
+        assert st.render_kernel == KERNEL_ID[kernel] and st.traversal_overflow == 0
+        total += counters(st)
+    r.assemble_tiles(gathered.data_ptr(), world)
+    r.wait()
+    frame = r.read_frame()
+    r.set_tile_partition(0, 1)
+    ref = oracle_frame(sc, cam, W, H, kw)
+    check_slice(frame, None, ref, "tiles world 3 %s" % kernel)
+    assert tuple(total) == counters(ref["stats"])
+    torch.cuda.synchronize()
+    report("sharded tiles %s" % kernel, collections.Counter({KERNEL_ID[kernel]: 1}))
+
+
+def mesh_sharded_frames(r, sc, W, H, F, angle, world, kw, no_cull=False):
+    """every rank of a mesh-tile partitioned launch on this context, in turn, then the assembly -> (uint8 [F, H, W, 4], counters
+    summed over the ranks, the kernels that rendered them, the partition)"""
+    import torch
+    flags = rr.DISPATCH_COLLECT_STATS | (rr.DISPATCH_DEBUG_NO_CULL if no_cull else 0)
+    r.set_tile_partition(0, world)
+    if no_cull:          # the whole-frame partition: what a NO_CULL launch renders and what its buffers are sized by
+        part = rr._capi.MeshPartition()
+        assert rr.lib().rr_host_mesh_partition(sc.bounds, None, F, W, H, world, C.byref(part)) == 0
+    else:
+        part = r.mesh_partition_for_orbit(W, H, F, angle=angle)
+    fs, bs = max(part.max_mesh_tiles_per_rank, 1) * 3072, max(part.n_bg_tiles, 1) * 3072
+    gat, bg, frames = _alloc(world * F * fs), _alloc(F * bs), _alloc(F * W * H * 4)
+    torch.cuda.synchronize()
+    total, kernels = np.zeros(len(COUNTERS), np.int64), []
+    for rank in range(world):
+        r.set_tile_partition(rank, world)
+        r.render_orbit_mesh_sharded(W, H, F, C.c_void_p(gat.data_ptr() + rank * F * fs), fs, C.c_void_p(bg.data_ptr()) if rank == 0 else None, bs,
+                                    angle=angle, params=rr.default_params(flags=flags, **kw))
+        r.lane_join(0)
+        r.wait()
+        st = r.stats()
+        assert st.traversal_overflow == 0
+        kernels.append(st.render_kernel)
+        total += counters(st)
+    r.set_tile_partition(0, world)
+    r.assemble_frames_mesh(C.c_void_p(gat.data_ptr()), F * fs, fs, C.c_void_p(bg.data_ptr()), bs, part, F, W, H, C.c_void_p(frames.data_ptr()), W * H * 4)
+    r.wait()
+    r.set_tile_partition(0, 1)
+    out = frames.cpu().numpy().reshape(F, H, W, 4).copy()
+    return out, total, kernels, part
+
+
+@pytest.mark.parametrize("world", [3, 8])
+@pytest.mark.parametrize("kernel", ["fused", "stream"])
+def test_mesh_partition_assembles_to_the_oracle(make_renderer, kernel, world):
+    """the mesh-tile partition at world 3 and 8, two frames per launch: assembled frames == the oracle's, counters too; and
+    with RR_DISPATCH_DEBUG_NO_CULL (the whole-frame partition, buffers sized by it) the same frames"""
+    sc = small_scene()
+    r = make_renderer(kernel)
+    sc.load_gpu(r)
+    (W, H), F, angle, kw = ((211, 149) if world == 3 else (320, 200)), 2, 0.3, dict(max_refract=6)
+    got, total, kernels, part = mesh_sharded_frames(r, sc, W, H, F, angle, world, kw)
+    assert kernels == [KERNEL_ID[kernel]] * world, kernels
+    assert part.rect_w > 0 and part.n_bg_tiles > 0           # a real rectangle: background tiles stay on rank 0
+    ref_total = np.zeros(len(COUNTERS), np.int64)
+    for k, a in enumerate(_orbit_angles(angle, F)):
+        ref = oracle_frame(sc, rr.camera_orbit(a), W, H, kw)
+        check_slice(got[k], None, ref, "mesh world %d %s frame %d" % (world, kernel, k))
+        ref_total += counters(ref["stats"])
+    assert np.array_equal(total, ref_total), (total, ref_total)
+    nc, nc_total, nc_kernels, nc_part = mesh_sharded_frames(r, sc, W, H, F, angle, world, kw, no_cull=True)
+    assert nc_part.rect_w == 0 and nc_part.n_bg_tiles == 0
+    assert nc_kernels == [KERNEL_ID[kernel]] * world, nc_kernels
+    assert np.array_equal(nc, got) and np.array_equal(nc_total, total)
+    report("mesh partition world %d %s" % (world, kernel), collections.Counter({KERNEL_ID[kernel]: F}))
+
+
+def test_no_cull_mesh_launch_refuses_buffers_sized_for_the_culled_partition(make_renderer):
+    """RR_DISPATCH_DEBUG_NO_CULL renders the whole-frame partition: tile buffers sized from rr_mesh_partition_for_orbit (the
+    culled one, fewer slots per rank) are refused before anything is launched -- the buffers keep their contents"""
+    import torch
+    sc = small_scene()
+    r = make_renderer("stream")
+    sc.load_gpu(r)
+    W, H, F, world, angle = 320, 200, 2, 3, 0.3
+    r.set_tile_partition(1, world)
+    part = r.mesh_partition_for_orbit(W, H, F, angle=angle)
+    whole = rr._capi.MeshPartition()
+    assert rr.lib().rr_host_mesh_partition(sc.bounds, None, F, W, H, world, C.byref(whole)) == 0
+    assert part.max_mesh_tiles_per_rank < whole.max_mesh_tiles_per_rank       # the two partitions differ
+    fs = part.max_mesh_tiles_per_rank * 3072
+    gat = torch.full((F * fs,), 0x5a, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    with pytest.raises(rr.RRError, match="RR_ERR_INVALID_ARGUMENT"):
+        r.render_orbit_mesh_sharded(W, H, F, C.c_void_p(gat.data_ptr()), fs, None, 0, angle=angle,
+                                    params=rr.default_params(flags=rr.DISPATCH_DEBUG_NO_CULL, max_refract=6))
+    r.wait()
+    torch.cuda.synchronize()
+    assert bool((gat == 0x5a).all())
+    # the same buffers without NO_CULL are the right size (rank 1 has no background buffer)
+    r.render_orbit_mesh_sharded(W, H, F, C.c_void_p(gat.data_ptr()), fs, None, 0, angle=angle, params=rr.default_params(max_refract=6))
+    r.lane_join(0)
+    r.wait()
+    r.set_tile_partition(0, 1)
+
+
+# ------------------------------------------------------------------------------------------------- 4. culling on lds / stream
+def _cull_case_bounds(scene):
+    lo = np.array(scene.bounds[:3], np.float64)
+    hi = np.array(scene.bounds[3:], np.float64)
+    return lo, hi
+
+
+@pytest.mark.parametrize("kernel", ["lds", "stream"])
+def test_background_culling_on_the_lds_and_stream_kernels(make_renderer, kernel):
+    """adversarial constants (test_background_culling_equals_tracing_every_primary_ray's) through k_render_lds -- 24-slice
+    batches, which take the two-phase ticket order (rectangle strips, then background tiles) -- and through the stream renderer
+    at Depth 1 and 3 (k_stream_background): every frame equals the same launch with RR_DISPATCH_DEBUG_NO_CULL, on the same
+    kernel; a subset against the oracle"""
+    if kernel == "lds":
+        sc = Scene("monkey-cull", [load("monkey.obj")], procedural_env(128, 64, seed=21))
+        plan = [(24, CULL_SIZES[k % len(CULL_SIZES)], k) for k in range(14)]
+    else:
+        sc = Scene("tlas-cull", [load("cube.obj"), load("monkey.obj")], procedural_env(128, 64, seed=21),
+                   rr.make_instances(transforms=[xf(0, 0, 0, (0.6,) * 3), xf(1.2, 0.3, -0.8, (0.3,) * 3), xf(-0.9, -0.4, 0.7, (0.4,) * 3)],
+                                     meshes=[1, 0, 1]))
+        plan = [(1 if k % 2 == 0 else 3, CULL_SIZES[(k // 2) % len(CULL_SIZES)], k) for k in range(42)]
+    r = make_renderer(kernel)
+    sc.load_gpu(r)
+    lo, hi = _cull_case_bounds(sc)
+    rng = np.random.default_rng(31 if kernel == "lds" else 32)
+    tally = collections.Counter()
+    culled_cases = 0
+    for depth, (W, H), k in plan:
+        kind = CULL_KINDS[k % len(CULL_KINDS)]
+        if depth >= 24:
+            # one adversarial camera, moved a little per slice: the launch's rectangle is the union over its slices, which
+            # independent cameras would spread over the whole frame (and no block would be culled)
+            base, M, cam = adversarial_constants(rng, kind, lo, hi)
+            cams = []
+            for f in range(depth):
+                cf = (cam * np.array([1.0 + 0.002 * f, 1.0, 1.0 - 0.001 * f, 1.0], np.float32)).astype(np.float32)
+                cams.append((rr.scene_constants(M, cf), M, cf))
+        else:
+            cams = [adversarial_constants(rng, kind, lo, hi) for _ in range(depth)]
+        kw = dict(max_refract=int(rng.choice([0, 2, 6])), max_reflect=int(rng.choice([0, 2])))
+        tag = "%s case %d: %s %dx%d depth %d %s" % (kernel, k, kind, W, H, depth, kw)
+        (fc, stc), (fn, stn) = [dispatch(r, W, H, [c[0] for c in cams], kw, rr.DISPATCH_FLOAT_OUTPUT | extra)
+                                for extra in (0, rr.DISPATCH_DEBUG_NO_CULL)]
+        assert stc.render_kernel == KERNEL_ID[kernel] and stn.render_kernel == KERNEL_ID[kernel], (tag, stc.render_kernel, stn.render_kernel)
+        # the culled branch ran: more blocks shaded as one Miss than with every primary ray traced
+        culled_cases += stc.background_waves > stn.background_waves
+        assert counters(stc) == counters(stn), tag
+        for f in range(depth):
+            assert np.array_equal(fc[f][0], fn[f][0]), (tag, f)
+            assert np.array_equal(fc[f][1].view(np.uint32), fn[f][1].view(np.uint32)), (tag, f)
+        if W * H <= 40000:
+            for f in sorted({0, depth - 1}):
+                M, cam = cams[f][1].reshape(16), cams[f][2]
+                ref = sc.oracle().render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, **kw))
+                if np.isfinite(ref["rgb"]).all():
+                    assert np.array_equal(fc[f][1][..., :3].view(np.uint32), ref["rgb"].view(np.uint32)), (tag, f)
+                assert np.array_equal(fc[f][0], ref["rgba8"]), (tag, f)
+                tally[stc.render_kernel] += 1
+    report("culling %s" % kernel, tally)
+    assert culled_cases >= len(plan) // 4, (culled_cases, len(plan))
+    assert sum(tally.values()) >= 6
+
+
+# ---------------------------------------------------------------------------------------------------- 5. after a refit
+def test_refitted_two_instance_scene_on_stream_and_paths(make_renderer):
+    """test_gpu_refit's two-instance scene, deformed: vertex update, BLAS update, TLAS update -- then stream (Depth 1, 3) and
+    paths (Depth 1, 2) and fused render the deformed geometry as the oracle does"""
+    from test_gpu_refit import _two_instances, deform
+    verts, idx = load("monkey.obj")
+    env = procedural_env(128, 64, seed=9)
+    tally = collections.Counter()
+    for kernel, depths in (("fused", (1, 3)), ("stream", (1, 3)), ("paths", (1, 2))):
+        r = make_renderer(kernel)
+        r.upload_envmap(env)
+        mid = r.upload_mesh(verts, idx)
+        r.build_blas(mid, allow_update=True)
+        r.build_tlas(_two_instances(mid, 0.0), allow_update=True)
+        r.set_tile_partition(0, 1)
+        for step, kind in enumerate(("wave", "scale")):
+            dv = deform(verts, kind, seed=step)
+            if kind == "scale":
+                dv["position"] = (dv["position"] - np.array([0.5, -0.25, 1.0], np.float32)) / np.float32(2.0)
+            r.update_mesh_vertices(mid, dv)
+            r.build_blas(mid, update=True)
+            inst = _two_instances(mid, 0.3 * (step + 1))
+            r.build_tlas(inst, update=True)
+            o_inst = inst.copy()
+            o_inst["blas"] = 0
+            sc = Scene("refit-%d" % step, [(dv, idx)], env, o_inst)
+            for depth in depths:
+                for kw in (dict(max_refract=6), dict(max_refract=3, max_reflect=1)):
+                    got = check_launch(r, kernel, sc, 200, 120, orbit(0.4 + step, depth), kw, rr.DISPATCH_FLOAT_OUTPUT, tally,
+                                       tag="refit %s step %d depth %d %s" % (kernel, step, depth, kw))
+                    assert got == KERNEL_ID[kernel]
+        r.close()
+    report("refit", tally)
+    assert tally[STREAM] >= 8 and tally[PATHS] >= 8 and tally[FUSED] >= 8

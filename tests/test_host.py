@@ -406,3 +406,33 @@ def test_hardened_obj_loader(tmp_path):
     assert np.all(m.verts["uv"][9:12] == (0.5, 0.25))
     p.write_text("v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2 9\n")
     assert rr.Mesh().load(str(p), hardened=True) is False      # out of range
+
+
+# ---------------------------------------------------------------------------------- mesh-tile partition without a camera
+@pytest.mark.parametrize("w,h", [(1920, 1080), (211, 149), (97, 61), (33, 1), (1, 1), (5, 600)])
+@pytest.mark.parametrize("world", [1, 2, 3, 8])
+def test_mesh_partition_without_constants_is_the_whole_frame(w, h, world):
+    """rr_host_mesh_partition(bounds, NULL, ...) -- what a RR_DISPATCH_DEBUG_NO_CULL launch on the mesh path renders and sizes
+    its buffers by: no rectangle, no background tiles, every tile a mesh tile dealt round robin over all ranks."""
+    m = rr.Mesh()
+    assert m.load(O.asset("monkey.obj"))
+    pos = m.verts["position"]
+    b = (C.c_float * 6)(*[float(v) for v in pos.min(axis=0)], *[float(v) for v in pos.max(axis=0)])
+    part = _capi.MeshPartition()
+    assert rr.lib().rr_host_mesh_partition(b, None, 1, w, h, world, C.byref(part)) == 0
+    tx = (w + 31) // 32
+    n_tiles = tx * ((h + 31) // 32)
+    assert (part.tiles_x, part.n_tiles, part.world) == (tx, n_tiles, world)
+    assert part.rect_w == 0 and part.rect_h == 0 and part.n_bg_tiles == 0 and part.n_mesh_tiles == n_tiles
+    assert part.rank0_rounds == 0
+    assert part.max_mesh_tiles_per_rank == -(-n_tiles // world)
+    counts = [rr.lib().rr_host_mesh_tiles_of_rank(C.byref(part), r) for r in range(world)]
+    assert sum(counts) == n_tiles and max(counts) == part.max_mesh_tiles_per_rank
+    # the culled partition of a view where the scene is small on screen holds fewer tiles per rank: a buffer sized from it
+    # cannot hold the whole-frame partition (the sharded launch refuses that pairing)
+    if (w, h) == (1920, 1080) and world > 1:
+        culled = _capi.MeshPartition()
+        sc = rr.camera_orbit(0.01)
+        assert rr.lib().rr_host_mesh_partition(b, C.byref(sc), 1, w, h, world, C.byref(culled)) == 0
+        assert culled.rect_w > 0 and culled.n_bg_tiles > 0
+        assert culled.max_mesh_tiles_per_rank < part.max_mesh_tiles_per_rank

@@ -18,9 +18,12 @@
 #include <string>
 #include <vector>
 
+#include "rr_choice.h"
 #include "rr_launch.h"
 
 using namespace rr;
+
+static_assert(CHOICE_TILE == (uint32_t)TILE && CHOICE_STREAM_MAX_GEN == STREAM_MAX_GEN, "rr_choice.h mirrors rr_types.h");
 
 static_assert(sizeof(rr_vertex) == 32, "Vertex stride (Mesh.cpp:45)");
 static_assert(sizeof(rr_instance_desc) == 64, "D3D12_RAYTRACING_INSTANCE_DESC");
@@ -114,7 +117,7 @@ struct rr_context {
     QGrid    scene_grid = { { 0, 0, 0 }, { 1, 1, 1 } };
     TriRec*  d_pool_tris = nullptr;
     NrmRec*  d_pool_nrms = nullptr;
-    uint32_t n_pool_tris = 0;
+    uint32_t n_pool_tris = 0, n_pool_nodes = 0;     // (n_pool_nodes: TLAS nodes, then those of every BLAS in use)
     uint32_t n_insts = 0, tlas_depth = 0;
     bool tlas_built = false;
     bool single_identity = false;
@@ -171,24 +174,17 @@ struct rr_context {
     CounterBlock* d_cnt_trial = nullptr;     // what the two renders of a kernel-choice measurement count into (thrown away)
     uint32_t* d_park[MAX_LANES + 1] = {};   // k_render_lds: parked reflected rays, one slab per stream slot like the tickets
     size_t    park_bytes[MAX_LANES + 1] = {};
-    // k_render_lds or k_render_fused for launches of many slices?  Neither wins everywhere (sphere.obj / shell.obj 1080p: the LDS
-    // kernel by 6 % all round the orbit; monkey.obj: the L1-fed one by 2 %), and which does depends on how busy the texture
-    // path is, not on anything the host can see.  So the first two eligible launches of a scene are timed with HIP events, one
-    // on each kernel (adjacent slices of the same orbit), and the faster per slice renders the rest.  Frames are bit-identical.
     char       last_kernel_name[96] = "";
-    uint32_t   last_kernel = 0;      // render kernel of the last dispatch: 0 k_render_fused, 1 k_render_lds, 2 k_render_paths, 3 experimental
+    uint32_t   last_kernel = 0;      // render kernel of the last dispatch (rr_choice.h RenderKernel): 0 fused, 1 lds, 2 paths, 7 stream
     uint32_t* d_tickets = nullptr;   // k_render_lds ticket words: one block per stream a launch can be on (lanes, then the context's stream)
 
     // diagnostics switches, read once at rr_create (never needed for correct results)
-    int  dbg_kernel = 0;             // RR_DEBUG_KERNEL: 0 default (measured choice), 1 "fused", 4 "lds", 5 "paths", 10 "stream": that kernel wherever it can render the launch
-    int  dbg_stack = 0;              // RR_DEBUG_STACK
+    DebugFacts dbg = { 0, 0, false };    // RR_DEBUG_KERNEL / _STACK / _TLAS32 (rr_choice.h): a forced kernel, wherever it can render the launch
     int  dbg_ticket_blocks = 0;      // RR_DEBUG_TICKET: 1 = k_render_lds treats the whole frame as the mesh rectangle, 2 = no rectangle
     bool dbg_group_trace = true;     // RR_DEBUG_GROUP_TRACE=0: k_render_paths never shares a ray between lanes
     bool dbg_async_set = false;
     uint32_t dbg_async[2] = { 2, 2 };    // RR_DEBUG_ASYNC="step,shade": issue thresholds of k_stream_rays in sixteenths of the live lanes
     bool dbg_tile_order = true;      // RR_DEBUG_TILE_ORDER=0: tiles in image order (DispatchDev::rt_*)
-    int  dbg_stream_waves = 6;       // (the stream renderer's waves per SIMD are a build-time constant now: -DRR_STREAM_WPS)
-    bool dbg_tlas32 = false;         // RR_DEBUG_TLAS32: two-level scenes keep 32-bit stack entries and register-parked rays
     int  dbg_shape = 0;              // RR_DEBUG_SHAPE: first k_render_lds workgroup shape to consider (rr_launch.h)
     std::string dbg_diag;            // RR_DEBUG_DIAG: file that receives per-wave diagnostics of Depth-1 dispatches
 
@@ -204,57 +200,13 @@ struct rr_context {
     size_t    strm_cap[MAX_LANES + 1] = {};          // queue entries allocated (each of the two queues)
     size_t    strm_pixels[MAX_LANES + 1] = {};       // pixel ordinals the slots / marks are allocated for
     size_t    strm_budget = 0;                       // bytes one set may take (stream_budget)
-    // Which of two kernels renders a class of launches is MEASURED, once per scene and launch shape: the scene's first dispatch of
-    // a class runs on the default kernel (clocks come up), the second is rendered by both candidates, each bracketed by HIP events
-    // (the frames are bit-identical, the dispatch just costs three extra launches), and again on the next dispatch of the shape; the default renders every later one unless
-    // the alternative took less than 98 % of its time over the two.
-    // rr_build_tlas starts every measurement afresh; a launch shape (frame size, bounce limits, launch depth 1 / 2 / 3-7 / 8-23 /
-    // 24-47 / 48 and up) has its own choice -- a class remembers its four most recent shapes, so a caller that alternates between two
-    // depths does not measure again at every switch -- and a rectangle share that doubles or halves renews a shape's.
-    // Classes: two-level scenes (k_render_fused / k_stream_*), launches of many slices of the reference's scene
-    // (k_render_fused / k_render_lds), launches of one or two slices (k_render_fused / k_render_paths).
-    struct KernelChoice {
-        int choice = 0;              // 0 undecided, 1 candidate A (k_render_fused), 2 candidate B
-        uint32_t seen = 0;
-        unsigned long long key = 0;  // the launch shape the choice was measured for
-        double share = 0.0;          // rectangle share of the frame at the measurement
-        float ms[2] = { 0.0f, 0.0f };
-        bool valid = false;
-        unsigned long long stamp = 0;
-    };
-    struct ChoiceClass {
-        KernelChoice e[4];
-        unsigned long long clock = 0;
-        KernelChoice* find(unsigned long long key)      // the shape's entry; a new shape takes the place of the least recently used
-        {
-            ++clock;
-            KernelChoice* lru = &e[0];
-            for (KernelChoice& x : e) {
-                if (x.valid && x.key == key) { x.stamp = clock; return &x; }
-                if (x.stamp < lru->stamp) lru = &x;
-            }
-            *lru = KernelChoice();
-            lru->valid = true; lru->key = key; lru->stamp = clock;
-            return lru;
-        }
-        const KernelChoice* peek(unsigned long long key) const
-        {
-            for (const KernelChoice& x : e) if (x.valid && x.key == key) return &x;
-            return nullptr;
-        }
-    };
-    static unsigned long long choice_key(uint32_t width, uint32_t height, const rr_dispatch_params& p, uint32_t depth)
-    {
-        return ((unsigned long long)width << 48) ^ ((unsigned long long)height << 32) ^ ((unsigned long long)(uint32_t)p.max_refract << 8) ^
-               ((unsigned long long)(uint32_t)p.max_reflect << 4) ^ (depth <= 2 ? depth : depth < 8 ? 3u : depth < 24 ? 4u : depth < 48 ? 5u : 6u);
-    }
-    ChoiceClass ch_tlas, ch_many, ch_few;
+    ChoiceClass ch[3];                   // the measured kernel choices (rr_choice.h), by ChoiceClassId
     hipEvent_t ch_ev[4] = {};
 
     // trace_rays scratch
     rr_ray_dev* d_rays = nullptr;
     rr_hit_dev* d_hits = nullptr;
-    uint32_t ray_cap = 0;
+    size_t ray_cap = 0;
 };
 
 namespace {
@@ -275,6 +227,18 @@ int fail(rr_context* ctx, int code, const char* what, hipError_t e = hipSuccess)
     } while (0)
 
 template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+// regrows device buffer p to n units of `unit` bytes; `have` counts them (0 while p is gone).  Waits for the context's stream
+// first: what is in flight there may still read the old buffer.
+template <class T> int grow(rr_context* ctx, T*& p, size_t& have, size_t n, size_t unit = sizeof(T))
+{
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    dfree(p);
+    have = 0;
+    RR_HIP(hipMalloc(&p, n * unit));
+    have = n;
+    return RR_OK;
+}
 
 uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
@@ -379,6 +343,17 @@ void fill_scene(const rr_context* ctx, SceneDev& sc)
     sc.env_w = ctx->env_w; sc.env_h = ctx->env_h;
 }
 
+// trace_rays scratch for n rays (a failure leaves ray_cap 0: the next call grows both again)
+int ensure_rays(rr_context* ctx, size_t n)
+{
+    if (n <= ctx->ray_cap) return RR_OK;
+    size_t hits = 0;
+    int r = grow(ctx, ctx->d_hits, hits, n);
+    if (r == RR_OK) r = grow(ctx, ctx->d_rays, ctx->ray_cap, n);
+    if (r != RR_OK) ctx->ray_cap = 0;
+    return r;
+}
+
 // InstanceMask of a single-identity scene's instance (the query kernels test it per ray before the walk)
 uint32_t inst0_mask(const rr_context* ctx)
 {
@@ -442,11 +417,11 @@ int rr_create(int device_ordinal, rr_context** out)
     (void)hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream);
     (void)hipMemsetAsync(ctx->d_tickets, 0, (rr_context::MAX_LANES + 1) * LDS_TICKET_WORDS * sizeof(uint32_t), ctx->stream);   // the kernel leaves them zero
     if (const char* e = getenv("RR_DEBUG_KERNEL"))
-        ctx->dbg_kernel = !strcmp(e, "fused") ? 1 : !strcmp(e, "lds") ? 4 : !strcmp(e, "paths") ? 5 : !strcmp(e, "stream") ? 10 : 0;
-    if (const char* e = getenv("RR_DEBUG_STACK")) ctx->dbg_stack = atoi(e);
+        ctx->dbg.kernel = !strcmp(e, "fused") ? 1 : !strcmp(e, "lds") ? 4 : !strcmp(e, "paths") ? 5 : !strcmp(e, "stream") ? 10 : 0;
+    if (const char* e = getenv("RR_DEBUG_STACK")) ctx->dbg.stack = atoi(e);
     if (const char* e = getenv("RR_DEBUG_TICKET")) ctx->dbg_ticket_blocks = atoi(e);
     if (const char* e = getenv("RR_DEBUG_SHAPE")) ctx->dbg_shape = atoi(e);
-    if (const char* e = getenv("RR_DEBUG_TLAS32")) ctx->dbg_tlas32 = atoi(e) != 0;
+    if (const char* e = getenv("RR_DEBUG_TLAS32")) ctx->dbg.tlas32 = atoi(e) != 0;
     if (const char* e = getenv("RR_DEBUG_TILE_ORDER")) ctx->dbg_tile_order = atoi(e) != 0;
     if (const char* e = getenv("RR_DEBUG_ASYNC")) { unsigned l = 2, sh = 2; if (sscanf(e, "%u,%u", &l, &sh) == 2 && l >= 1 && sh >= 1) { ctx->dbg_async[0] = l; ctx->dbg_async[1] = sh; ctx->dbg_async_set = true; } }
     if (const char* e = getenv("RR_DEBUG_DIAG")) ctx->dbg_diag = e;
@@ -808,7 +783,7 @@ int finish_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, 
     ctx->single_identity = n == 1 && inst0.identity && (d0.hitgroup_flags >> 24) == 0 && ((d0.instance_id_mask >> 24) & 0xffu) != 0;
     if (scene_stack_need(ctx) > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: TLAS+BLAS deeper than the 64-entry stack");
     ctx->tlas_built = true;
-    ctx->ch_tlas = rr_context::ChoiceClass(); ctx->ch_many = rr_context::ChoiceClass(); ctx->ch_few = rr_context::ChoiceClass();      // a new scene: the kernels are chosen afresh
+    for (ChoiceClass& c : ctx->ch) c = ChoiceClass();         // a new scene: the kernels are chosen afresh
     return RR_OK;
 }
 
@@ -930,7 +905,7 @@ int rr_build_tlas_ex(rr_context* ctx, const rr_instance_desc* instances, uint32_
     (void)hipFree(d_xb);
     if (rc != RR_OK) return rc;
     if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "TLAS build", e);
-    ctx->n_pool_tris = n_pool_tris;
+    ctx->n_pool_tris = n_pool_tris; ctx->n_pool_nodes = n_pool_nodes;
     ctx->tlas_depth = depth;
     ctx->tlas_refittable = keep;
     return finish_tlas(ctx, instances, n, host[0], scene_scale);
@@ -952,22 +927,20 @@ int rr_set_tile_partition(rr_context* ctx, uint32_t rank, uint32_t world)
     return RR_OK;
 }
 
-static void tile_counts(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, uint32_t& tiles_x, uint32_t& n_tiles,
-                        uint32_t& local, uint32_t& max_local)
+// round-robin tiles of a W x H frame: tiles across, tiles, this rank's, the most any rank has
+struct Tiles { uint32_t tiles_x, n_tiles, local, max_local; };
+static Tiles tile_counts(uint32_t W, uint32_t H, uint32_t rank, uint32_t world)
 {
-    tiles_x = (W + TILE - 1) / TILE;
-    n_tiles = tiles_x * ((H + TILE - 1) / TILE);
-    local = n_tiles > rank ? (n_tiles - rank + world - 1) / world : 0;
-    max_local = (n_tiles + world - 1) / world;
+    const uint32_t tiles_x = (W + TILE - 1) / TILE, n_tiles = tiles_x * ((H + TILE - 1) / TILE);
+    return { tiles_x, n_tiles, n_tiles > rank ? (n_tiles - rank + world - 1) / world : 0, (n_tiles + world - 1) / world };
 }
 
 int rr_local_tile_count(rr_context* ctx, uint32_t width, uint32_t height, uint32_t* n_tiles, uint32_t* max_tiles_any_rank)
 {
     if (!ctx || width == 0 || height == 0) return RR_ERR_INVALID_ARGUMENT;
-    uint32_t tx, nt, local, mx;
-    tile_counts(width, height, ctx->tile_rank, ctx->tile_world, tx, nt, local, mx);
-    if (n_tiles) *n_tiles = local;
-    if (max_tiles_any_rank) *max_tiles_any_rank = mx;
+    const Tiles t = tile_counts(width, height, ctx->tile_rank, ctx->tile_world);
+    if (n_tiles) *n_tiles = t.local;
+    if (max_tiles_any_rank) *max_tiles_any_rank = t.max_local;
     return RR_OK;
 }
 
@@ -975,34 +948,16 @@ namespace {
 
 int ensure_cams(rr_context* ctx, size_t n)
 {
-    if (n <= ctx->cams_cap) return RR_OK;
-    RR_HIP(hipStreamSynchronize(ctx->stream));
-    dfree(ctx->d_cams);
-    ctx->cams_cap = 0;
-    size_t cap = n < 64 ? 64 : n;
-    RR_HIP(hipMalloc(&ctx->d_cams, cap * sizeof(CamDev)));
-    ctx->cams_cap = cap;
-    return RR_OK;
+    return n <= ctx->cams_cap ? RR_OK : grow(ctx, ctx->d_cams, ctx->cams_cap, n < 64 ? 64 : n);
 }
 
 // DispatchRays(W, H, depth): slice f uses the constants d_cams[f] and writes to out + f*stride.
 // ext_tiles != null: compact tile output into caller memory with the given stride (sharded frames).
 int ensure_frame_buffers(rr_context* ctx, size_t elems, bool want_f32)
 {
-    if (elems > ctx->rgba_elems || !ctx->d_rgba8) {
-        RR_HIP(hipStreamSynchronize(ctx->stream));
-        dfree(ctx->d_rgba8);
-        ctx->rgba_elems = 0;
-        RR_HIP(hipMalloc(&ctx->d_rgba8, elems * 4));
-        ctx->rgba_elems = elems;
-    }
-    if (want_f32 && (elems > ctx->f32_elems || !ctx->d_f32)) {
-        RR_HIP(hipStreamSynchronize(ctx->stream));
-        dfree(ctx->d_f32);
-        ctx->f32_elems = 0;
-        RR_HIP(hipMalloc(&ctx->d_f32, elems * 16));
-        ctx->f32_elems = elems;
-    }
+    if (elems > ctx->rgba_elems || !ctx->d_rgba8)
+        if (int r = grow(ctx, ctx->d_rgba8, ctx->rgba_elems, elems)) return r;
+    if (want_f32 && (elems > ctx->f32_elems || !ctx->d_f32)) return grow(ctx, ctx->d_f32, ctx->f32_elems, elems);
     return RR_OK;
 }
 
@@ -1015,11 +970,6 @@ int ensure_lane(rr_context* ctx, uint32_t lane)
     return RR_OK;
 }
 
-// (the screen rectangle of the scene bounds: rr_host_screen_rect, csrc/host/rr_host_partition.cpp)
-inline void mesh_screen_rect(const float box[6], const rr_scene_constants* cams, uint32_t n, uint32_t W, uint32_t H, uint32_t r[4])
-{
-    (void)rr_host_screen_rect(box, cams, n, W, H, r);
-}
 
 // ---- k_stream_* : buffers and passes ----------------------------------------------------------------------------------
 // One pass renders `fc` consecutive slices of the dispatch.  Worst case per pixel of the ray kernels' blocks: four rays alive in
@@ -1043,19 +993,31 @@ size_t stream_budget(rr_context* ctx)
     return ctx->strm_budget;
 }
 
-// launches of the reference's scene from this many slices on take k_render_lds unless k_render_fused measures faster
-inline bool lds_default_depth(uint32_t depth) { return depth >= 24u; }
+// nodes of a BLAS as k_render_lds holds them in LDS
+uint32_t lds_node_bytes(const MeshRes& m) { return (m.n_tris > 1 ? m.n_tris - 1 : 1) * (uint32_t)sizeof(QNode); }
 
-// the reference's scene (one identity instance) with a node array small enough for LDS beside the traversal stacks
-bool scene_fits_lds(const rr_context* ctx)
+// what the kernel choice (rr_choice.h) knows of the scene
+SceneFacts scene_facts(const rr_context* ctx)
 {
-    if (!ctx->single_identity || ctx->dbg_stack != 0 || ctx->inst_host.empty()) return false;
-    const MeshRes& m0 = ctx->meshes[(size_t)ctx->inst_host[0].blas];
-    const uint32_t node_bytes = (m0.n_tris > 1 ? m0.n_tris - 1 : 1) * (uint32_t)sizeof(QNode);
-    return m0.n_tris < 32768u && lds_kernel_shape(node_bytes, scene_stack_need(ctx) + 1, nullptr, ctx->dbg_shape) >= 0;
+    SceneFacts s = { ctx->single_identity, scene_stack_need(ctx), 0, ctx->n_pool_nodes, ctx->n_pool_tris + ctx->n_insts, false };
+    if (ctx->single_identity && !ctx->inst_host.empty()) {
+        const MeshRes& m0 = ctx->meshes[(size_t)ctx->inst_host[0].blas];
+        s.blas_tris = m0.n_tris;
+        s.lds_fits = ctx->dbg.stack == 0 && m0.n_tris < 32768u && lds_kernel_shape(lds_node_bytes(m0), s.need + 1, nullptr, ctx->dbg_shape) >= 0;
+    }
+    return s;
 }
 
-// the buffer set of the stream the dispatch is on
+// what the kernel choice knows of a launch of `depth` slices whose scene rectangle (pixels) is `rect`
+LaunchFacts launch_facts(const rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth, const uint32_t rect[4],
+                         const rr_dispatch_params& p, bool compact, bool mesh)
+{
+    return { depth, ((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE), ctx->tile_world, compact, mesh,
+             rect[2] > rect[0] && rect[3] > rect[1], (double)(rect[2] - rect[0]) * (double)(rect[3] - rect[1]) / ((double)width * (double)height),
+             p.max_refract, p.max_reflect, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) != 0, !ctx->dbg_diag.empty() && ctx->single_identity };
+}
+
+// the buffer set of the stream the dispatch is on (launches on one stream are ordered: one set per stream)
 uint32_t stream_slot(const rr_context* ctx)
 {
     for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l) if (ctx->lane_stream[l] && ctx->stream == ctx->lane_stream[l]) return l;
@@ -1076,9 +1038,8 @@ size_t stream_rect_wb(const DispatchDev& a, uint32_t frames)
 
 StreamPlan stream_plan(rr_context* ctx, const DispatchDev& a, uint32_t depth)
 {
-    auto rect_wb = [&](uint32_t frames) -> size_t { return stream_rect_wb(a, frames); };
     auto bytes = [&](uint32_t frames, StreamPlan& pl) -> size_t {
-        const size_t wb = rect_wb(frames);
+        const size_t wb = stream_rect_wb(a, frames);
         pl.pixels = wb * 64u;
         pl.n_wg = (uint32_t)std::min<size_t>((size_t)ctx->n_cus * 6u, std::max<size_t>(1u, (wb + 15u) / 16u));     // six workgroups of the ray kernels fit a CU
         pl.cap = ((4u * pl.pixels + (size_t)pl.n_wg * 4u * STREAM_BLK + STREAM_BLK - 1u) / STREAM_BLK) * STREAM_BLK;
@@ -1124,7 +1085,7 @@ int ensure_stream_buffers(rr_context* ctx, const StreamPlan& pl)
 }
 
 // the whole dispatch through the generation-per-kernel renderer, `fc` slices per pass
-int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uint32_t depth, int need, bool stats, bool rgb8)
+int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uint32_t depth, int need, bool stats)
 {
     const StreamPlan pl = stream_plan(ctx, a, depth);
     if (int r = ensure_stream_buffers(ctx, pl)) return r;
@@ -1142,23 +1103,25 @@ int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uin
         StreamDev s = ctx->strm[stream_slot(ctx)];
         s.cap = (uint32_t)ctx->strm_cap[stream_slot(ctx)];
         s.n_rect_wb = (uint32_t)stream_rect_wb(a, fc);
-        RR_HIP(launch_render_stream(sc, b, s, need, pl.n_wg, stats, ctx->stream, ctx->dbg_stream_waves));
+        RR_HIP(launch_render_stream(sc, b, s, need, pl.n_wg, stats, ctx->stream));
     }
-    (void)rgb8;
     return RR_OK;
 }
 
-// mesh-tile partition (rr_mesh_partition): the partition the caller's tile buffers were checked against, and where rank 0's
-// background tiles of a dispatch go
+// mesh-tile partition: the partition the caller's tile buffers were checked against, where rank 0's background tiles go
 struct MeshOut { const rr_mesh_partition* part; uint32_t* bg; size_t bg_stride_elems; };
 
-inline bool timed_request(const rr_dispatch_params& p) { return (p.flags & RR_DISPATCH_TIME_KERNEL) != 0; }
+// where a dispatch's slices go: this rank's tiles and the output's element layout (elements are 32-bit words)
+struct Layout : Tiles {
+    rr_mesh_partition part; uint32_t n_mesh_local;          // mesh: the caller's partition, this rank's mesh tiles
+    bool want_f32, compact, rgb8;
+    size_t slice_elems, stride, out_base;
+};
 
-// out_slot: which of the frames_in_flight output regions of the internal frame buffer this dispatch writes;
-// h_cams: host copy of the depth slices' constants (may be null: no ordering hint)
-int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth, const CamDev* d_cams,
-                  const rr_scene_constants* h_cams, const rr_dispatch_params& p, uint32_t* ext_tiles, size_t ext_stride_elems,
-                  bool keep_counters, uint32_t out_slot = 0, uint32_t out_slot_depth = 0, const MeshOut* mesh = nullptr)
+// checks the request, lays out (and allocates) its output and GenerateCameraRay's screen tables for the frame size
+int layout_dispatch(rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth, const rr_scene_constants* h_cams,
+                    const rr_dispatch_params& p, uint32_t* ext_tiles, size_t ext_stride_elems, uint32_t out_slot,
+                    uint32_t out_slot_depth, const MeshOut* mesh, Layout& o)
 {
     if (width == 0 || height == 0 || width > 32768 || height > 32768 || depth == 0 || depth > 65535)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "dispatch: bad frame size or depth");
@@ -1168,33 +1131,29 @@ int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t dep
     if (p.max_reflect > 8) return fail(ctx, RR_ERR_UNSUPPORTED, "dispatch: max_reflect > 8 (parked-ray registers)");
     if (!(p.ior > 0.0f)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "dispatch: ior must be > 0");
 
-    uint32_t tiles_x, n_tiles, local, max_local;
-    tile_counts(width, height, ctx->tile_rank, ctx->tile_world, tiles_x, n_tiles, local, max_local);
-    rr_mesh_partition part;
-    memset(&part, 0, sizeof part);
-    uint32_t n_mesh_local = 0;
+    static_cast<Tiles&>(o) = tile_counts(width, height, ctx->tile_rank, ctx->tile_world);
+    memset(&o.part, 0, sizeof o.part); o.n_mesh_local = 0;
     if (mesh) {         // mesh tiles dealt round robin, background tiles to rank 0: this rank's tiles are its mesh tiles, then those
         if (!ext_tiles || !(p.flags & RR_DISPATCH_TILES_RGB8) || !h_cams || !mesh->part) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: RGB8 tile buffers and host constants");
         // the partition is the caller's (its buffers were sized and checked against it), never recomputed here
-        part = *mesh->part;
-        if (part.world != ctx->tile_world || part.tiles_x != tiles_x || part.n_tiles != n_tiles) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: not one of this launch");
-        n_mesh_local = rr_host_mesh_tiles_of_rank(&part, ctx->tile_rank);
-        if (ctx->tile_rank == 0 && part.n_bg_tiles && !mesh->bg) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: rank 0 needs the background tile buffer");
-        local = n_mesh_local + (ctx->tile_rank == 0 ? part.n_bg_tiles : 0);
-        max_local = part.max_mesh_tiles_per_rank;
+        o.part = *mesh->part;
+        if (o.part.world != ctx->tile_world || o.part.tiles_x != o.tiles_x || o.part.n_tiles != o.n_tiles) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: not one of this launch");
+        o.n_mesh_local = rr_host_mesh_tiles_of_rank(&o.part, ctx->tile_rank);
+        if (ctx->tile_rank == 0 && o.part.n_bg_tiles && !mesh->bg) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "mesh partition: rank 0 needs the background tile buffer");
+        o.local = o.n_mesh_local + (ctx->tile_rank == 0 ? o.part.n_bg_tiles : 0);
+        o.max_local = o.part.max_mesh_tiles_per_rank;
     }
-    const bool want_f32 = (p.flags & RR_DISPATCH_FLOAT_OUTPUT) != 0;
-    const bool compact = ctx->tile_world > 1 || ext_tiles != nullptr;
-    const bool rgb8 = (p.flags & RR_DISPATCH_TILES_RGB8) != 0;
-    if (rgb8 && !ext_tiles) return fail(ctx, RR_ERR_UNSUPPORTED, "dispatch: RGB8 tiles only exist in external tile buffers (rr_render_orbit_sharded)");
-    // elements are 32-bit words; an RGB8 tile is 3/4 of an RGBA8 tile
-    const size_t slice_elems = compact ? (size_t)max_local * TILE * TILE * (rgb8 ? 3 : 4) / 4 : (size_t)width * height;
-    const size_t stride = ext_tiles ? ext_stride_elems : slice_elems;
-    if (ext_tiles && want_f32) return fail(ctx, RR_ERR_UNSUPPORTED, "dispatch: float output is not available for external tile buffers");
-    const size_t out_base = ext_tiles ? 0 : slice_elems * out_slot_depth * out_slot;
+    o.want_f32 = (p.flags & RR_DISPATCH_FLOAT_OUTPUT) != 0;
+    o.compact = ctx->tile_world > 1 || ext_tiles != nullptr;
+    o.rgb8 = (p.flags & RR_DISPATCH_TILES_RGB8) != 0;
+    if (o.rgb8 && !ext_tiles) return fail(ctx, RR_ERR_UNSUPPORTED, "dispatch: RGB8 tiles only exist in external tile buffers (rr_render_orbit_sharded)");
+    // an RGB8 tile is 3/4 of an RGBA8 tile
+    o.slice_elems = o.compact ? (size_t)o.max_local * TILE * TILE * (o.rgb8 ? 3 : 4) / 4 : (size_t)width * height;
+    o.stride = ext_tiles ? ext_stride_elems : o.slice_elems;
+    if (ext_tiles && o.want_f32) return fail(ctx, RR_ERR_UNSUPPORTED, "dispatch: float output is not available for external tile buffers");
+    o.out_base = ext_tiles ? 0 : o.slice_elems * out_slot_depth * out_slot;
     if (!ext_tiles)
-        if (int r = ensure_frame_buffers(ctx, out_base + slice_elems * depth, want_f32)) return r;
-
+        if (int r = ensure_frame_buffers(ctx, o.out_base + o.slice_elems * depth, o.want_f32)) return r;
     if (width != ctx->screen_w || height != ctx->screen_h) {     // new frame size: new tables (nothing in flight may still read the old ones)
         RR_HIP(hipDeviceSynchronize());
         dfree(ctx->d_screen);
@@ -1204,288 +1163,213 @@ int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t dep
         RR_HIP(hipStreamSynchronize(ctx->stream));
         ctx->screen_w = width; ctx->screen_h = height;
     }
-    SceneDev sc;
-    fill_scene(ctx, sc);
+    return RR_OK;
+}
+
+// the tiles of the rectangle x0, y0, w, h (tile units) come first in launch order (DispatchDev::rt_*)
+void set_rect_tiles(DispatchDev& a, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
+{
+    a.rt_x0 = x0; a.rt_y0 = y0; a.rt_w = w; a.rt_h = h;
+    a.rt_div_w = (uint32_t)(0x100000000ull / w) + 1u;
+    a.rt_div_o = a.tiles_x > w ? (uint32_t)(0x100000000ull / (a.tiles_x - w)) + 1u : 0u;
+}
+
+// DispatchRays(W, H, depth): slice f uses the constants d_cams[f] and writes to out + f * stride
+DispatchDev make_dispatch(const rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth, const CamDev* d_cams,
+                          const rr_scene_constants* h_cams, const rr_dispatch_params& p, uint32_t* ext_tiles, const MeshOut* mesh,
+                          const Layout& o)
+{
     DispatchDev a;
     memset(&a, 0, sizeof a);
     a.sx = ctx->d_screen; a.sy = ctx->d_screen + width;
     a.async_leaf_num = ctx->dbg_async[0]; a.async_shade_num = ctx->dbg_async[1];
     a.group_trace = ctx->dbg_group_trace ? 1u : 0u;
-    {   // where the scene can be seen at all in these slices
-        uint32_t hr[4];
-        mesh_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : h_cams, depth, width, height, hr);
-        a.hx0 = hr[0]; a.hy0 = hr[1]; a.hx1 = hr[2]; a.hy1 = hr[3];
-    }
+    uint32_t hr[4];     // where the scene can be seen at all in these slices
+    (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : h_cams, depth, width, height, hr);
+    a.hx0 = hr[0]; a.hy0 = hr[1]; a.hx1 = hr[2]; a.hy1 = hr[3];
+    a.W = width; a.H = height; a.tiles_x = o.tiles_x; a.n_tiles = o.n_tiles;
     if (mesh) {
-        a.mesh_part = 1u; a.n_mesh_local = n_mesh_local; a.n_rect_tiles = part.n_mesh_tiles; a.mesh_rounds = part.rank0_rounds;
+        a.mesh_part = 1u; a.n_mesh_local = o.n_mesh_local; a.n_rect_tiles = o.part.n_mesh_tiles; a.mesh_rounds = o.part.rank0_rounds;
         a.out_bg = mesh->bg; a.bg_stride = mesh->bg_stride_elems;
-        if (part.rect_w) {
-            a.rt_x0 = part.rect_x0; a.rt_y0 = part.rect_y0; a.rt_w = part.rect_w; a.rt_h = part.rect_h;
-            a.rt_div_w = (uint32_t)(0x100000000ull / a.rt_w) + 1u;
-            a.rt_div_o = tiles_x > a.rt_w ? (uint32_t)(0x100000000ull / (tiles_x - a.rt_w)) + 1u : 0u;
-        }
-    } else if (ctx->dbg_tile_order && ctx->tile_world == 1 && n_tiles < 65536u && a.hx1 > a.hx0 && a.hy1 > a.hy0) {
-        // unsharded frames: the tiles that touch the rectangle are rendered first (DispatchDev::rt_*)
+        if (o.part.rect_w) set_rect_tiles(a, o.part.rect_x0, o.part.rect_y0, o.part.rect_w, o.part.rect_h);
+    } else if (ctx->dbg_tile_order && ctx->tile_world == 1 && o.n_tiles < 65536u && a.hx1 > a.hx0 && a.hy1 > a.hy0) {
+        // unsharded frames: the tiles that touch the rectangle are rendered first
         const uint32_t tiles_y = (height + TILE - 1) / TILE;
         const uint32_t x0 = a.hx0 / TILE, y0 = a.hy0 / TILE;
-        const uint32_t x1 = std::min(tiles_x, (a.hx1 + TILE - 1) / TILE), y1 = std::min(tiles_y, (a.hy1 + TILE - 1) / TILE);
-        if (x1 > x0 && y1 > y0 && (x1 - x0) * (y1 - y0) < n_tiles) {
-            a.rt_x0 = x0; a.rt_y0 = y0; a.rt_w = x1 - x0; a.rt_h = y1 - y0;
-            a.rt_div_w = (uint32_t)(0x100000000ull / a.rt_w) + 1u;
-            a.rt_div_o = tiles_x > a.rt_w ? (uint32_t)(0x100000000ull / (tiles_x - a.rt_w)) + 1u : 0u;
-        }
+        const uint32_t x1 = std::min(o.tiles_x, (a.hx1 + TILE - 1) / TILE), y1 = std::min(tiles_y, (a.hy1 + TILE - 1) / TILE);
+        if (x1 > x0 && y1 > y0 && (x1 - x0) * (y1 - y0) < o.n_tiles) set_rect_tiles(a, x0, y0, x1 - x0, y1 - y0);
     }
-    a.cams = d_cams;
-    a.n_frames = depth;
-    a.blocks_per_frame = ((local + 7u) & ~7u) * 4u;
-    a.frame_stride = stride;
-    a.W = width; a.H = height; a.tiles_x = tiles_x; a.n_tiles = n_tiles;
-    a.tile_rank = ctx->tile_rank; a.tile_world = ctx->tile_world;
-    a.n_local_tiles = local;
+    a.cams = d_cams; a.n_frames = depth;
+    a.blocks_per_frame = ((o.local + 7u) & ~7u) * 4u;
+    a.frame_stride = o.stride;
+    a.tile_rank = ctx->tile_rank; a.tile_world = ctx->tile_world; a.n_local_tiles = o.local;
     a.n_blocks = a.blocks_per_frame * depth;
-    a.compact_out = compact ? (rgb8 ? 2u : 1u) : 0u;
+    a.compact_out = o.compact ? (o.rgb8 ? 2u : 1u) : 0u;
     a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
     a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
     a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
     a.tmin_p = p.tmin_primary; a.tmax_p = p.tmax_primary; a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
-    a.out_rgba8 = ext_tiles ? ext_tiles : ctx->d_rgba8 + out_base;
-    a.out_f32 = want_f32 ? ctx->d_f32 + out_base : nullptr;
-    a.counters = ctx->d_cnt->counters;
-    a.ray_shards = ctx->d_cnt->shards;
-    a.error_flag = &ctx->d_cnt->error;
-    a.diag = nullptr;
-    unsigned long long* d_diag = nullptr;
-    const char* diag_path = ctx->dbg_diag.empty() ? nullptr : ctx->dbg_diag.c_str();
-    const size_t diag_waves = std::max<size_t>(((size_t)a.n_blocks + (size_t)((a.hx1 - a.hx0) / 8u + 1u) * ((a.hy1 - a.hy0) / 8u + 1u) * depth) * 4 * 2, (size_t)ctx->n_cus * 32);
-    if (diag_path && ctx->single_identity) {
+    a.out_rgba8 = ext_tiles ? ext_tiles : ctx->d_rgba8 + o.out_base;
+    a.out_f32 = o.want_f32 ? ctx->d_f32 + o.out_base : nullptr;
+    a.counters = ctx->d_cnt->counters; a.ray_shards = ctx->d_cnt->shards; a.error_flag = &ctx->d_cnt->error;
+    return a;
+}
+
+// one render launch of a dispatch: what the kernels read, and what their host sides need besides
+struct Launch {
+    SceneDev sc;
+    DispatchDev a;
+    uint32_t need;
+    const rr_scene_constants* h_cams; const rr_dispatch_params* p;      // (h_cams may be null: no ordering hint)
+    FusedVariant fused;
+};
+
+// k_render_lds parks reflected rays in a slab per stream slot (allocated at first use: outside anything that is timed)
+int ensure_lds_park(rr_context* ctx, uint32_t slot, int max_reflect)
+{
+    const size_t park_need = (size_t)ctx->n_cus * 32 * (max_reflect <= 2 ? 2u : 8u) * 8 * 64 * sizeof(uint32_t);     // at most 32 waves per CU
+    return ctx->park_bytes[slot] < park_need ? grow(ctx, ctx->d_park[slot], ctx->park_bytes[slot], park_need, 1) : RR_OK;
+}
+
+// k_render_lds: the reference's scene with a node array small enough for LDS (its own meshes up to shell.obj): persistent
+// workgroups, nodes read from LDS
+int launch_lds(rr_context* ctx, const Launch& L, bool stats)
+{
+    const MeshRes& m0 = ctx->meshes[(size_t)ctx->inst_host[0].blas];
+    LdsDispatch q;
+    memset(&q, 0, sizeof q);
+    const uint32_t slot = stream_slot(ctx);
+    q.tickets = ctx->d_tickets + (size_t)slot * LDS_TICKET_WORDS;
+    q.park_slots = L.p->max_reflect <= 2 ? 2u : 8u;
+    if (int r = ensure_lds_park(ctx, slot, L.p->max_reflect)) return r;
+    q.park = ctx->d_park[slot];
+    uint32_t rect[4];
+    (void)rr_host_screen_rect(m0.bounds, ((ctx->dbg_ticket_blocks & 3) == 1 || (L.p->flags & RR_DISPATCH_DEBUG_NO_CULL)) ? nullptr : L.h_cams, L.a.n_frames,
+                     L.a.W, L.a.H, rect);
+    // experiments (RR_DEBUG_TICKET): low bits 1 = whole frame in phase 1, 2 = no phase 1, 3 = phase 1 at every depth;
+    // +16: eight queues, a wave starts on its XCD's; +32: parked rays in registers
+    if ((ctx->dbg_ticket_blocks & 3) == 2) rect[2] = rect[0];
+    // eight queues, a wave starts on its XCD's: an XCD then works on every eighth slice, which its L2 rewards
+    // (monkey.obj Depth 64: 90 us per frame, 104 with 32 queues entered by wave number)
+    q.n_queues = (ctx->dbg_ticket_blocks & 64) ? 64u : (ctx->dbg_ticket_blocks & 128) ? LDS_QUEUES : 8u;   // launch_render_lds caps it at the grid size
+    q.home_xcc = (ctx->dbg_ticket_blocks & 16) ? 0u : 1u;
+    q.rx0 = rect[0]; q.ry0 = rect[1]; q.rx1 = rect[2]; q.ry1 = rect[3];
+    q.node_bytes = lds_node_bytes(m0);
+    q.stack_entries = L.need + 1;                     // the tree's depth bounds the stack; one entry to spare
+    RR_HIP(launch_render_lds(L.sc, L.a, q, ctx->n_cus, stats, ctx->stream, ctx->dbg_shape));
+    return RR_OK;
+}
+
+int launch_kernel(rr_context* ctx, const Launch& L, int kernel, bool stats)
+{
+    if (kernel == K_STREAM) return render_stream(ctx, L.sc, L.a, L.a.n_frames, (int)L.need, stats);
+    if (kernel == K_LDS) return launch_lds(ctx, L, stats);
+    if (kernel == K_PATHS) RR_HIP(launch_render_paths(L.sc, L.a, (int)L.need, stats, ctx->stream));
+    else RR_HIP(launch_render_fused(L.sc, L.a, L.fused.stack, L.fused.pend, stats, ctx->stream, L.fused.stack16));
+    return RR_OK;
+}
+
+// A kernel-choice measurement: both candidates render the dispatch into a counter block of their own (the dispatch's are the
+// caller's), after the other lanes' launches (they would be timed along); A once untimed (clocks come back), then A and B timed.
+int time_candidates(rr_context* ctx, Launch L, int cand_a, int cand_b, float ms[2])
+{
+    if (cand_b == K_STREAM) if (int r = ensure_stream_buffers(ctx, stream_plan(ctx, L.a, L.a.n_frames))) return r;
+    if (cand_a == K_LDS || cand_b == K_LDS) if (int r = ensure_lds_park(ctx, stream_slot(ctx), L.p->max_reflect)) return r;
+    for (hipEvent_t& e : ctx->ch_ev) if (!e) RR_HIP(hipEventCreate(&e));
+    if (!ctx->d_cnt_trial) RR_HIP(hipMalloc(&ctx->d_cnt_trial, sizeof(CounterBlock)));
+    RR_HIP(hipDeviceSynchronize());
+    RR_HIP(hipMemsetAsync(ctx->d_cnt_trial, 0, sizeof(CounterBlock), ctx->stream));
+    L.a.counters = ctx->d_cnt_trial->counters; L.a.ray_shards = ctx->d_cnt_trial->shards; L.a.error_flag = &ctx->d_cnt_trial->error;
+    if (int r = launch_kernel(ctx, L, cand_a, false)) return r;
+    for (int c = 0; c < 2; ++c) {
+        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c], ctx->stream));
+        if (int r = launch_kernel(ctx, L, c == 0 ? cand_a : cand_b, false)) return r;
+        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c + 1], ctx->stream));
+    }
+    RR_HIP(hipEventSynchronize(ctx->ch_ev[3]));
+    RR_HIP(hipEventElapsedTime(&ms[0], ctx->ch_ev[0], ctx->ch_ev[1]));
+    RR_HIP(hipEventElapsedTime(&ms[1], ctx->ch_ev[2], ctx->ch_ev[3]));
+    return RR_OK;
+}
+
+// the kernel that renders the launch: forced by RR_DEBUG_KERNEL, or its class's measured choice (measured now if that is due)
+int choose_kernel(rr_context* ctx, const Launch& L, const KernelPick& pk, const LaunchFacts& lf, int& kernel)
+{
+    kernel = pk.kernel;
+    if (pk.cls == CLS_NONE) return RR_OK;
+    KernelChoice* const ch = ctx->ch[pk.cls].find(choice_key(L.a.W, L.a.H, *L.p, L.a.n_frames));
+    if (measure_due(*ch, lf.rect_share, lf.no_cull)) {
+        float ms[2] = { 0.0f, 0.0f };
+        if (int r = time_candidates(ctx, L, pk.cand_a, pk.cand_b, ms)) return r;
+        record_timings(*ch, ms[0], ms[1], lf.rect_share);
+        if (getenv("RR_DEBUG_CHOICE"))
+            fprintf(stderr, "[rr] kernel choice: depth %u candidate %d: default %.3f ms, candidate %.3f ms (%.3f)%s\n", L.a.n_frames, pk.cand_b, ms[0], ms[1],
+                    ms[1] / ms[0], ch->choice == 2 ? " -> candidate" : ch->choice == 1 ? " -> default" : " (once more)");
+    }
+    kernel = chosen_kernel(pk, ch, lf.rect_share);
+    return RR_OK;
+}
+
+// out_slot: which of the frames_in_flight output regions of the internal frame buffer this dispatch writes;
+// h_cams: host copy of the depth slices' constants (may be null: no ordering hint)
+int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth, const CamDev* d_cams,
+                  const rr_scene_constants* h_cams, const rr_dispatch_params& p, uint32_t* ext_tiles, size_t ext_stride_elems,
+                  bool keep_counters, uint32_t out_slot = 0, uint32_t out_slot_depth = 0, const MeshOut* mesh = nullptr)
+{
+    Layout o;
+    if (int r = layout_dispatch(ctx, width, height, depth, h_cams, p, ext_tiles, ext_stride_elems, out_slot, out_slot_depth, mesh, o)) return r;
+    Launch L;
+    fill_scene(ctx, L.sc);
+    L.a = make_dispatch(ctx, width, height, depth, d_cams, h_cams, p, ext_tiles, mesh, o);
+    L.need = scene_stack_need(ctx); L.h_cams = h_cams; L.p = &p;
+
+    unsigned long long* d_diag = nullptr;       // RR_DEBUG_DIAG: per-wave records of the launch
+    const size_t diag_waves = std::max<size_t>(((size_t)L.a.n_blocks + (size_t)((L.a.hx1 - L.a.hx0) / 8u + 1u) * ((L.a.hy1 - L.a.hy0) / 8u + 1u) * depth) * 4 * 2, (size_t)ctx->n_cus * 32);
+    if (!ctx->dbg_diag.empty() && ctx->single_identity) {
         RR_HIP(hipMalloc(&d_diag, diag_waves * 64));
         RR_HIP(hipMemsetAsync(d_diag, 0, diag_waves * 64, ctx->stream));
-        a.diag = d_diag;
+        L.a.diag = d_diag;
     }
+    const uint32_t filled = mesh ? o.n_mesh_local : o.local;       // slots of the (gathered) tile buffer this rank writes
+    const size_t tile_bytes = (size_t)TILE * TILE * (o.rgb8 ? 3 : 4);
+    if (o.compact && filled < o.max_local)           // keep the gathered tail deterministic
+        for (uint32_t f = 0; f < depth; ++f)
+            RR_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(L.a.out_rgba8 + f * o.stride) + filled * tile_bytes, 0, (o.max_local - filled) * tile_bytes, ctx->stream));
+
+    const SceneFacts sf = scene_facts(ctx);
+    const uint32_t rect[4] = { L.a.hx0, L.a.hy0, L.a.hx1, L.a.hy1 };
+    const LaunchFacts lf = launch_facts(ctx, width, height, depth, rect, p, o.compact, mesh != nullptr);
+    L.fused = fused_variant(sf, depth, p.max_reflect, ctx->dbg);
+    int kernel = K_FUSED;
+    if (int r = choose_kernel(ctx, L, pick_kernel(sf, lf, ctx->dbg), lf, kernel)) return r;
 
     const bool stats = (p.flags & RR_DISPATCH_COLLECT_STATS) != 0;
-    const uint32_t need = scene_stack_need(ctx);
     const bool keep = keep_counters || (p.flags & RR_DISPATCH_KEEP_COUNTERS) != 0;
-    const uint32_t filled = mesh ? n_mesh_local : local;       // slots of the (gathered) tile buffer this rank writes
-    if (compact && filled < max_local)           // keep the gathered tail deterministic
-        for (uint32_t f = 0; f < depth; ++f)
-            RR_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(a.out_rgba8 + f * stride) + (size_t)filled * TILE * TILE * (rgb8 ? 3 : 4), 0,
-                                  (size_t)(max_local - filled) * TILE * TILE * (rgb8 ? 3 : 4), ctx->stream));
-    int stack_sel = need <= 19 ? 19 : need <= 22 ? 22 : need <= 26 ? 26 : need <= 31 ? 31 : need <= 39 ? 39 : 64;     // rr_render.hip: sizes that fill the LDS with 6 / 5 / 4 / 2 workgroups
-    if (ctx->dbg_stack >= (int)need) stack_sel = ctx->dbg_stack;   // experiments only; never below the tree depth (the kernels do not check)
-    // the reference's scene with a node array small enough for LDS (its own meshes up to shell.obj): persistent workgroups,
-    // nodes read from LDS
-    const MeshRes* m0 = ctx->single_identity ? &ctx->meshes[(size_t)ctx->inst_host[0].blas] : nullptr;
-    const uint32_t node_bytes = m0 ? (m0->n_tris > 1 ? m0->n_tris - 1 : 1) * (uint32_t)sizeof(QNode) : 0;
-    // share of the frame in which the scene can be seen at all in these slices
-    const double rect_share = (double)(a.hx1 - a.hx0) * (double)(a.hy1 - a.hy0) / ((double)width * (double)height);
-    // k_render_lds (persistent workgroups, the BLAS's nodes in LDS) is an alternative for the reference's small meshes that
-    // measures within 1-3 % of k_render_fused either way (monkey.obj Depth 64: 5.71 against 5.68 ms per launch); it is kept
-    // behind RR_DEBUG_KERNEL=lds, for the parity tests and for experiments, and never chosen by itself.
-    const bool lds_fits = scene_fits_lds(ctx) && (uint64_t)a.n_tiles * depth * depth < 0x40000000ull;       // (its ticket arithmetic divides by multiply-high)
-    // Launches of one or two slices whose scene is small on screen last as long as their most expensive wave: there the
-    // path-parallel kernel (four lanes per pixel inside the scene's screen rectangle: a fifth of the longest chain of
-    // dependent rays, four waves per block) wins -- monkey.obj 1080p Depth 1: 268 us against 471, ott.obj 626 against 1 419.
-    // It traces the primary ray four times and the count-1 rays twice, so where the mesh fills the frame and the launch is
-    // bound by throughput it loses (sphere.obj 483 us against 263, shell.obj 606 against 348): those stay with k_render_fused.
-    const bool have_rect = a.hx1 > a.hx0 && a.hy1 > a.hy0;
-    uint32_t pool_nodes = 0;
-    if (!ctx->single_identity) {
-        pool_nodes = ctx->n_insts > 1 ? ctx->n_insts - 1 : 1;
-        std::vector<char> seen(ctx->meshes.size(), 0);
-        for (uint32_t i = 0; i < ctx->n_insts; ++i) {
-            const size_t mi = (size_t)ctx->inst_host[i].blas;
-            if (!seen[mi]) { seen[mi] = 1; pool_nodes += ctx->meshes[mi].n_tris > 1 ? ctx->meshes[mi].n_tris - 1 : 1; }
-        }
-    }
-    const bool refill_stack16 = ctx->single_identity ? (m0 && m0->n_tris < 32768u && need > 19)
-                                                     : (pool_nodes < 32768u && ctx->n_pool_tris + ctx->n_insts < 32768u);
-    // ---- the candidates
-    const bool stream_ok = !ctx->single_identity && p.max_reflect <= 2 && p.max_refract <= (int)STREAM_MAX_GEN - 2 && refill_stack16 && need <= 39 &&
-                           !a.diag && ctx->dbg_stack == 0 && !ctx->dbg_tlas32;
-    const bool paths_ok = !compact && ctx->tile_world == 1 && p.max_reflect <= 2 && need <= 39 && ctx->dbg_stack == 0 && have_rect && depth <= 2;
-    auto launch_fused = [&](bool st) -> int {
-        // deep trees of small meshes: 16-bit stack entries keep eight waves per SIMD (LDS would otherwise allow 6/5/4)
-        bool stack16 = ctx->single_identity && need > 19 && need <= 39 && ctx->dbg_stack == 0 &&
-                       ctx->meshes[(size_t)ctx->inst_host[0].blas].n_tris < 32768u;
-        // two-level scenes: 16-bit entries wherever every node / leaf reference of the pool fits them (RR_DEBUG_TLAS32=1: never)
-        if (!ctx->single_identity && refill_stack16 && (need <= 30 || (need <= 39 && depth > 2)) && p.max_reflect <= 2 && ctx->dbg_stack == 0 && !ctx->dbg_tlas32) stack16 = true;
-        // (launches of one or two slices used to take the five-wave build, whose long waves ran faster without the spills of the
-        // 6..8-wave builds; since the background branch left those builds with six spilled words the ladder above is the faster one
-        // at every depth: sphere.obj Depth 1 250 us against 268, monkey.obj and shell.obj equal)
-        if (depth <= 2 && ctx->single_identity) stack16 = false;
-        // (the two-level 16-bit-stack builds are sized by the tree itself: 30 entries still leave five workgroups per CU)
-        RR_HIP(launch_render_fused(sc, a, !ctx->single_identity && stack16 && ctx->dbg_stack == 0 ? (int)need : stack_sel, p.max_reflect <= 2 ? 2 : 8, st, ctx->stream, stack16));
-        return RR_OK;
-    };
-    // k_render_lds parks reflected rays in a slab per stream slot (allocated at first use: outside anything that is timed)
-    auto lds_slot = [&]() -> uint32_t {
-        for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l) if (ctx->lane_stream[l] && ctx->stream == ctx->lane_stream[l]) return l;
-        return rr_context::MAX_LANES;          // launches on one stream are ordered: one ticket block and one slab per stream
-    };
-    auto ensure_lds_park = [&](uint32_t slot) -> int {
-        const size_t park_need = (size_t)ctx->n_cus * 32 * (p.max_reflect <= 2 ? 2u : 8u) * 8 * 64 * sizeof(uint32_t);     // at most 32 waves per CU
-        if (ctx->park_bytes[slot] < park_need) {
-            RR_HIP(hipStreamSynchronize(ctx->stream));
-            dfree(ctx->d_park[slot]);
-            ctx->park_bytes[slot] = 0;
-            RR_HIP(hipMalloc(&ctx->d_park[slot], park_need));
-            ctx->park_bytes[slot] = park_need;
-        }
-        return RR_OK;
-    };
-    auto launch_lds = [&](bool st) -> int {
-        LdsDispatch q;
-        memset(&q, 0, sizeof q);
-        const uint32_t slot = lds_slot();
-        q.tickets = ctx->d_tickets + (size_t)slot * LDS_TICKET_WORDS;
-        q.park_slots = p.max_reflect <= 2 ? 2u : 8u;
-        if (int r = ensure_lds_park(slot)) return r;
-        q.park = ctx->d_park[slot];
-        uint32_t rect[4];
-        mesh_screen_rect(m0->bounds, ((ctx->dbg_ticket_blocks & 3) == 1 || (p.flags & RR_DISPATCH_DEBUG_NO_CULL)) ? nullptr : h_cams, depth, width, height, rect);
-        // experiments (RR_DEBUG_TICKET): low bits 1 = whole frame in phase 1, 2 = no phase 1, 3 = phase 1 at every depth;
-        // +16: eight queues, a wave starts on its XCD's; +32: parked rays in registers
-        const int tk = ctx->dbg_ticket_blocks & 3;
-        if (tk == 2) rect[2] = rect[0];
-        // eight queues, a wave starts on its XCD's: an XCD then works on every eighth slice, which its L2 rewards
-        // (monkey.obj Depth 64: 90 us per frame, 104 with 32 queues entered by wave number)
-        q.n_queues = (ctx->dbg_ticket_blocks & 64) ? 64u : (ctx->dbg_ticket_blocks & 128) ? LDS_QUEUES : 8u;   // launch_render_lds caps it at the grid size
-        q.home_xcc = (ctx->dbg_ticket_blocks & 16) ? 0u : 1u;
-        q.rx0 = rect[0]; q.ry0 = rect[1]; q.rx1 = rect[2]; q.ry1 = rect[3];
-        q.node_bytes = node_bytes;
-        q.stack_entries = need + 1;                     // the tree's depth bounds the stack; one entry to spare
-        RR_HIP(launch_render_lds(sc, a, q, ctx->n_cus, st, ctx->stream, ctx->dbg_shape));
-        return RR_OK;
-    };
-    auto launch_paths = [&](bool st) -> int { RR_HIP(launch_render_paths(sc, a, (int)need, st, ctx->stream)); return RR_OK; };
-    auto launch_stream = [&](bool st) -> int { return render_stream(ctx, sc, a, depth, (int)need, st, rgb8); };
-
-    // ---- which kernel: forced by RR_DEBUG_KERNEL, or the class's measured choice
-    enum { K_FUSED = 0, K_LDS = 1, K_PATHS = 2, K_STREAM = 7 };
-    int kernel = K_FUSED;
-    rr_context::ChoiceClass* cls = nullptr;             // the class this launch belongs to, if it has two candidates
-    int cand_a = K_FUSED, cand_b = K_FUSED;          // the default and the alternative of the launch's class
-    if (ctx->dbg_kernel == 10) { if (stream_ok) kernel = K_STREAM; }
-    else if (ctx->dbg_kernel == 5) { if (paths_ok) kernel = K_PATHS; }
-    else if (ctx->dbg_kernel == 4) { if (lds_fits && !mesh && !compact) kernel = K_LDS; }      // (k_render_lds renders unsharded dispatches only)
-    else if (ctx->dbg_kernel == 0 && !a.diag) {
-        if (stream_ok) { cls = &ctx->ch_tlas; cand_b = K_STREAM; }
-        else if (paths_ok) { cls = &ctx->ch_few; cand_b = K_PATHS; }
-        else if (lds_fits && depth >= 3 && !compact && !mesh) {
-            // the persistent kernel pays off from about twenty slices a launch (monkey.obj: 1.43 against 1.38 ms at Depth 16,
-            // 1.67 / 1.74 at 20, 2.53 / 2.77 at 32, 4.80 / 5.45 at 64; tools/exp_lds_depths.py): from 24 on it is the default, the
-            // L1-fed one the alternative
-            cls = &ctx->ch_many;
-            if (lds_default_depth(depth)) { cand_a = K_LDS; cand_b = K_FUSED; } else cand_b = K_LDS;
-        }
-    }
-    if (a.diag && paths_ok && rect_share < 0.25 && ctx->dbg_kernel == 0) kernel = K_PATHS;      // (the diagnostic builds keep round 2's rule)
-    if (cls) {
-        // (k_render_lds gains on k_render_fused with the launch depth: sphere.obj 160 / 160 us per frame at Depth 16, 146 / 157 at 64)
-        const unsigned long long key = rr_context::choice_key(width, height, p, depth);
-        rr_context::KernelChoice* const ch = cls->find(key);
-        if (ch->choice != 0 && (rect_share > 2.0 * ch->share || rect_share * 2.0 < ch->share)) { ch->choice = 0; ch->seen = 0; ch->ms[0] = ch->ms[1] = 0.0f; }
-        if (ch->choice == 0 && !(p.flags & RR_DISPATCH_DEBUG_NO_CULL)) {
-            if (ch->seen++ >= 1u) {
-                // the measurement: both candidates render this dispatch (product builds), one after the other, counting into a
-                // block of their own (the dispatch's counters are the caller's: a batch of a sharded pipeline keeps adding to them);
-                // launches still running on other lanes would be timed along, so they are waited for first
-                if (cand_b == K_STREAM) if (int r = ensure_stream_buffers(ctx, stream_plan(ctx, a, depth))) return r;
-                if (cand_a == K_LDS || cand_b == K_LDS) if (int r = ensure_lds_park(lds_slot())) return r;
-                for (int k = 0; k < 4; ++k) if (!ctx->ch_ev[k]) RR_HIP(hipEventCreate(&ctx->ch_ev[k]));
-                if (!ctx->d_cnt_trial) RR_HIP(hipMalloc(&ctx->d_cnt_trial, sizeof(CounterBlock)));
-                RR_HIP(hipDeviceSynchronize());
-                RR_HIP(hipMemsetAsync(ctx->d_cnt_trial, 0, sizeof(CounterBlock), ctx->stream));
-                struct Restore { DispatchDev& a; unsigned long long* c; uint32_t* s; uint32_t* e; ~Restore() { a.counters = c; a.ray_shards = s; a.error_flag = e; } }
-                    restore{ a, a.counters, a.ray_shards, a.error_flag };
-                a.counters = ctx->d_cnt_trial->counters; a.ray_shards = ctx->d_cnt_trial->shards; a.error_flag = &ctx->d_cnt_trial->error;
-                // A (untimed: the device was just idle, its first launch would pay for the clocks coming back), then A and B timed
-                auto launch_k = [&](int k) -> int { return k == K_STREAM ? launch_stream(false) : k == K_PATHS ? launch_paths(false) : k == K_LDS ? launch_lds(false) : launch_fused(false); };
-                if (int r = launch_k(cand_a)) return r;
-                for (int c = 0; c < 2; ++c) {
-                    RR_HIP(hipEventRecord(ctx->ch_ev[2 * c], ctx->stream));
-                    if (int r = launch_k(c == 0 ? cand_a : cand_b)) return r;
-                    RR_HIP(hipEventRecord(ctx->ch_ev[2 * c + 1], ctx->stream));
-                }
-                RR_HIP(hipEventSynchronize(ctx->ch_ev[3]));
-                float ms_a = 0.0f, ms_b = 0.0f;
-                RR_HIP(hipEventElapsedTime(&ms_a, ctx->ch_ev[0], ctx->ch_ev[1]));
-                RR_HIP(hipEventElapsedTime(&ms_b, ctx->ch_ev[2], ctx->ch_ev[3]));
-                // Two measurements, on consecutive dispatches of the shape, decide together: the alternative renders the shape from
-                // then on if it took less than 98 % of the default's time over both (a launch repeats within 1-2 %, and how far apart
-                // two kernels are depends on the view: k_render_lds against k_render_fused on monkey.obj at Depth 64 is 2 to 10 %
-                // faster launch by launch round the orbit, 6 % over it; tools/exp_lds_vs_fused.py).  An alternative that is clearly
-                // slower the first time is not measured again.
-                const bool first = !(ch->ms[0] > 0.0f);
-                const float sum_a = ch->ms[0] + ms_a, sum_b = ch->ms[1] + ms_b;
-                if (first && ms_b >= 1.02f * ms_a) ch->choice = 1;
-                else if (!first) ch->choice = sum_b < 0.98f * sum_a ? 2 : 1;
-                ch->ms[0] = sum_a; ch->ms[1] = sum_b;
-                if (getenv("RR_DEBUG_CHOICE"))
-                    fprintf(stderr, "[rr] kernel choice: depth %u candidate %d: default %.3f ms, candidate %.3f ms (%.3f)%s\n", depth, cand_b, ms_a, ms_b,
-                            ms_b / ms_a, ch->choice == 2 ? " -> candidate" : ch->choice == 1 ? " -> default" : " (once more)");
-                ch->share = rect_share;
-            }
-        }
-        kernel = ch->choice == 2 ? cand_b : cand_a;
-        // (until the measurement: the round-2 rule for launches of one or two slices -- the path-parallel kernel where the scene is small on screen)
-        if (ch->choice == 0 && cand_b == K_PATHS && rect_share < 0.25) kernel = K_PATHS;
-    }
-    const bool stream_kernel = kernel == K_STREAM, paths_kernel = kernel == K_PATHS, lds_kernel = kernel == K_LDS;
-
     if (!keep) RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
-    const bool timed = (p.flags & RR_DISPATCH_TIME_KERNEL) != 0;
+    const bool timed = (p.flags & RR_DISPATCH_TIME_KERNEL) != 0;      // between a pair of rr_kernel_time events
     if (timed) {
         if (ctx->kev_used >= 4096) return fail(ctx, RR_ERR_STATE, "dispatch: 4096 timed dispatches pending, call rr_kernel_time");
-        while (ctx->kev.size() < (size_t)(ctx->kev_used + 1) * 2) {
-            hipEvent_t e;
-            RR_HIP(hipEventCreate(&e));
-            ctx->kev.push_back(e);
-        }
+        for (hipEvent_t e; ctx->kev.size() < (size_t)(ctx->kev_used + 1) * 2; ctx->kev.push_back(e)) RR_HIP(hipEventCreate(&e));
         RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2], ctx->stream));
     }
-    if (stream_kernel) { if (int r = launch_stream(stats)) return r; }
-    else if (paths_kernel) { if (int r = launch_paths(stats)) return r; }
-    else if (lds_kernel) { if (int r = launch_lds(stats)) return r; }
-    else { if (int r = launch_fused(stats)) return r; }
-    if (timed) {
-        RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2 + 1], ctx->stream));
-        ++ctx->kev_used;
-    }
+    if (int r = launch_kernel(ctx, L, kernel, stats)) return r;
+    if (timed) { RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2 + 1], ctx->stream)); ++ctx->kev_used; }
     if (d_diag) {       // experiments only: dump per-wave {start, cycles, max rays per lane, loop trips}
         std::vector<unsigned long long> h(diag_waves * 8);
         RR_HIP(hipStreamSynchronize(ctx->stream));
         RR_HIP(hipMemcpy(h.data(), d_diag, h.size() * 8, hipMemcpyDeviceToHost));
         (void)hipFree(d_diag);
-        if (FILE* f = fopen(diag_path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+        if (FILE* f = fopen(ctx->dbg_diag.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
     }
-    snprintf(ctx->last_kernel_name, sizeof ctx->last_kernel_name, "%s", stream_kernel ? last_stream_kernel_name() : last_render_kernel_name());
-    ctx->last_kernel = stream_kernel ? 7u : paths_kernel ? 2u : lds_kernel ? 1u : 0u;
+
+    snprintf(ctx->last_kernel_name, sizeof ctx->last_kernel_name, "%s", kernel == K_STREAM ? last_stream_kernel_name() : last_render_kernel_name());
+    ctx->last_kernel = (uint32_t)kernel;
     ctx->W = width; ctx->H = height; ctx->frame_world = ctx->tile_world; ctx->frame_depth = depth;
-    ctx->have_f32 = want_f32; ctx->have_frame = ext_tiles == nullptr; ctx->have_assembled = false;
-    if (!ext_tiles) ctx->frame_base = out_base;
+    ctx->have_f32 = o.want_f32; ctx->have_frame = ext_tiles == nullptr; ctx->have_assembled = false;
+    if (!ext_tiles) ctx->frame_base = o.out_base;
     ctx->last_stats = stats;
-    // pixels actually owned by this rank (partial edge tiles counted exactly)
-    uint64_t px = 0;
-    auto tile_px = [&](uint32_t t) {
-        const uint32_t x0 = (t % tiles_x) * TILE, y0 = (t / tiles_x) * TILE;
-        const uint32_t w = width - x0 < TILE ? width - x0 : TILE, h = height - y0 < TILE ? height - y0 : TILE;
-        return (uint64_t)w * h;
-    };
-    if (!mesh) for (uint32_t t = ctx->tile_rank; t < n_tiles; t += ctx->tile_world) px += tile_px(t);
-    else
-        for (uint32_t t = 0; t < n_tiles; ++t) {
-            const uint32_t tx = t % tiles_x, ty = t / tiles_x;
-            const bool in_rect = part.rect_w == 0 || (tx >= part.rect_x0 && tx < part.rect_x0 + part.rect_w && ty >= part.rect_y0 && ty < part.rect_y0 + part.rect_h);
-            const uint32_t i = part.rect_w == 0 ? t : (ty - part.rect_y0) * part.rect_w + (tx - part.rect_x0);
-            uint32_t owner = 0, slot = 0;
-            if (in_rect) (void)rr_host_mesh_tile_home(&part, i, &owner, &slot);
-            if (in_rect ? owner == ctx->tile_rank : ctx->tile_rank == 0) px += tile_px(t);
-        }
-    px *= depth;
-    ctx->last_pixels = px;
-    ctx->accum_pixels = (keep ? ctx->accum_pixels : 0) + px;
+    ctx->last_pixels = owned_pixels(width, height, ctx->tile_rank, ctx->tile_world, mesh ? &o.part : nullptr) * depth;
+    ctx->accum_pixels = (keep ? ctx->accum_pixels : 0) + ctx->last_pixels;
     return RR_OK;
 }
 
@@ -1510,6 +1394,74 @@ int upload_cams(rr_context* ctx, const rr_scene_constants* c, size_t n)
     return RR_OK;
 }
 
+rr_dispatch_params params_or_default(const rr_dispatch_params* params)
+{
+    rr_dispatch_params p;
+    return params ? *params : (rr_default_dispatch_params(&p), p);
+}
+
+// waits for the context's stream, then reads the device error flag of what it rendered
+int check_error_flag(rr_context* ctx, const char* what)
+{
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    uint32_t err = 0;
+    RR_HIP(hipMemcpy(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost));
+    return err ? fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, what) : RR_OK;
+}
+
+// drawFrame loop: camera constants for n consecutive orbit angles (RefractionDemo.cpp:559-565), the angle advanced past them (:567)
+int orbit_cams(rr_context* ctx, const char* what, float& angle, float angle_step, uint32_t n, float fov_y, float aspect, float zn, float zf,
+               std::vector<rr_scene_constants>& cams)
+{
+    cams.resize(n);
+    for (uint32_t k = 0; k < n; ++k, angle += angle_step)
+        if (int rc = rr_host_camera_orbit(angle, fov_y, aspect, zn, zf, &cams[k])) return fail(ctx, rc, what);
+    return RR_OK;
+}
+
+// zero the counters where every lane will see it (before the fork); the launches then keep adding to them
+int zero_counters_before_fork(rr_context* ctx, rr_dispatch_params& p)
+{
+    if (p.flags & RR_DISPATCH_KEEP_COUNTERS) return RR_OK;
+    RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
+    ctx->accum_pixels = 0; p.flags |= RR_DISPATCH_KEEP_COUNTERS;
+    return RR_OK;
+}
+
+// the lane starts after everything submitted to the context's stream so far
+int fork_lane(rr_context* ctx, uint32_t lane)
+{
+    RR_HIP(hipEventRecord(ctx->lane_fork[lane], ctx->stream));
+    RR_HIP(hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork[lane], 0));
+    return RR_OK;
+}
+
+// Launches on a forked lane (rr_render_orbit_sharded_lane): while the scope lasts, the lane's stream and constant buffer are
+// the context's (no reuse race between lanes; a lane is one stream, its launches stay in order)
+struct LaneScope {
+    rr_context* const ctx;
+    const uint32_t lane;
+    const hipStream_t stream; CamDev* const cams; const size_t cams_cap; const uint32_t in_flight;
+    LaneScope(rr_context* c, uint32_t l)
+        : ctx(c), lane(l), stream(c->stream), cams(c->d_cams), cams_cap(c->cams_cap), in_flight(c->frames_in_flight)
+    {
+        ctx->stream = ctx->lane_stream[lane]; ctx->d_cams = ctx->lane_cams[lane]; ctx->cams_cap = ctx->lane_cams_cap[lane];
+        ctx->frames_in_flight = 1;
+    }
+    ~LaneScope()
+    {
+        ctx->lane_cams[lane] = ctx->d_cams; ctx->lane_cams_cap[lane] = ctx->cams_cap;
+        ctx->stream = stream; ctx->d_cams = cams; ctx->cams_cap = cams_cap; ctx->frames_in_flight = in_flight;
+    }
+    int done(int rc, const char* what)      // the lane's end, behind what `rc` reports on
+    {
+        if (rc != RR_OK) return rc;
+        if (hipError_t e = hipEventRecord(ctx->lane_done[lane], ctx->stream)) return fail(ctx, RR_ERR_DEVICE, what, e);
+        ctx->lane_busy[lane] = true;
+        return RR_OK;
+    }
+};
+
 } // namespace
 
 int rr_dispatch_rays(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispatch_params* params)
@@ -1517,8 +1469,7 @@ int rr_dispatch_rays(rr_context* ctx, uint32_t width, uint32_t height, const rr_
     const Range range_("rr_dispatch_rays");
     if (int r = use_device(ctx)) return r;
     if (!ctx->cam_set) return fail(ctx, RR_ERR_STATE, "rr_dispatch_rays: rr_set_camera first");
-    rr_dispatch_params p;
-    if (params) p = *params; else rr_default_dispatch_params(&p);
+    rr_dispatch_params p = params_or_default(params);
     if (int r = upload_cams(ctx, &ctx->cam, 1)) return r;
     return dispatch_impl(ctx, width, height, 1, ctx->d_cams, &ctx->cam, p, nullptr, 0, false);
 }
@@ -1528,8 +1479,7 @@ int rr_dispatch_rays_batch(rr_context* ctx, uint32_t width, uint32_t height, uin
 {
     if (int r = use_device(ctx)) return r;
     if (!constants || depth == 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_dispatch_rays_batch: need depth >= 1 constants");
-    rr_dispatch_params p;
-    if (params) p = *params; else rr_default_dispatch_params(&p);
+    rr_dispatch_params p = params_or_default(params);
     if (int r = upload_cams(ctx, constants, depth)) return r;
     return dispatch_impl(ctx, width, height, depth, ctx->d_cams, constants, p, nullptr, 0, false);
 }
@@ -1549,11 +1499,7 @@ int rr_read_frame_slice(rr_context* ctx, uint32_t slice, uint8_t* rgba8, float* 
         if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_rgba8 + ctx->frame_base + slice * n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_f32 + ctx->frame_base + slice * n, n * 16, hipMemcpyDeviceToHost, ctx->stream));
     }
-    RR_HIP(hipStreamSynchronize(ctx->stream));
-    uint32_t err = 0;
-    RR_HIP(hipMemcpy(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost));
-    if (err) return fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, "traversal stack overflow: frame invalid");
-    return RR_OK;
+    return check_error_flag(ctx, "traversal stack overflow: frame invalid");
 }
 
 int rr_read_frame(rr_context* ctx, uint8_t* rgba8, float* rgba32f) { return rr_read_frame_slice(ctx, 0, rgba8, rgba32f); }
@@ -1563,9 +1509,8 @@ int rr_export_tiles(rr_context* ctx, void* d_dst)
     if (int r = use_device(ctx)) return r;
     if (!d_dst) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_export_tiles: null destination");
     if (!ctx->have_frame || ctx->frame_world < 2) return fail(ctx, RR_ERR_STATE, "rr_export_tiles: no sharded frame");
-    uint32_t tx, nt, local, mx;
-    tile_counts(ctx->W, ctx->H, ctx->tile_rank, ctx->frame_world, tx, nt, local, mx);
-    RR_HIP(hipMemcpyAsync(d_dst, ctx->d_rgba8 + ctx->frame_base, (size_t)mx * TILE * TILE * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    const Tiles t = tile_counts(ctx->W, ctx->H, ctx->tile_rank, ctx->frame_world);
+    RR_HIP(hipMemcpyAsync(d_dst, ctx->d_rgba8 + ctx->frame_base, (size_t)t.max_local * TILE * TILE * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return RR_OK;
 }
 
@@ -1574,21 +1519,15 @@ int rr_assemble_tiles(rr_context* ctx, const void* d_gathered, uint32_t world, v
     if (int r = use_device(ctx)) return r;
     if (!d_gathered || world == 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_assemble_tiles: bad arguments");
     if (!ctx->have_frame || ctx->W == 0) return fail(ctx, RR_ERR_STATE, "rr_assemble_tiles: dispatch first (frame size)");
-    uint32_t tx, nt, local, mx;
-    tile_counts(ctx->W, ctx->H, 0, world, tx, nt, local, mx);
+    const Tiles t = tile_counts(ctx->W, ctx->H, 0, world);
     uint32_t* dst = (uint32_t*)d_frame;
     if (!dst) {
         const size_t n = (size_t)ctx->W * ctx->H;
-        if (n > ctx->assembled_elems) {
-            RR_HIP(hipStreamSynchronize(ctx->stream));
-            dfree(ctx->d_assembled);
-            ctx->assembled_elems = 0;
-            RR_HIP(hipMalloc(&ctx->d_assembled, n * 4));
-            ctx->assembled_elems = n;
-        }
+        if (n > ctx->assembled_elems)
+            if (int r = grow(ctx, ctx->d_assembled, ctx->assembled_elems, n)) return r;
         dst = ctx->d_assembled;
     }
-    RR_HIP(launch_assemble_tiles((const uint32_t*)d_gathered, dst, ctx->W, ctx->H, tx, nt, world, mx, ctx->stream));
+    RR_HIP(launch_assemble_tiles((const uint32_t*)d_gathered, dst, ctx->W, ctx->H, t.tiles_x, t.n_tiles, world, t.max_local, ctx->stream));
     if (!d_frame) ctx->have_assembled = true;
     return RR_OK;
 }
@@ -1605,14 +1544,9 @@ int orbit_impl(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispat
     if (!angle) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "render_orbit: null angle");
     if (n_frames == 0) return RR_OK;
     if (batch == 0) batch = 1;
-    rr_dispatch_params p;
-    if (params) p = *params; else rr_default_dispatch_params(&p);
-    std::vector<rr_scene_constants> cams(n_frames);
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        int rc = rr_host_camera_orbit(*angle, fov_y, aspect, zn, zf, &cams[k]);      // RefractionDemo.cpp:559-565
-        if (rc != RR_OK) return fail(ctx, rc, "render_orbit: camera");
-        *angle += angle_step;                                                       // :567
-    }
+    rr_dispatch_params p = params_or_default(params);
+    std::vector<rr_scene_constants> cams;
+    if (int r = orbit_cams(ctx, "render_orbit: camera", *angle, angle_step, n_frames, fov_y, aspect, zn, zf, cams)) return r;
     ctx->cam = cams.back(); ctx->cam_set = true;
     if (int r = upload_cams(ctx, cams.data(), n_frames)) return r;
     const bool keep_first = (p.flags & RR_DISPATCH_KEEP_COUNTERS) != 0;
@@ -1622,14 +1556,17 @@ int orbit_impl(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispat
     uint32_t lanes = ctx->frames_in_flight < n_batches ? ctx->frames_in_flight : n_batches;
     if ((p.flags & RR_DISPATCH_TIME_KERNEL) || !ctx->dbg_diag.empty()) lanes = 1;
     // k_render_lds is persistent -- its workgroups hold every CU until the launch is over --, so two of its launches in flight only
-    // get in each other's way (sphere.obj Depth 64: 145 us per frame one at a time, 167 with two in flight)
+    // get in each other's way (sphere.obj Depth 64: 145 us per frame one at a time, 167 with two in flight).  Does it render the
+    // first launch?  (As dispatch_impl would pick it, changing no choice.)
     bool one_kernel_at_a_time = false;
-    if (scene_fits_lds(ctx) && ctx->tile_world == 1) {
+    if (ctx->tlas_built && width && height) {
         const uint32_t d = batch < n_frames ? batch : n_frames;
-        const rr_context::KernelChoice* c = ctx->ch_many.peek(rr_context::choice_key(width, height, p, d));
-        const bool alt = c && c->choice == 2;
-        const bool lds_renders = ctx->dbg_kernel == 0 ? (lds_default_depth(d) ? !alt : alt) : ctx->dbg_kernel == 4;
-        one_kernel_at_a_time = d >= 3u && lds_renders;
+        uint32_t rect[4];
+        (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : cams.data(), d, width, height, rect);
+        const LaunchFacts lf = launch_facts(ctx, width, height, d, rect, p, ctx->tile_world > 1 || ext_tiles, false);
+        const KernelPick pk = pick_kernel(scene_facts(ctx), lf, ctx->dbg);
+        const KernelChoice* ch = pk.cls == CLS_NONE ? nullptr : ctx->ch[pk.cls].peek(choice_key(width, height, p, d));
+        one_kernel_at_a_time = chosen_kernel(pk, ch, lf.rect_share) == K_LDS;
         if (lanes > 1 && one_kernel_at_a_time) lanes = 1;
     }
     if (host_out) {          // streaming to host: the copy of one region overlaps the rendering of the other
@@ -1646,16 +1583,12 @@ int orbit_impl(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispat
         return RR_OK;
     }
     if (!ext_tiles) {        // all output regions exist before anything overlaps
-        uint32_t tiles_x, n_tiles, local, max_local;
         if (width == 0 || height == 0 || width > 32768 || height > 32768) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "dispatch: bad frame size or depth");
-        tile_counts(width, height, ctx->tile_rank, ctx->tile_world, tiles_x, n_tiles, local, max_local);
-        const size_t slice_elems = ctx->tile_world > 1 ? (size_t)max_local * TILE * TILE : (size_t)width * height;
+        const Tiles t = tile_counts(width, height, ctx->tile_rank, ctx->tile_world);
+        const size_t slice_elems = ctx->tile_world > 1 ? (size_t)t.max_local * TILE * TILE : (size_t)width * height;
         if (int r = ensure_frame_buffers(ctx, slice_elems * batch * lanes, (p.flags & RR_DISPATCH_FLOAT_OUTPUT) != 0)) return r;
     }
-    if (!keep_first) {
-        RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
-        ctx->accum_pixels = 0;
-    }
+    if (int r = zero_counters_before_fork(ctx, p)) return r;
     for (uint32_t l = 0; l < lanes; ++l) {
         if (int r = ensure_lane(ctx, l)) return r;
         if (ctx->lane_busy[l]) { RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[l], 0)); ctx->lane_busy[l] = false; }
@@ -1708,11 +1641,7 @@ int rr_render_orbit_to_host(rr_context* ctx, uint32_t width, uint32_t height, co
     if (!host_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_to_host: null host buffer");
     if (int r = orbit_impl(ctx, width, height, params, angle, angle_step, n_frames, frames_per_dispatch, fov_y, aspect, zn, zf,
                            nullptr, 0, host_rgba8)) return r;
-    RR_HIP(hipStreamSynchronize(ctx->stream));          // every frame is in host memory on return
-    uint32_t err = 0;
-    RR_HIP(hipMemcpy(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost));
-    if (err) return fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, "device error flag set: frames invalid");
-    return RR_OK;
+    return check_error_flag(ctx, "device error flag set: frames invalid");          // every frame is in host memory on return
 }
 
 int rr_render_orbit_sharded(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispatch_params* params, float* angle,
@@ -1721,10 +1650,9 @@ int rr_render_orbit_sharded(rr_context* ctx, uint32_t width, uint32_t height, co
 {
     if (int r = use_device(ctx)) return r;
     if (!d_tiles) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_sharded: null tile buffer");
-    uint32_t tx, nt, local, mx;
-    tile_counts(width ? width : 1, height ? height : 1, ctx->tile_rank, ctx->tile_world, tx, nt, local, mx);
+    const Tiles t = tile_counts(width ? width : 1, height ? height : 1, ctx->tile_rank, ctx->tile_world);
     const uint64_t bpp = (params && (params->flags & RR_DISPATCH_TILES_RGB8)) ? 3 : 4;
-    if (frame_stride_bytes < (uint64_t)mx * TILE * TILE * bpp || (frame_stride_bytes & 3u))
+    if (frame_stride_bytes < (uint64_t)t.max_local * TILE * TILE * bpp || (frame_stride_bytes & 3u))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_sharded: frame stride smaller than a tile buffer");
     return orbit_impl(ctx, width, height, params, angle, angle_step, n_frames, frames_per_dispatch, fov_y, aspect, zn, zf,
                       (uint32_t*)d_tiles, (size_t)(frame_stride_bytes / 4));
@@ -1737,37 +1665,12 @@ int rr_render_orbit_sharded_lane(rr_context* ctx, uint32_t width, uint32_t heigh
     if (int r = use_device(ctx)) return r;
     if (lane >= rr_context::MAX_LANES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_sharded_lane: lane out of range");
     if (int r = ensure_lane(ctx, lane)) return r;
-    rr_dispatch_params p;
-    if (params) p = *params; else rr_default_dispatch_params(&p);
-    if (!(p.flags & RR_DISPATCH_KEEP_COUNTERS)) {      // zero the counters where every lane will see it: before the fork
-        RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
-        ctx->accum_pixels = 0;
-        p.flags |= RR_DISPATCH_KEEP_COUNTERS;
-    }
-    // fork: the lane starts after everything submitted to the context's stream so far
-    RR_HIP(hipEventRecord(ctx->lane_fork[lane], ctx->stream));
-    RR_HIP(hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork[lane], 0));
-    hipStream_t main_stream = ctx->stream;
-    CamDev* main_cams = ctx->d_cams;
-    size_t main_cap = ctx->cams_cap;
-    const uint32_t main_in_flight = ctx->frames_in_flight;
-    ctx->stream = ctx->lane_stream[lane];               // the lane has its own constant buffer: no reuse race between lanes
-    ctx->d_cams = ctx->lane_cams[lane];
-    ctx->cams_cap = ctx->lane_cams_cap[lane];
-    ctx->frames_in_flight = 1;                          // a lane is one stream: its launches stay in order
-    int rc = rr_render_orbit_sharded(ctx, width, height, &p, angle, angle_step, n_frames, frames_per_dispatch, fov_y, aspect, zn,
-                                     zf, d_tiles, frame_stride_bytes);
-    hipError_t e = rc == RR_OK ? hipEventRecord(ctx->lane_done[lane], ctx->stream) : hipSuccess;
-    ctx->lane_cams[lane] = ctx->d_cams;
-    ctx->lane_cams_cap[lane] = ctx->cams_cap;
-    ctx->stream = main_stream;
-    ctx->d_cams = main_cams;
-    ctx->cams_cap = main_cap;
-    ctx->frames_in_flight = main_in_flight;
-    if (rc != RR_OK) return rc;
-    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "rr_render_orbit_sharded_lane: event", e);
-    ctx->lane_busy[lane] = true;
-    return RR_OK;
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = zero_counters_before_fork(ctx, p)) return r;
+    if (int r = fork_lane(ctx, lane)) return r;
+    LaneScope scope(ctx, lane);
+    return scope.done(rr_render_orbit_sharded(ctx, width, height, &p, angle, angle_step, n_frames, frames_per_dispatch, fov_y, aspect, zn,
+                                               zf, d_tiles, frame_stride_bytes), "rr_render_orbit_sharded_lane: event");
 }
 
 int rr_mesh_partition_for_orbit(rr_context* ctx, uint32_t width, uint32_t height, float angle, float angle_step, uint32_t n_frames,
@@ -1775,12 +1678,8 @@ int rr_mesh_partition_for_orbit(rr_context* ctx, uint32_t width, uint32_t height
 {
     if (!ctx || !out || n_frames == 0) return RR_ERR_INVALID_ARGUMENT;
     if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_mesh_partition_for_orbit: build the BLAS and TLAS first");
-    std::vector<rr_scene_constants> cams(n_frames);
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        const int rc = rr_host_camera_orbit(angle, fov_y, aspect, zn, zf, &cams[k]);
-        if (rc != RR_OK) return fail(ctx, rc, "rr_mesh_partition_for_orbit: camera");
-        angle += angle_step;
-    }
+    std::vector<rr_scene_constants> cams;
+    if (int r = orbit_cams(ctx, "rr_mesh_partition_for_orbit: camera", angle, angle_step, n_frames, fov_y, aspect, zn, zf, cams)) return r;
     return rr_host_mesh_partition(ctx->scene_bounds, cams.data(), n_frames, width, height, ctx->tile_world, out);
 }
 
@@ -1794,15 +1693,10 @@ int rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t 
     if (!angle || !d_mesh_tiles || n_frames == 0 || (mesh_stride_bytes & 3u) || (bg_stride_bytes & 3u))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_mesh_sharded_lane: bad arguments");
     if (int r = ensure_lane(ctx, lane)) return r;
-    rr_dispatch_params p;
-    if (params) p = *params; else rr_default_dispatch_params(&p);
+    rr_dispatch_params p = params_or_default(params);
     p.flags |= RR_DISPATCH_TILES_RGB8;
-    std::vector<rr_scene_constants> cams(n_frames);
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        const int rc = rr_host_camera_orbit(*angle, fov_y, aspect, zn, zf, &cams[k]);
-        if (rc != RR_OK) return fail(ctx, rc, "render_orbit: camera");
-        *angle += angle_step;
-    }
+    std::vector<rr_scene_constants> cams;
+    if (int r = orbit_cams(ctx, "render_orbit: camera", *angle, angle_step, n_frames, fov_y, aspect, zn, zf, cams)) return r;
     // the one partition of this launch: its buffers are checked against it and the kernel renders it (DEBUG_NO_CULL: the whole
     // frame is mesh tiles, as rr_host_mesh_partition(bounds, NULL, ...) says)
     rr_mesh_partition part;
@@ -1812,34 +1706,14 @@ int rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t 
     if (mesh_stride_bytes < (uint64_t)part.max_mesh_tiles_per_rank * TILE * TILE * 3 ||
         (ctx->tile_rank == 0 && part.n_bg_tiles && (!d_bg_tiles || bg_stride_bytes < (uint64_t)part.n_bg_tiles * TILE * TILE * 3)))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_orbit_mesh_sharded_lane: tile buffers smaller than rr_mesh_partition_for_orbit says");
-    const bool keep = (p.flags & RR_DISPATCH_KEEP_COUNTERS) != 0;
-    if (!keep) {                                        // zero the counters where every lane will see it: before the fork
-        RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
-        ctx->accum_pixels = 0;
-        p.flags |= RR_DISPATCH_KEEP_COUNTERS;
-    }
+    if (int r = zero_counters_before_fork(ctx, p)) return r;
     ctx->cam = cams.back(); ctx->cam_set = true;
-    RR_HIP(hipEventRecord(ctx->lane_fork[lane], ctx->stream));
-    RR_HIP(hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork[lane], 0));
-    hipStream_t main_stream = ctx->stream;
-    CamDev* main_cams = ctx->d_cams;
-    size_t main_cap = ctx->cams_cap;
-    ctx->stream = ctx->lane_stream[lane];               // the lane has its own constant buffer: no reuse race between lanes
-    ctx->d_cams = ctx->lane_cams[lane];
-    ctx->cams_cap = ctx->lane_cams_cap[lane];
+    if (int r = fork_lane(ctx, lane)) return r;
+    LaneScope scope(ctx, lane);
     int rc = upload_cams(ctx, cams.data(), n_frames);
     const MeshOut mo = { &part, (uint32_t*)d_bg_tiles, (size_t)(bg_stride_bytes / 4) };
     if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, n_frames, ctx->d_cams, cams.data(), p, (uint32_t*)d_mesh_tiles, (size_t)(mesh_stride_bytes / 4), true, 0, 0, &mo);
-    hipError_t e = rc == RR_OK ? hipEventRecord(ctx->lane_done[lane], ctx->stream) : hipSuccess;
-    ctx->lane_cams[lane] = ctx->d_cams;
-    ctx->lane_cams_cap[lane] = ctx->cams_cap;
-    ctx->stream = main_stream;
-    ctx->d_cams = main_cams;
-    ctx->cams_cap = main_cap;
-    if (rc != RR_OK) return rc;
-    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "rr_render_orbit_mesh_sharded_lane: event", e);
-    ctx->lane_busy[lane] = true;
-    return RR_OK;
+    return scope.done(rc, "rr_render_orbit_mesh_sharded_lane: event");
 }
 
 int rr_assemble_frames_mesh_rgb8(rr_context* ctx, const void* d_gathered, uint64_t rank_stride_bytes, uint64_t frame_stride_bytes,
@@ -1873,11 +1747,10 @@ int rr_assemble_frames(rr_context* ctx, const void* d_gathered, uint32_t world, 
     if (int r = use_device(ctx)) return r;
     if (!d_gathered || !d_frames || world == 0 || width == 0 || height == 0 || ((rank_stride_bytes | frame_stride_bytes | out_stride_bytes) & 3u))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_assemble_frames: bad arguments");
-    uint32_t tx, nt, local, mx;
-    tile_counts(width, height, 0, world, tx, nt, local, mx);
-    if (frame_stride_bytes < (uint64_t)mx * TILE * TILE * 4 || out_stride_bytes < (uint64_t)width * height * 4)
+    const Tiles t = tile_counts(width, height, 0, world);
+    if (frame_stride_bytes < (uint64_t)t.max_local * TILE * TILE * 4 || out_stride_bytes < (uint64_t)width * height * 4)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_assemble_frames: stride too small");
-    RR_HIP(launch_assemble_frames((const uint32_t*)d_gathered, (uint32_t*)d_frames, width, height, tx, nt, world,
+    RR_HIP(launch_assemble_frames((const uint32_t*)d_gathered, (uint32_t*)d_frames, width, height, t.tiles_x, t.n_tiles, world,
                                   rank_stride_bytes / 4, frame_stride_bytes / 4, out_stride_bytes / 4, n_frames, ctx->stream));
     return RR_OK;
 }
@@ -1891,11 +1764,10 @@ int rr_assemble_frames_rgb8(rr_context* ctx, const void* d_gathered, uint32_t wo
     if (!d_gathered || !d_frames || world == 0 || width == 0 || height == 0 ||
         ((rank_stride_bytes | frame_stride_bytes | out_stride_bytes | (uint64_t)(uintptr_t)d_gathered) & 3u))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_assemble_frames_rgb8: bad arguments (strides and buffers are 4-byte aligned)");
-    uint32_t tx, nt, local, mx;
-    tile_counts(width, height, 0, world, tx, nt, local, mx);
-    if (frame_stride_bytes < (uint64_t)mx * TILE * TILE * 3 || out_stride_bytes < (uint64_t)width * height * 4)
+    const Tiles t = tile_counts(width, height, 0, world);
+    if (frame_stride_bytes < (uint64_t)t.max_local * TILE * TILE * 3 || out_stride_bytes < (uint64_t)width * height * 4)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_assemble_frames_rgb8: stride too small");
-    RR_HIP(launch_assemble_frames_rgb8((const uint8_t*)d_gathered, (uint32_t*)d_frames, width, height, tx, nt, world,
+    RR_HIP(launch_assemble_frames_rgb8((const uint8_t*)d_gathered, (uint32_t*)d_frames, width, height, t.tiles_x, t.n_tiles, world,
                                        rank_stride_bytes, frame_stride_bytes, out_stride_bytes / 4, n_frames, ctx->stream));
     return RR_OK;
 }
@@ -2080,14 +1952,7 @@ int rr_trace_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
     if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_trace_rays: build the BLAS and TLAS first");
     if (n == 0) return RR_OK;
     if (!rays || !hits) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_trace_rays: null arrays");
-    if (n > ctx->ray_cap) {
-        RR_HIP(hipStreamSynchronize(ctx->stream));
-        dfree(ctx->d_rays); dfree(ctx->d_hits);
-        ctx->ray_cap = 0;
-        RR_HIP(hipMalloc(&ctx->d_rays, (size_t)n * sizeof(rr_ray_dev)));
-        RR_HIP(hipMalloc(&ctx->d_hits, (size_t)n * sizeof(rr_hit_dev)));
-        ctx->ray_cap = n;
-    }
+    if (int r = ensure_rays(ctx, n)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
     RR_HIP(hipMemsetAsync(&ctx->d_cnt->error, 0, 4, ctx->stream));
@@ -2107,14 +1972,7 @@ int rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
     if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays: build the BLAS and TLAS first");
     if (n == 0) return RR_OK;
     if (!rays || !hits) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays: null arrays");
-    if (n > ctx->ray_cap) {
-        RR_HIP(hipStreamSynchronize(ctx->stream));
-        dfree(ctx->d_rays); dfree(ctx->d_hits);
-        ctx->ray_cap = 0;
-        RR_HIP(hipMalloc(&ctx->d_rays, (size_t)n * sizeof(rr_ray_dev)));
-        RR_HIP(hipMalloc(&ctx->d_hits, (size_t)n * sizeof(rr_hit_dev)));
-        ctx->ray_cap = n;
-    }
+    if (int r = ensure_rays(ctx, n)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
     RR_HIP(hipMemcpyAsync(ctx->d_rays, rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));

@@ -23,7 +23,7 @@ hipError_t launch_render_paths(const SceneDev& sc, const DispatchDev& a, int sta
 hipError_t launch_assemble_frames_mesh_rgb8(const uint8_t* gathered, const uint8_t* bg, uint32_t* frames, uint32_t W, uint32_t H, const MeshPartDev& mp,
                                             size_t rank_stride_b, size_t frame_stride_b, size_t bg_stride_b, size_t out_stride, uint32_t n_frames, hipStream_t s);
 // ---- rr_render_stream.hip: one kernel per ray generation, rays in HBM queues, lanes refilled as their rays end (two-level scenes)
-hipError_t launch_render_stream(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, int stack, uint32_t n_wg, bool stats, hipStream_t st, int waves = 6);
+hipError_t launch_render_stream(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, int stack, uint32_t n_wg, bool stats, hipStream_t st);
 const char* last_stream_kernel_name();
 // the instantiation the calling thread's last launch_render_* call launched, e.g. "k_render_fused<19, 2, false, false, false, unsigned int, 0>"
 const char* last_render_kernel_name();

@@ -539,12 +539,11 @@ static hipError_t launch_stream_sw(const SceneDev& sc, const DispatchDev& a, con
 }
 
 // two-level scenes whose stack entries fit 16 bits, trees of at most 39 levels, max_reflect <= 2, max_refract < STREAM_MAX_GEN - 1
-hipError_t launch_render_stream(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, int stack, uint32_t n_wg, bool stats, hipStream_t st, int waves)
+hipError_t launch_render_stream(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, int stack, uint32_t n_wg, bool stats, hipStream_t st)
 {
     if (a.n_blocks == 0) return hipSuccess;
     // (built for six waves per SIMD: the eight-wave build spilled into every loop header, those for seven and five measured up to
     // 8 % slower on C5 when the kernel was tuned; -DRR_STREAM_WPS=<n> rebuilds it for another number)
-    (void)waves;
     if (stack <= 30) return stats ? launch_stream_sw<30, true, RR_STREAM_WPS>(sc, a, s, n_wg, st) : launch_stream_sw<30, false, RR_STREAM_WPS>(sc, a, s, n_wg, st);
     return stats ? launch_stream_sw<39, true, RR_STREAM_WPS>(sc, a, s, n_wg, st) : launch_stream_sw<39, false, RR_STREAM_WPS>(sc, a, s, n_wg, st);
 }

@@ -1,0 +1,119 @@
+// Driver for the kernel-choice policy (csrc/rr_choice.cpp), built with g++ by tests/test_kernel_choice.py.  Reads one command
+// per line from stdin and prints one line per command:
+//   pick <single need blas_tris pool_nodes pool_refs lds_fits> <depth n_tiles world compact mesh have_rect share refract reflect
+//        no_cull diag> <dbg_kernel dbg_stack tlas32>          -> kernel cls cand_a cand_b kernel-before-any-measurement
+//   fused <scene facts as pick> <depth reflect> <dbg_kernel dbg_stack tlas32>   -> stack pend stack16
+//   key <W H refract reflect depth>                          -> choice_key
+//   new                                                      -> (a fresh class) ok
+//   due <key share no_cull>        -> find + measure_due: due choice seen
+//   rec <ms_a ms_b share>          -> record_timings on the entry of the last `due`: choice
+//   peek <key>                     -> choice of the shape, -1 if the class does not hold it
+//   owned <W H world mode>         -> pixels of every rank summed, pixels of rank 0, mesh tiles, background tiles
+//                                     (mode 0 round robin, 1 mesh partition of a unit box seen by the orbit camera, 2 its
+//                                     whole-frame partition as under DEBUG_NO_CULL)
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+
+#include "../../refraction_raytracing_dxr_amd/csrc/rr_choice.h"
+
+using namespace rr;
+
+static SceneFacts read_scene(std::istream& in)
+{
+    SceneFacts s;
+    int single, fits;
+    in >> single >> s.need >> s.blas_tris >> s.pool_nodes >> s.pool_refs >> fits;
+    s.single_identity = single != 0; s.lds_fits = fits != 0;
+    return s;
+}
+
+static DebugFacts read_debug(std::istream& in)
+{
+    DebugFacts d;
+    int t32;
+    in >> d.kernel >> d.stack >> t32;
+    d.tlas32 = t32 != 0;
+    return d;
+}
+
+int main()
+{
+    ChoiceClass cls;
+    KernelChoice* cur = nullptr;
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string cmd;
+        if (!(in >> cmd)) continue;
+        if (cmd == "pick") {
+            const SceneFacts s = read_scene(in);
+            LaunchFacts l;
+            int compact, mesh, have_rect, no_cull, diag;
+            in >> l.depth >> l.n_tiles >> l.tile_world >> compact >> mesh >> have_rect >> l.rect_share >> l.max_refract >> l.max_reflect >> no_cull >> diag;
+            l.compact = compact != 0; l.mesh = mesh != 0; l.have_rect = have_rect != 0; l.no_cull = no_cull != 0; l.diag = diag != 0;
+            const DebugFacts d = read_debug(in);
+            const KernelPick pk = pick_kernel(s, l, d);
+            printf("%d %d %d %d %d\n", pk.kernel, pk.cls, pk.cand_a, pk.cand_b, chosen_kernel(pk, nullptr, l.rect_share));
+        } else if (cmd == "fused") {
+            const SceneFacts s = read_scene(in);
+            uint32_t depth;
+            int reflect;
+            in >> depth >> reflect;
+            const DebugFacts d = read_debug(in);
+            const FusedVariant v = fused_variant(s, depth, reflect, d);
+            printf("%d %d %d\n", v.stack, v.pend, v.stack16 ? 1 : 0);
+        } else if (cmd == "key") {
+            uint32_t w, h, depth;
+            rr_dispatch_params p = {};
+            in >> w >> h >> p.max_refract >> p.max_reflect >> depth;
+            printf("%llu\n", choice_key(w, h, p, depth));
+        } else if (cmd == "new") {
+            cls = ChoiceClass();
+            cur = nullptr;
+            printf("ok\n");
+        } else if (cmd == "due") {
+            unsigned long long key;
+            double share;
+            int no_cull;
+            in >> key >> share >> no_cull;
+            cur = cls.find(key);
+            const bool due = measure_due(*cur, share, no_cull != 0);
+            printf("%d %d %u\n", due ? 1 : 0, cur->choice, cur->seen);
+        } else if (cmd == "rec") {
+            float a, b;
+            double share;
+            in >> a >> b >> share;
+            record_timings(*cur, a, b, share);
+            printf("%d\n", cur->choice);
+        } else if (cmd == "peek") {
+            unsigned long long key;
+            in >> key;
+            const KernelChoice* c = cls.peek(key);
+            printf("%d\n", c ? c->choice : -1);
+        } else if (cmd == "owned") {
+            uint32_t w, h, world;
+            int mode;
+            in >> w >> h >> world >> mode;
+            rr_mesh_partition part = {};
+            if (mode) {
+                const float box[6] = { -1, -1, -1, 1, 1, 1 };
+                rr_scene_constants cam;
+                if (rr_host_camera_orbit(0.01f, float(52.0 / 180.0 * 3.1415), 1.333f, 1.0f, 125.0f, &cam) != RR_OK ||
+                    rr_host_mesh_partition(box, mode == 1 ? &cam : nullptr, 1, w, h, world, &part) != RR_OK) { printf("error\n"); continue; }
+            }
+            unsigned long long sum = 0, rank0 = 0;
+            for (uint32_t r = 0; r < world; ++r) {
+                const uint64_t px = owned_pixels(w, h, r, world, mode ? &part : nullptr);
+                sum += px;
+                if (r == 0) rank0 = px;
+            }
+            printf("%llu %llu %u %u\n", sum, rank0, part.n_mesh_tiles, part.n_bg_tiles);
+        } else {
+            printf("unknown\n");
+        }
+        fflush(stdout);
+    }
+    return 0;
+}

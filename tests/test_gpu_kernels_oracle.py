@@ -163,7 +163,7 @@ def screen_rect(scene, cams, W, H):
 
 
 def expected_kernel(kernel, scene, W, H, cams, kw, need, flags=0, shape=0, sharded=False):
-    """the kernel the forced switch must have rendered the launch with (rr_capi.cpp dispatch_impl, "the candidates")"""
+    """the kernel the forced switch must have rendered the launch with (rr_choice.cpp pick_kernel)"""
     depth = len(cams)
     refl = kw.get("max_reflect", 2)
     if kernel == "lds":

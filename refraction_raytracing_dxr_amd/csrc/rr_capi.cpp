@@ -63,23 +63,74 @@ struct Range {
 
 namespace {
 
+// What the context allocates is held by these owners: each releases what it holds when it goes (errors ignored), so that an
+// early return frees its temporaries and rr_destroy only has to wait for the streams.
+
+// n units of `unit` bytes (by default: n elements of T) in device memory, or in page-locked host memory; size() is 0 while
+// nothing is held
+template <class T, bool Pinned = false> class Buf {
+public:
+    Buf() = default;
+    Buf(Buf&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); }
+    Buf& operator=(Buf&& o) noexcept { if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(n_, o.n_); } return *this; }
+    ~Buf() { reset(); }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    void reset() { if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; n_ = 0; }
+    hipError_t alloc(size_t n, size_t unit = sizeof(T))      // (what was held is released first)
+    {
+        reset();
+        void* p = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&p, n * unit, hipHostMallocDefault) : hipMalloc(&p, n * unit);
+        if (e == hipSuccess) { p_ = static_cast<T*>(p); n_ = n; }
+        return e;
+    }
+    int grow(rr_context* ctx, size_t n);
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+template <class T> using DevBuf = Buf<T>;
+template <class T> using HostBuf = Buf<T, true>;
+
+// an event or a stream, created with explicit flags
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)> class Handle {
+public:
+    Handle() = default;
+    Handle(Handle&& o) noexcept { std::swap(h_, o.h_); }     // (std::vector<Event>)
+    ~Handle() { reset(); }
+    H get() const { return h_; }
+    void reset() { if (h_) (void)Destroy(h_); h_ = nullptr; }
+    hipError_t create(unsigned flags)
+    {
+        reset();
+        const hipError_t e = Create(&h_, flags);
+        if (e != hipSuccess) h_ = nullptr;
+        return e;
+    }
+private:
+    H h_ = nullptr;
+};
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+
 struct MeshRes {
-    float*    d_verts = nullptr;     // n_verts * 8 floats
-    uint32_t* d_idx = nullptr;
+    DevBuf<float>    d_verts;        // n_verts * 8 floats
+    DevBuf<uint32_t> d_idx;
     uint32_t  n_verts = 0, n_idx = 0, n_tris = 0;
-    BvhNode*  nodes = nullptr;       // fp32 hierarchy (builder output, rr_download_blas)
-    QNode*    qnodes = nullptr;      // what traversal reads: the same nodes with fp16 planes on the grid of the bounds
+    DevBuf<BvhNode> nodes;           // fp32 hierarchy (builder output, rr_download_blas)
+    DevBuf<QNode>   qnodes;          // what traversal reads: the same nodes with fp16 planes on the grid of the bounds
     QGrid     grid = { { 0, 0, 0 }, { 1, 1, 1 } };
-    TriRec*   tris = nullptr;
-    NrmRec*   nrms = nullptr;
+    DevBuf<TriRec> tris;
+    DevBuf<NrmRec> nrms;
     bool      built = false;
     float     bounds[6] = { 0, 0, 0, 0, 0, 0 };
     float     scale = 1.0f;          // max |bounds|
     uint32_t  depth = 0;
     // update builds (RR_BUILD_ALLOW_UPDATE / PERFORM_UPDATE)
-    int32_t*  links = nullptr;       // ALLOW_UPDATE builds: (parent << 1 | child slot) of every node (launch_keep_links)
-    uint32_t* visit = nullptr;       // ALLOW_UPDATE builds: n_tris-1 arrival counters of the refit
-    uint32_t* d_upd = nullptr;       // 8 words: refit bounds (ordered uints) [0,6), device vertex check [6] scratch, [7] sticky reject
+    DevBuf<int32_t>  links;          // ALLOW_UPDATE builds: (parent << 1 | child slot) of every node (launch_keep_links)
+    DevBuf<uint32_t> visit;          // ALLOW_UPDATE builds: n_tris-1 arrival counters of the refit
+    DevBuf<uint32_t> d_upd;          // 8 words: refit bounds (ordered uints) [0,6), device vertex check [6] scratch, [7] sticky reject
     bool      allow_update = false;
     bool      stale = false;         // vertices replaced since the last build: the BLAS must be rebuilt or updated before a TLAS build
     bool      dev_pending = false;   // a device vertex update whose verdict (d_upd[7]) the next build reads
@@ -95,28 +146,37 @@ struct CounterBlock {
     uint32_t pad[3];
 };
 
+// the k_stream_* buffers of one stream slot; render_stream gives the kernels a StreamDev of them
+struct StreamSet {
+    DevBuf<float4>   q[2];           // entries of 3 x float4 (q[1] is allocated last: its size is the set's queue capacity)
+    DevBuf<uint32_t> fill[2];
+    DevBuf<uint32_t> heads;          // head counters and, behind them, the chunk ticket counters
+    DevBuf<float4>   slots;          // units of 4 x float4 per pixel
+    DevBuf<uint8_t>  pending;        // one per pixel (allocated after slots: its size is the set's pixel count)
+};
+
 } // namespace
 
 struct rr_context {
     int device = 0;
     int n_cus = 256;
-    hipStream_t own_stream = nullptr;
+    Stream      own_stream;          // (declared first: released last)
     hipStream_t stream = nullptr;
     std::string err;
 
     std::vector<MeshRes> meshes;
 
-    float4* d_env = nullptr;
+    DevBuf<float4> d_env;
     int env_w = 0, env_h = 0;
 
     // TLAS
     std::vector<rr_instance_desc> inst_host;
-    InstDev* d_insts = nullptr;
-    BvhNode* d_pool_nodes = nullptr;   // fp32 TLAS nodes (builder output)
-    QNode*   d_pool_qnodes = nullptr;  // flattened scene as traversal reads it: TLAS nodes, then every BLAS in use
+    DevBuf<InstDev> d_insts;
+    DevBuf<BvhNode> d_pool_nodes;      // fp32 TLAS nodes (builder output)
+    DevBuf<QNode>   d_pool_qnodes;     // flattened scene as traversal reads it: TLAS nodes, then every BLAS in use
     QGrid    scene_grid = { { 0, 0, 0 }, { 1, 1, 1 } };
-    TriRec*  d_pool_tris = nullptr;
-    NrmRec*  d_pool_nrms = nullptr;
+    DevBuf<TriRec>  d_pool_tris;
+    DevBuf<NrmRec>  d_pool_nrms;
     uint32_t n_pool_tris = 0, n_pool_nodes = 0;     // (n_pool_nodes: TLAS nodes, then those of every BLAS in use)
     uint32_t n_insts = 0, tlas_depth = 0;
     bool tlas_built = false;
@@ -127,23 +187,21 @@ struct rr_context {
     // only what changed); TLAS ALLOW_UPDATE builds also keep the links and counters of the top level
     std::vector<uint32_t> pool_node_off, pool_tri_off;
     std::vector<uint64_t> pool_version;
-    int32_t*  d_tlas_links = nullptr;
-    uint32_t* d_tlas_visit = nullptr;
+    DevBuf<int32_t>  d_tlas_links;
+    DevBuf<uint32_t> d_tlas_visit;
     bool tlas_refittable = false;
 
-    float*   d_screen = nullptr;     // GenerateCameraRay's screen coordinates for frames of screen_w x screen_h: sx[W], sy[H]
-    uint32_t screen_w = 0, screen_h = 0;
+    DevBuf<float> d_screen;          // GenerateCameraRay's screen coordinates for frames of screen_w x screen_h: sx[W], sy[H]
+    uint32_t screen_w = 0, screen_h = 0;     // (0: the tables are not valid)
 
     rr_scene_constants cam;
     bool cam_set = false;
-    CamDev* d_cams = nullptr;        // device-side constant buffer(s), one per depth slice
-    size_t cams_cap = 0;
+    DevBuf<CamDev> d_cams;           // device-side constant buffer(s), one per depth slice
     // page-locked staging for the constants (a copy from pageable memory makes the runtime stage it itself, a few hundred
     // microseconds in front of every launch): four slots in turn, each guarded by an event recorded behind its copy
     static constexpr int CAM_SLOTS = 4;
-    void*      h_cams[CAM_SLOTS] = {};
-    size_t     h_cams_cap[CAM_SLOTS] = {};
-    hipEvent_t h_cams_ev[CAM_SLOTS] = {};
+    HostBuf<CamDev> h_cams[CAM_SLOTS];
+    Event      h_cams_ev[CAM_SLOTS];
     bool       h_cams_busy[CAM_SLOTS] = {};
     uint32_t   h_cams_next = 0;
 
@@ -151,32 +209,29 @@ struct rr_context {
 
     // lanes: internal streams whose launches may overlap each other (rr_render_orbit_sharded_lane)
     static constexpr uint32_t MAX_LANES = 4;
-    hipStream_t lane_stream[MAX_LANES] = {};
-    hipEvent_t  lane_fork[MAX_LANES] = {}, lane_done[MAX_LANES] = {};
-    CamDev*     lane_cams[MAX_LANES] = {};
-    size_t      lane_cams_cap[MAX_LANES] = {};
+    Stream      lane_stream[MAX_LANES];
+    Event       lane_fork[MAX_LANES], lane_done[MAX_LANES];
+    DevBuf<CamDev> lane_cams[MAX_LANES];
     bool        lane_busy[MAX_LANES] = {};
     uint32_t    frames_in_flight = 2;    // rr_set_frames_in_flight: launches of rr_render_orbit that may overlap
     size_t      frame_base = 0;          // element offset of the most recent dispatch inside d_rgba8 / d_f32
 
     // frame
     uint32_t W = 0, H = 0, frame_world = 0, frame_depth = 1;
-    uint32_t* d_rgba8 = nullptr;     // world==1: W*H; else local tiles
-    float4*   d_f32 = nullptr;
-    uint32_t* d_assembled = nullptr; // rank-0 raster after rr_assemble_tiles
-    size_t    rgba_elems = 0, f32_elems = 0, assembled_elems = 0;
+    DevBuf<uint32_t> d_rgba8;        // world==1: W*H; else local tiles
+    DevBuf<float4>   d_f32;
+    DevBuf<uint32_t> d_assembled;    // rank-0 raster after rr_assemble_tiles
     bool      have_f32 = false, have_frame = false, have_assembled = false;
     uint64_t  last_pixels = 0;
     uint64_t  accum_pixels = 0;      // pixels of all dispatches since the counters were last zeroed
     bool      last_stats = false;
 
-    CounterBlock* d_cnt = nullptr;
-    CounterBlock* d_cnt_trial = nullptr;     // what the two renders of a kernel-choice measurement count into (thrown away)
-    uint32_t* d_park[MAX_LANES + 1] = {};   // k_render_lds: parked reflected rays, one slab per stream slot like the tickets
-    size_t    park_bytes[MAX_LANES + 1] = {};
+    DevBuf<CounterBlock> d_cnt;
+    DevBuf<CounterBlock> d_cnt_trial;        // what the two renders of a kernel-choice measurement count into (thrown away)
+    DevBuf<uint32_t> d_park[MAX_LANES + 1]; // k_render_lds: parked reflected rays, one slab per stream slot like the tickets
     char       last_kernel_name[96] = "";
     uint32_t   last_kernel = 0;      // render kernel of the last dispatch (rr_choice.h RenderKernel): 0 fused, 1 lds, 2 paths, 7 stream
-    uint32_t* d_tickets = nullptr;   // k_render_lds ticket words: one block per stream a launch can be on (lanes, then the context's stream)
+    DevBuf<uint32_t> d_tickets;      // k_render_lds ticket words: one block per stream a launch can be on (lanes, then the context's stream)
 
     // diagnostics switches, read once at rr_create (never needed for correct results)
     DebugFacts dbg = { 0, 0, false };    // RR_DEBUG_KERNEL / _STACK / _TLAS32 (rr_choice.h): a forced kernel, wherever it can render the launch
@@ -189,24 +244,21 @@ struct rr_context {
     std::string dbg_diag;            // RR_DEBUG_DIAG: file that receives per-wave diagnostics of Depth-1 dispatches
 
     // timing
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> kev;     // pairs
+    Event ev_begin, ev_end;
+    std::vector<Event> kev;          // pairs
     uint32_t kev_used = 0;
 
     // k_stream_* (rr_render_stream.hip): ray queues, leaf slots and pixel marks of one pass; grown on demand, never shrunk.
     // One set per stream a launch can be on (the lanes, then the context's stream: launches on one stream are ordered, launches
     // on different lanes overlap), allocated when that stream first renders with the stream renderer.
-    StreamDev strm[MAX_LANES + 1] = {};
-    size_t    strm_cap[MAX_LANES + 1] = {};          // queue entries allocated (each of the two queues)
-    size_t    strm_pixels[MAX_LANES + 1] = {};       // pixel ordinals the slots / marks are allocated for
+    StreamSet strm[MAX_LANES + 1];
     size_t    strm_budget = 0;                       // bytes one set may take (stream_budget)
     ChoiceClass ch[3];                   // the measured kernel choices (rr_choice.h), by ChoiceClassId
-    hipEvent_t ch_ev[4] = {};
+    Event      ch_ev[4];
 
     // trace_rays scratch
-    rr_ray_dev* d_rays = nullptr;
-    rr_hit_dev* d_hits = nullptr;
-    size_t ray_cap = 0;
+    DevBuf<rr_ray_dev> d_rays;
+    DevBuf<rr_hit_dev> d_hits;
 };
 
 namespace {
@@ -226,17 +278,19 @@ int fail(rr_context* ctx, int code, const char* what, hipError_t e = hipSuccess)
         if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? RR_ERR_OUT_OF_MEMORY : RR_ERR_DEVICE, #call, e_); \
     } while (0)
 
-template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// as RR_HIP, but any failure is RR_ERR_DEVICE and reported as `what`
+#define RR_HIP_MSG(call, what)                                                            \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) return fail(ctx, RR_ERR_DEVICE, what, e_);                  \
+    } while (0)
 
-// regrows device buffer p to n units of `unit` bytes; `have` counts them (0 while p is gone).  Waits for the context's stream
-// first: what is in flight there may still read the old buffer.
-template <class T> int grow(rr_context* ctx, T*& p, size_t& have, size_t n, size_t unit = sizeof(T))
+// reallocates to n elements (size() 0 if that fails).  Waits for the context's stream first: what is in flight there may still
+// read the old buffer.
+template <class T, bool Pinned> int Buf<T, Pinned>::grow(rr_context* ctx, size_t n)
 {
     RR_HIP(hipStreamSynchronize(ctx->stream));
-    dfree(p);
-    have = 0;
-    RR_HIP(hipMalloc(&p, n * unit));
-    have = n;
+    RR_HIP(alloc(n));
     return RR_OK;
 }
 
@@ -268,8 +322,7 @@ float ord2f_host(uint32_t u)
 
 struct BuildScratch {
     BuildBuffers b{};
-    void* raw = nullptr;
-    ~BuildScratch() { if (raw) (void)hipFree(raw); }
+    DevBuf<char> raw;
 };
 
 // one allocation carved into the builder's scratch arrays (16-byte aligned pieces)
@@ -287,8 +340,8 @@ int alloc_build(rr_context* ctx, uint32_t n, BuildScratch& s)
     size_t o_depth = o_scene + al(6 * 4);
     size_t o_ploc = o_depth + al(4);
     size_t total = o_ploc + al((size_t)n * 8);
-    RR_HIP(hipMalloc(&s.raw, total));
-    char* base = (char*)s.raw;
+    RR_HIP(s.raw.alloc(total));
+    char* base = s.raw.get();
     s.b.n = n; s.b.n_pad = n_pad;
     s.b.prim_box = (float*)(base + o_box);
     s.b.keys = (unsigned long long*)(base + o_keys);
@@ -330,28 +383,24 @@ void fill_scene(const rr_context* ctx, SceneDev& sc)
     const MeshRes* m0 = nullptr;
     if (ctx->single_identity) m0 = &ctx->meshes[(size_t)ctx->inst_host[0].blas];
     if (m0) {
-        sc.blas0.nodes = m0->qnodes; sc.blas0.grid = m0->grid; sc.blas0.tris = m0->tris; sc.blas0.nrms = m0->nrms;
+        sc.blas0.nodes = m0->qnodes.get(); sc.blas0.grid = m0->grid; sc.blas0.tris = m0->tris.get(); sc.blas0.nrms = m0->nrms.get();
         sc.blas0.n_tris = m0->n_tris; sc.blas0.depth = m0->depth; sc.blas0.scale = m0->scale;
     }
-    sc.pool_nodes = ctx->d_pool_qnodes; sc.grid = ctx->scene_grid; sc.pool_tris = ctx->d_pool_tris; sc.pool_nrms = ctx->d_pool_nrms;
-    sc.insts = ctx->d_insts;
+    sc.pool_nodes = ctx->d_pool_qnodes.get(); sc.grid = ctx->scene_grid; sc.pool_tris = ctx->d_pool_tris.get(); sc.pool_nrms = ctx->d_pool_nrms.get();
+    sc.insts = ctx->d_insts.get();
     sc.n_insts = ctx->n_insts;
     sc.n_pool_tris = ctx->n_pool_tris;
     sc.single_identity = ctx->single_identity ? 1u : 0u;
     sc.scale = ctx->scene_scale;
-    sc.env = ctx->d_env;
+    sc.env = ctx->d_env.get();
     sc.env_w = ctx->env_w; sc.env_h = ctx->env_h;
 }
 
-// trace_rays scratch for n rays (a failure leaves ray_cap 0: the next call grows both again)
+// trace_rays scratch for n rays
 int ensure_rays(rr_context* ctx, size_t n)
 {
-    if (n <= ctx->ray_cap) return RR_OK;
-    size_t hits = 0;
-    int r = grow(ctx, ctx->d_hits, hits, n);
-    if (r == RR_OK) r = grow(ctx, ctx->d_rays, ctx->ray_cap, n);
-    if (r != RR_OK) ctx->ray_cap = 0;
-    return r;
+    if (n > ctx->d_hits.size()) if (int r = ctx->d_hits.grow(ctx, n)) return r;
+    return n > ctx->d_rays.size() ? ctx->d_rays.grow(ctx, n) : RR_OK;
 }
 
 // InstanceMask of a single-identity scene's instance (the query kernels test it per ray before the walk)
@@ -404,18 +453,14 @@ int rr_create(int device_ordinal, rr_context** out)
     if (!ctx) return RR_ERR_OUT_OF_MEMORY;
     ctx->device = device_ordinal;
     ctx->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (hipSetDevice(device_ordinal) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&ctx->d_cnt, sizeof(CounterBlock)) != hipSuccess ||
-        hipMalloc(&ctx->d_tickets, (rr_context::MAX_LANES + 1) * LDS_TICKET_WORDS * sizeof(uint32_t)) != hipSuccess) {
-        if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-        dfree(ctx->d_cnt);
+    if (hipSetDevice(device_ordinal) != hipSuccess || ctx->own_stream.create(hipStreamNonBlocking) != hipSuccess ||
+        ctx->d_cnt.alloc(1) != hipSuccess || ctx->d_tickets.alloc((rr_context::MAX_LANES + 1) * LDS_TICKET_WORDS) != hipSuccess) {
         delete ctx;
         return RR_ERR_DEVICE;
     }
-    ctx->stream = ctx->own_stream;
-    (void)hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream);
-    (void)hipMemsetAsync(ctx->d_tickets, 0, (rr_context::MAX_LANES + 1) * LDS_TICKET_WORDS * sizeof(uint32_t), ctx->stream);   // the kernel leaves them zero
+    ctx->stream = ctx->own_stream.get();
+    (void)hipMemsetAsync(ctx->d_cnt.get(), 0, sizeof(CounterBlock), ctx->stream);
+    (void)hipMemsetAsync(ctx->d_tickets.get(), 0, (rr_context::MAX_LANES + 1) * LDS_TICKET_WORDS * sizeof(uint32_t), ctx->stream);   // the kernel leaves them zero
     if (const char* e = getenv("RR_DEBUG_KERNEL"))
         ctx->dbg.kernel = !strcmp(e, "fused") ? 1 : !strcmp(e, "lds") ? 4 : !strcmp(e, "paths") ? 5 : !strcmp(e, "stream") ? 10 : 0;
     if (const char* e = getenv("RR_DEBUG_STACK")) ctx->dbg.stack = atoi(e);
@@ -435,27 +480,8 @@ int rr_destroy(rr_context* ctx)
     if (!ctx) return RR_ERR_INVALID_ARGUMENT;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l) {
-        if (!ctx->lane_stream[l]) continue;
-        (void)hipStreamSynchronize(ctx->lane_stream[l]);
-        (void)hipStreamDestroy(ctx->lane_stream[l]);
-        (void)hipEventDestroy(ctx->lane_fork[l]);
-        (void)hipEventDestroy(ctx->lane_done[l]);
-        dfree(ctx->lane_cams[l]);
-    }
-    for (MeshRes& m : ctx->meshes) { dfree(m.d_verts); dfree(m.d_idx); dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms); dfree(m.links); dfree(m.visit); dfree(m.d_upd); }
-    dfree(ctx->d_tlas_links); dfree(ctx->d_tlas_visit);
-    dfree(ctx->d_env); dfree(ctx->d_insts); dfree(ctx->d_pool_nodes); dfree(ctx->d_pool_qnodes); dfree(ctx->d_pool_tris); dfree(ctx->d_pool_nrms); dfree(ctx->d_rgba8); dfree(ctx->d_f32);
-    for (StreamDev& sd : ctx->strm) { dfree(sd.q[0]); dfree(sd.q[1]); dfree(sd.fill[0]); dfree(sd.fill[1]); dfree(sd.heads); dfree(sd.slots); dfree(sd.pending); }
-    for (hipEvent_t e : ctx->ch_ev) if (e) (void)hipEventDestroy(e);
-    dfree(ctx->d_assembled); dfree(ctx->d_cnt); dfree(ctx->d_cnt_trial); dfree(ctx->d_tickets); dfree(ctx->d_screen);
-    for (uint32_t l = 0; l <= rr_context::MAX_LANES; ++l) dfree(ctx->d_park[l]); dfree(ctx->d_rays); dfree(ctx->d_hits); dfree(ctx->d_cams);
-    for (int k = 0; k < rr_context::CAM_SLOTS; ++k) { if (ctx->h_cams[k]) (void)hipHostFree(ctx->h_cams[k]); if (ctx->h_cams_ev[k]) (void)hipEventDestroy(ctx->h_cams_ev[k]); }
-    if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    for (const Stream& s : ctx->lane_stream) if (s.get()) (void)hipStreamSynchronize(s.get());
+    delete ctx;          // (its members release what it holds)
     return RR_OK;
 }
 
@@ -473,7 +499,7 @@ int rr_reset_stream(rr_context* ctx)
 {
     if (int r = use_device(ctx)) return r;
     RR_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->stream = ctx->own_stream;
+    ctx->stream = ctx->own_stream.get();
     return RR_OK;
 }
 
@@ -483,7 +509,7 @@ int join_lanes(rr_context* ctx)
 {
     for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l)
         if (ctx->lane_busy[l]) {
-            RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[l], 0));
+            RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[l].get(), 0));
             ctx->lane_busy[l] = false;
         }
     return RR_OK;
@@ -511,7 +537,7 @@ int rr_lane_join(rr_context* ctx, uint32_t lane)
     if (int r = use_device(ctx)) return r;
     if (lane >= rr_context::MAX_LANES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_lane_join: lane out of range");
     if (ctx->lane_busy[lane]) {
-        RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[lane], 0));
+        RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[lane].get(), 0));
         ctx->lane_busy[lane] = false;
     }
     return RR_OK;
@@ -529,15 +555,13 @@ int rr_upload_mesh(rr_context* ctx, const rr_vertex* verts, uint32_t n_verts, co
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_upload_mesh: non-finite or huge (> 1e18) vertex position");
     MeshRes m;
     m.n_verts = n_verts; m.n_idx = n_indices; m.n_tris = n_indices / 3;
-    RR_HIP(hipMalloc(&m.d_verts, (size_t)n_verts * sizeof(rr_vertex)));
-    hipError_t e = hipMalloc(&m.d_idx, (size_t)n_indices * 4);
-    if (e != hipSuccess) { dfree(m.d_verts); return fail(ctx, RR_ERR_OUT_OF_MEMORY, "hipMalloc(indices)", e); }
+    RR_HIP(m.d_verts.alloc((size_t)n_verts * 8));
+    if (hipError_t e = m.d_idx.alloc(n_indices)) return fail(ctx, RR_ERR_OUT_OF_MEMORY, "hipMalloc(indices)", e);
     // Mesh.cpp:76-79,88-91: memcpy into the mapped upload buffers
-    e = hipMemcpyAsync(m.d_verts, verts, (size_t)n_verts * sizeof(rr_vertex), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(m.d_idx, indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // caller keeps ownership of the host arrays
-    if (e != hipSuccess) { dfree(m.d_verts); dfree(m.d_idx); return fail(ctx, RR_ERR_DEVICE, "mesh upload", e); }
-    ctx->meshes.push_back(m);
+    RR_HIP_MSG(hipMemcpyAsync(m.d_verts.get(), verts, (size_t)n_verts * sizeof(rr_vertex), hipMemcpyHostToDevice, ctx->stream), "mesh upload");
+    RR_HIP_MSG(hipMemcpyAsync(m.d_idx.get(), indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, ctx->stream), "mesh upload");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "mesh upload");   // caller keeps ownership of the host arrays
+    ctx->meshes.push_back(std::move(m));
     *mesh_id = (uint32_t)ctx->meshes.size() - 1u;
     return RR_OK;
 }
@@ -547,17 +571,14 @@ int rr_upload_envmap(rr_context* ctx, const float* rgb, int32_t w, int32_t h)
     if (int r = use_device(ctx)) return r;
     if (!rgb || w <= 0 || h <= 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_upload_envmap: null data or empty size");
     const size_t n = (size_t)w * (size_t)h;
-    float* staging = nullptr;
-    float4* env = nullptr;
-    RR_HIP(hipMalloc(&staging, n * 12));
-    hipError_t e = hipMalloc(&env, n * 16);
-    if (e == hipSuccess) e = hipMemcpyAsync(staging, rgb, n * 12, hipMemcpyHostToDevice, ctx->stream);   // RowPitch = x*3*4 (:128)
-    if (e == hipSuccess) e = launch_env_pad(staging, env, (uint32_t)n, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(staging);
-    if (e != hipSuccess) { if (env) (void)hipFree(env); return fail(ctx, RR_ERR_DEVICE, "env upload", e); }
-    dfree(ctx->d_env);
-    ctx->d_env = env; ctx->env_w = w; ctx->env_h = h;
+    DevBuf<float> staging;
+    DevBuf<float4> env;
+    RR_HIP(staging.alloc(n * 3));
+    RR_HIP_MSG(env.alloc(n), "env upload");
+    RR_HIP_MSG(hipMemcpyAsync(staging.get(), rgb, n * 12, hipMemcpyHostToDevice, ctx->stream), "env upload");   // RowPitch = x*3*4 (:128)
+    RR_HIP_MSG(launch_env_pad(staging.get(), env.get(), (uint32_t)n, ctx->stream), "env upload");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "env upload");
+    ctx->d_env = std::move(env); ctx->env_w = w; ctx->env_h = h;
     return RR_OK;
 }
 
@@ -569,9 +590,9 @@ namespace {
 
 int ensure_upd(rr_context* ctx, MeshRes& m)
 {
-    if (m.d_upd) return RR_OK;
-    RR_HIP(hipMalloc(&m.d_upd, 8 * sizeof(uint32_t)));
-    RR_HIP(hipMemsetAsync(m.d_upd, 0, 8 * sizeof(uint32_t), ctx->stream));
+    if (m.d_upd.get()) return RR_OK;
+    RR_HIP(m.d_upd.alloc(8));
+    RR_HIP(hipMemsetAsync(m.d_upd.get(), 0, 8 * sizeof(uint32_t), ctx->stream));
     return RR_OK;
 }
 
@@ -580,8 +601,8 @@ int take_device_verdict(rr_context* ctx, MeshRes& m)
 {
     if (!m.dev_pending) return RR_OK;
     uint32_t rejected = 0;
-    RR_HIP(hipMemcpyAsync(&rejected, m.d_upd + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipMemsetAsync(m.d_upd + 7, 0, 4, ctx->stream));
+    RR_HIP(hipMemcpyAsync(&rejected, m.d_upd.get() + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemsetAsync(m.d_upd.get() + 7, 0, 4, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     m.dev_pending = false;
     if (rejected)
@@ -606,12 +627,13 @@ int refit_blas(rr_context* ctx, MeshRes& m)
         return fail(ctx, RR_ERR_STATE, "rr_build_blas: PERFORM_UPDATE needs a BLAS built with RR_BUILD_ALLOW_UPDATE");
     const uint32_t n = m.n_tris;
     ctx->tlas_built = false;      // the pooled copies of this BLAS are stale until the TLAS is rebuilt or updated
-    RR_HIP(launch_refit_blas(m.d_verts, m.d_idx, n, m.tris, m.nrms, m.nodes, m.links, m.visit, m.d_upd, ctx->stream));
+    RR_HIP(launch_refit_blas(m.d_verts.get(), m.d_idx.get(), n, m.tris.get(), m.nrms.get(), m.nodes.get(), m.links.get(), m.visit.get(),
+                             m.d_upd.get(), ctx->stream));
     uint32_t sb[6];
-    RR_HIP(hipMemcpyAsync(sb, m.d_upd, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemcpyAsync(sb, m.d_upd.get(), sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     set_bounds(m, sb);
-    RR_HIP(launch_quantize_nodes(m.qnodes, m.nodes, n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
+    RR_HIP(launch_quantize_nodes(m.qnodes.get(), m.nodes.get(), n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
     m.stale = false;
     ++m.version;
     return RR_OK;
@@ -634,36 +656,36 @@ int rr_build_blas_ex(rr_context* ctx, uint32_t mesh_id, uint32_t flags)
     const bool keep = (flags & RR_BUILD_ALLOW_UPDATE) != 0;
     BuildScratch s;
     if (int r = alloc_build(ctx, n, s)) return r;
-    dfree(m.nodes); dfree(m.qnodes); dfree(m.tris); dfree(m.nrms); dfree(m.links); dfree(m.visit);
+    m.nodes.reset(); m.qnodes.reset(); m.tris.reset(); m.nrms.reset(); m.links.reset(); m.visit.reset();
     m.built = false;
     m.allow_update = false;
-    RR_HIP(hipMalloc(&m.nodes, (size_t)(n > 1 ? n - 1 : 1) * sizeof(BvhNode)));
-    RR_HIP(hipMalloc(&m.qnodes, (size_t)(n > 1 ? n - 1 : 1) * sizeof(QNode)));
-    RR_HIP(hipMalloc(&m.tris, (size_t)n * sizeof(TriRec)));
-    RR_HIP(hipMalloc(&m.nrms, (size_t)n * sizeof(NrmRec)));
+    RR_HIP(m.nodes.alloc(n > 1 ? n - 1 : 1));
+    RR_HIP(m.qnodes.alloc(n > 1 ? n - 1 : 1));
+    RR_HIP(m.tris.alloc(n));
+    RR_HIP(m.nrms.alloc(n));
     if (keep) {
         if (int r = ensure_upd(ctx, m)) return r;
         if (n > 1) {
-            RR_HIP(hipMalloc(&m.links, (size_t)(2 * (size_t)n - 1) * sizeof(int32_t)));
-            RR_HIP(hipMalloc(&m.visit, (size_t)(n - 1) * sizeof(uint32_t)));
-            RR_HIP(hipMemsetAsync(m.visit, 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
+            RR_HIP(m.links.alloc(2 * (size_t)n - 1));
+            RR_HIP(m.visit.alloc(n - 1));
+            RR_HIP(hipMemsetAsync(m.visit.get(), 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
         }
     }
-    s.b.nodes = m.nodes;
-    RR_HIP(launch_tri_setup(m.d_verts, m.d_idx, n, s.b, ctx->stream));
+    s.b.nodes = m.nodes.get();
+    RR_HIP(launch_tri_setup(m.d_verts.get(), m.d_idx.get(), n, s.b, ctx->stream));
     if ((flags & RR_BUILD_PREFER_FAST_TRACE) && !(flags & RR_BUILD_PREFER_FAST_BUILD) && n > 1 && n <= PLOC_MAX_PRIMS)
         RR_HIP(launch_ploc(s.b, ctx->stream));          // clustered hierarchy (fewer node visits)
     else
         RR_HIP(launch_lbvh(s.b, ctx->stream));          // Karras radix tree (fastest build, any size)
-    if (keep) RR_HIP(launch_keep_links(s.b, m.links, ctx->stream));
-    RR_HIP(launch_pack_tris(m.d_verts, m.d_idx, s.b, m.tris, m.nrms, ctx->stream));
+    if (keep) RR_HIP(launch_keep_links(s.b, m.links.get(), ctx->stream));
+    RR_HIP(launch_pack_tris(m.d_verts.get(), m.d_idx.get(), s.b, m.tris.get(), m.nrms.get(), ctx->stream));
     uint32_t sb[6], depth = 0;
     RR_HIP(hipMemcpyAsync(sb, s.b.scene_box, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     set_bounds(m, sb);
     m.depth = depth;
-    RR_HIP(launch_quantize_nodes(m.qnodes, m.nodes, n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
+    RR_HIP(launch_quantize_nodes(m.qnodes.get(), m.nodes.get(), n > 1 ? n - 1 : 1, m.grid, 0, 0, ctx->stream));
     if (depth > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_blas: LBVH deeper than the 64-entry traversal stack");
     m.built = true;
     m.allow_update = keep;
@@ -682,7 +704,7 @@ int rr_update_mesh_vertices(rr_context* ctx, uint32_t mesh_id, const rr_vertex* 
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices: need the uploaded vertex count");
     if (rr_host_validate_positions(verts, n_verts, nullptr) != RR_OK)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices: non-finite or huge (> 1e18) vertex position");
-    RR_HIP(hipMemcpyAsync(m.d_verts, verts, (size_t)n_verts * sizeof(rr_vertex), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipMemcpyAsync(m.d_verts.get(), verts, (size_t)n_verts * sizeof(rr_vertex), hipMemcpyHostToDevice, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));   // caller keeps ownership of the host array
     m.stale = true;
     return RR_OK;
@@ -696,7 +718,7 @@ int rr_update_mesh_vertices_device(rr_context* ctx, uint32_t mesh_id, const void
     if (!d_verts || ((uintptr_t)d_verts & 3u) != 0 || n_verts != m.n_verts)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_update_mesh_vertices_device: need a 4-byte aligned pointer and the uploaded vertex count");
     if (int r = ensure_upd(ctx, m)) return r;
-    RR_HIP(launch_update_verts(d_verts, m.d_verts, n_verts, m.d_upd + 6, ctx->stream));
+    RR_HIP(launch_update_verts(d_verts, m.d_verts.get(), n_verts, m.d_upd.get() + 6, ctx->stream));
     m.stale = true;
     m.dev_pending = true;
     return RR_OK;
@@ -756,21 +778,21 @@ void scene_from_root(rr_context* ctx, const BvhNode& root)
 }
 
 // quantize + copy into the pools every BLAS of the scene whose version differs from the pooled one (all of them after a build)
-hipError_t repool(rr_context* ctx)
+// (`what` names the TLAS step in a failure)
+int repool(rr_context* ctx, const char* what)
 {
-    hipError_t e = hipSuccess;
     // (pool_node_off covers the meshes that existed at the TLAS build; later uploads are not in the scene)
-    for (size_t mi = 0; mi < ctx->pool_node_off.size() && e == hipSuccess; ++mi) {
+    for (size_t mi = 0; mi < ctx->pool_node_off.size(); ++mi) {
         if (ctx->pool_node_off[mi] == 0xffffffffu) continue;
         const MeshRes& m = ctx->meshes[mi];
         if (ctx->pool_version[mi] == m.version) continue;
         const uint32_t no = ctx->pool_node_off[mi], to = ctx->pool_tri_off[mi];
-        e = launch_quantize_nodes(ctx->d_pool_qnodes + no, m.nodes, m.n_tris > 1 ? m.n_tris - 1 : 1, m.grid, no, to, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_tris + to, m.tris, (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_pool_nrms + to, m.nrms, (size_t)m.n_tris * sizeof(NrmRec), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) ctx->pool_version[mi] = m.version;
+        RR_HIP_MSG(launch_quantize_nodes(ctx->d_pool_qnodes.get() + no, m.nodes.get(), m.n_tris > 1 ? m.n_tris - 1 : 1, m.grid, no, to, ctx->stream), what);
+        RR_HIP_MSG(hipMemcpyAsync(ctx->d_pool_tris.get() + to, m.tris.get(), (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToDevice, ctx->stream), what);
+        RR_HIP_MSG(hipMemcpyAsync(ctx->d_pool_nrms.get() + to, m.nrms.get(), (size_t)m.n_tris * sizeof(NrmRec), hipMemcpyDeviceToDevice, ctx->stream), what);
+        ctx->pool_version[mi] = m.version;
     }
-    return e;
+    return RR_OK;
 }
 
 // what a successful TLAS build or update leaves in the context
@@ -800,23 +822,20 @@ int refit_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n)
     float scene_scale = 0.0f;
     if (int r = tlas_inputs(ctx, instances, n, ctx->pool_node_off, host, xb, scene_scale)) return r;
     ctx->tlas_built = false;
-    float* d_xb = nullptr;
-    RR_HIP(hipMalloc(&d_xb, xb.size() * 4));
+    DevBuf<float> d_xb;
+    RR_HIP(d_xb.alloc(xb.size()));
     const uint32_t n_tlas = n > 1 ? n - 1 : 1;
     BvhNode root;
-    hipError_t e = hipMemcpyAsync(ctx->d_insts, host.data(), (size_t)n * sizeof(InstDev), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_xb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_refit_tlas(ctx->d_insts, d_xb, n, ctx->d_pool_nodes, ctx->d_tlas_links, ctx->d_tlas_visit, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&root, ctx->d_pool_nodes, sizeof root, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) {
-        scene_from_root(ctx, root);
-        e = launch_quantize_nodes(ctx->d_pool_qnodes, ctx->d_pool_nodes, n_tlas, ctx->scene_grid, 0, 0, ctx->stream);
-    }
-    if (e == hipSuccess) e = repool(ctx);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_xb);
-    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "TLAS update", e);
+    RR_HIP_MSG(hipMemcpyAsync(ctx->d_insts.get(), host.data(), (size_t)n * sizeof(InstDev), hipMemcpyHostToDevice, ctx->stream), "TLAS update");
+    RR_HIP_MSG(hipMemcpyAsync(d_xb.get(), xb.data(), xb.size() * 4, hipMemcpyHostToDevice, ctx->stream), "TLAS update");
+    RR_HIP_MSG(launch_refit_tlas(ctx->d_insts.get(), d_xb.get(), n, ctx->d_pool_nodes.get(), ctx->d_tlas_links.get(), ctx->d_tlas_visit.get(), ctx->stream),
+               "TLAS update");
+    RR_HIP_MSG(hipMemcpyAsync(&root, ctx->d_pool_nodes.get(), sizeof root, hipMemcpyDeviceToHost, ctx->stream), "TLAS update");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "TLAS update");
+    scene_from_root(ctx, root);
+    RR_HIP_MSG(launch_quantize_nodes(ctx->d_pool_qnodes.get(), ctx->d_pool_nodes.get(), n_tlas, ctx->scene_grid, 0, 0, ctx->stream), "TLAS update");
+    if (int r = repool(ctx, "TLAS update")) return r;
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "TLAS update");
     return finish_tlas(ctx, instances, n, host[0], scene_scale);
 }
 
@@ -859,52 +878,44 @@ int rr_build_tlas_ex(rr_context* ctx, const rr_instance_desc* instances, uint32_
     if (int r = tlas_inputs(ctx, instances, n, node_off, host, xb, scene_scale)) return r;
     ctx->tlas_built = false;
     ctx->tlas_refittable = false;
-    dfree(ctx->d_insts); dfree(ctx->d_pool_nodes); dfree(ctx->d_pool_qnodes); dfree(ctx->d_pool_tris); dfree(ctx->d_pool_nrms);
-    dfree(ctx->d_tlas_links); dfree(ctx->d_tlas_visit);
-    RR_HIP(hipMalloc(&ctx->d_insts, (size_t)n * sizeof(InstDev)));
-    RR_HIP(hipMalloc(&ctx->d_pool_nodes, (size_t)n_tlas * sizeof(BvhNode)));
-    RR_HIP(hipMalloc(&ctx->d_pool_qnodes, (size_t)n_pool_nodes * sizeof(QNode)));
-    RR_HIP(hipMalloc(&ctx->d_pool_tris, (size_t)n_pool_tris * sizeof(TriRec)));
-    RR_HIP(hipMalloc(&ctx->d_pool_nrms, (size_t)n_pool_tris * sizeof(NrmRec)));
+    ctx->d_insts.reset(); ctx->d_pool_nodes.reset(); ctx->d_pool_qnodes.reset(); ctx->d_pool_tris.reset(); ctx->d_pool_nrms.reset();
+    ctx->d_tlas_links.reset(); ctx->d_tlas_visit.reset();
+    RR_HIP(ctx->d_insts.alloc(n));
+    RR_HIP(ctx->d_pool_nodes.alloc(n_tlas));
+    RR_HIP(ctx->d_pool_qnodes.alloc(n_pool_nodes));
+    RR_HIP(ctx->d_pool_tris.alloc(n_pool_tris));
+    RR_HIP(ctx->d_pool_nrms.alloc(n_pool_tris));
     if (keep && n > 1) {
-        RR_HIP(hipMalloc(&ctx->d_tlas_links, (size_t)(2 * (size_t)n - 1) * sizeof(int32_t)));
-        RR_HIP(hipMalloc(&ctx->d_tlas_visit, (size_t)(n - 1) * sizeof(uint32_t)));
-        RR_HIP(hipMemsetAsync(ctx->d_tlas_visit, 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
+        RR_HIP(ctx->d_tlas_links.alloc(2 * (size_t)n - 1));
+        RR_HIP(ctx->d_tlas_visit.alloc(n - 1));
+        RR_HIP(hipMemsetAsync(ctx->d_tlas_visit.get(), 0, (size_t)(n - 1) * sizeof(uint32_t), ctx->stream));
     }
     ctx->pool_node_off = node_off;
     ctx->pool_tri_off = tri_off;
     ctx->pool_version.assign(ctx->meshes.size(), ~0ull);     // nothing pooled yet: repool copies every BLAS of the scene
-    float* d_xb = nullptr;
-    RR_HIP(hipMalloc(&d_xb, xb.size() * 4));
+    DevBuf<float> d_xb;
+    RR_HIP(d_xb.alloc(xb.size()));
     BuildScratch s;
-    int rc = alloc_build(ctx, n, s);
-    hipError_t e = hipSuccess;
+    if (int r = alloc_build(ctx, n, s)) return r;
+    s.b.nodes = ctx->d_pool_nodes.get();
+    s.b.leaf_ref_prim = 1;
+    s.b.leaf_base = n_pool_tris;                  // an instance leaf is ~(n_pool_tris + instance index)
+    RR_HIP_MSG(hipMemcpyAsync(ctx->d_insts.get(), host.data(), (size_t)n * sizeof(InstDev), hipMemcpyHostToDevice, ctx->stream), "TLAS build");
+    RR_HIP_MSG(hipMemcpyAsync(d_xb.get(), xb.data(), xb.size() * 4, hipMemcpyHostToDevice, ctx->stream), "TLAS build");
+    RR_HIP_MSG(launch_inst_setup(ctx->d_insts.get(), d_xb.get(), n, s.b, ctx->stream), "TLAS build");
+    // (the top level keeps the Karras hierarchy: the clustered builder, tried on it in round 3, makes the 1 024-instance grid
+    // 5 % slower on both renderers -- on a regular lattice every merged-box area ties)
+    RR_HIP_MSG(launch_lbvh(s.b, ctx->stream), "TLAS build");
+    if (keep) RR_HIP_MSG(launch_keep_links(s.b, ctx->d_tlas_links.get(), ctx->stream), "TLAS build");
     uint32_t depth = 0;
-    if (rc == RR_OK) {
-        s.b.nodes = ctx->d_pool_nodes;
-        s.b.leaf_ref_prim = 1;
-        s.b.leaf_base = n_pool_tris;                  // an instance leaf is ~(n_pool_tris + instance index)
-        e = hipMemcpyAsync(ctx->d_insts, host.data(), (size_t)n * sizeof(InstDev), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_xb, xb.data(), xb.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = launch_inst_setup(ctx->d_insts, d_xb, n, s.b, ctx->stream);
-        // (the top level keeps the Karras hierarchy: the clustered builder, tried on it in round 3, makes the 1 024-instance grid
-        // 5 % slower on both renderers -- on a regular lattice every merged-box area ties)
-        if (e == hipSuccess) e = launch_lbvh(s.b, ctx->stream);
-        if (e == hipSuccess && keep) e = launch_keep_links(s.b, ctx->d_tlas_links, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream);
-        BvhNode root;
-        if (e == hipSuccess) e = hipMemcpyAsync(&root, ctx->d_pool_nodes, sizeof root, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) {
-            scene_from_root(ctx, root);
-            e = launch_quantize_nodes(ctx->d_pool_qnodes, ctx->d_pool_nodes, n_tlas, ctx->scene_grid, 0, 0, ctx->stream);
-        }
-        if (e == hipSuccess) e = repool(ctx);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(d_xb);
-    if (rc != RR_OK) return rc;
-    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "TLAS build", e);
+    BvhNode root;
+    RR_HIP_MSG(hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream), "TLAS build");
+    RR_HIP_MSG(hipMemcpyAsync(&root, ctx->d_pool_nodes.get(), sizeof root, hipMemcpyDeviceToHost, ctx->stream), "TLAS build");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "TLAS build");
+    scene_from_root(ctx, root);
+    RR_HIP_MSG(launch_quantize_nodes(ctx->d_pool_qnodes.get(), ctx->d_pool_nodes.get(), n_tlas, ctx->scene_grid, 0, 0, ctx->stream), "TLAS build");
+    if (int r = repool(ctx, "TLAS build")) return r;
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "TLAS build");
     ctx->n_pool_tris = n_pool_tris; ctx->n_pool_nodes = n_pool_nodes;
     ctx->tlas_depth = depth;
     ctx->tlas_refittable = keep;
@@ -948,25 +959,25 @@ namespace {
 
 int ensure_cams(rr_context* ctx, size_t n)
 {
-    return n <= ctx->cams_cap ? RR_OK : grow(ctx, ctx->d_cams, ctx->cams_cap, n < 64 ? 64 : n);
+    return n <= ctx->d_cams.size() ? RR_OK : ctx->d_cams.grow(ctx, n < 64 ? 64 : n);
 }
 
 // DispatchRays(W, H, depth): slice f uses the constants d_cams[f] and writes to out + f*stride.
 // ext_tiles != null: compact tile output into caller memory with the given stride (sharded frames).
 int ensure_frame_buffers(rr_context* ctx, size_t elems, bool want_f32)
 {
-    if (elems > ctx->rgba_elems || !ctx->d_rgba8)
-        if (int r = grow(ctx, ctx->d_rgba8, ctx->rgba_elems, elems)) return r;
-    if (want_f32 && (elems > ctx->f32_elems || !ctx->d_f32)) return grow(ctx, ctx->d_f32, ctx->f32_elems, elems);
+    if (elems > ctx->d_rgba8.size())
+        if (int r = ctx->d_rgba8.grow(ctx, elems)) return r;
+    if (want_f32 && elems > ctx->d_f32.size()) return ctx->d_f32.grow(ctx, elems);
     return RR_OK;
 }
 
 int ensure_lane(rr_context* ctx, uint32_t lane)
 {
-    if (ctx->lane_stream[lane]) return RR_OK;
-    RR_HIP(hipStreamCreateWithFlags(&ctx->lane_stream[lane], hipStreamNonBlocking));
-    RR_HIP(hipEventCreateWithFlags(&ctx->lane_fork[lane], hipEventDisableTiming));
-    RR_HIP(hipEventCreateWithFlags(&ctx->lane_done[lane], hipEventDisableTiming));
+    if (ctx->lane_stream[lane].get()) return RR_OK;
+    RR_HIP(ctx->lane_stream[lane].create(hipStreamNonBlocking));
+    RR_HIP(ctx->lane_fork[lane].create(hipEventDisableTiming));
+    RR_HIP(ctx->lane_done[lane].create(hipEventDisableTiming));
     return RR_OK;
 }
 
@@ -1020,7 +1031,7 @@ LaunchFacts launch_facts(const rr_context* ctx, uint32_t width, uint32_t height,
 // the buffer set of the stream the dispatch is on (launches on one stream are ordered: one set per stream)
 uint32_t stream_slot(const rr_context* ctx)
 {
-    for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l) if (ctx->lane_stream[l] && ctx->stream == ctx->lane_stream[l]) return l;
+    for (uint32_t l = 0; l < rr_context::MAX_LANES; ++l) if (ctx->lane_stream[l].get() && ctx->stream == ctx->lane_stream[l].get()) return l;
     return rr_context::MAX_LANES;
 }
 
@@ -1057,29 +1068,20 @@ StreamPlan stream_plan(rr_context* ctx, const DispatchDev& a, uint32_t depth)
 int ensure_stream_buffers(rr_context* ctx, const StreamPlan& pl)
 {
     if (pl.cap > 0xffffffffull || pl.pixels > 0xffffffffull) return fail(ctx, RR_ERR_UNSUPPORTED, "stream renderer: pass too large for 32-bit ray indices");
-    const uint32_t slot = stream_slot(ctx);
-    StreamDev& sd = ctx->strm[slot];
-    if (!sd.heads) {      // head counters and, behind them, the chunk ticket counters: one block, zeroed by one memset per pass
-        RR_HIP(hipMalloc(&sd.heads, (STREAM_MAX_GEN + STREAM_MAX_GEN * 8u * 16u) * sizeof(uint32_t)));
-        sd.next = sd.heads + STREAM_MAX_GEN;
-    }
-    if (pl.cap > ctx->strm_cap[slot]) {
+    StreamSet& sd = ctx->strm[stream_slot(ctx)];
+    if (!sd.heads.get())      // head counters and, behind them, the chunk ticket counters: one block, zeroed by one memset per pass
+        RR_HIP(sd.heads.alloc(STREAM_MAX_GEN + STREAM_MAX_GEN * 8u * 16u));
+    if (pl.cap > sd.q[1].size()) {
         RR_HIP(hipStreamSynchronize(ctx->stream));          // (this stream is the set's only user)
-        dfree(sd.q[0]); dfree(sd.q[1]); dfree(sd.fill[0]); dfree(sd.fill[1]);
-        ctx->strm_cap[slot] = 0;
-        for (int k = 0; k < 2; ++k) {
-            RR_HIP(hipMalloc(&sd.q[k], pl.cap * 48u));
-            RR_HIP(hipMalloc(&sd.fill[k], (pl.cap / 64u) * 4u));
-        }
-        ctx->strm_cap[slot] = pl.cap;
+        sd.q[0].reset(); sd.q[1].reset(); sd.fill[0].reset(); sd.fill[1].reset();
+        for (int k = 0; k < 2; ++k) RR_HIP(sd.fill[k].alloc(pl.cap / 64u));
+        for (int k = 0; k < 2; ++k) RR_HIP(sd.q[k].alloc(pl.cap, 48u));
     }
-    if (pl.pixels > ctx->strm_pixels[slot]) {
+    if (pl.pixels > sd.pending.size()) {
         RR_HIP(hipStreamSynchronize(ctx->stream));
-        dfree(sd.slots); dfree(sd.pending);
-        ctx->strm_pixels[slot] = 0;
-        RR_HIP(hipMalloc(&sd.slots, pl.pixels * 64u));
-        RR_HIP(hipMalloc(&sd.pending, pl.pixels));
-        ctx->strm_pixels[slot] = pl.pixels;
+        sd.slots.reset(); sd.pending.reset();
+        RR_HIP(sd.slots.alloc(pl.pixels, 64u));
+        RR_HIP(sd.pending.alloc(pl.pixels));
     }
     return RR_OK;
 }
@@ -1089,6 +1091,9 @@ int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uin
 {
     const StreamPlan pl = stream_plan(ctx, a, depth);
     if (int r = ensure_stream_buffers(ctx, pl)) return r;
+    const StreamSet& set = ctx->strm[stream_slot(ctx)];
+    StreamDev s = { { set.q[0].get(), set.q[1].get() }, { set.fill[0].get(), set.fill[1].get() }, set.heads.get(), set.heads.get() + STREAM_MAX_GEN,
+                    set.slots.get(), set.pending.get(), (uint32_t)set.q[1].size(), 0u };
     for (uint32_t f0 = 0; f0 < depth; f0 += pl.fc) {
         const uint32_t fc = std::min(pl.fc, depth - f0);
         DispatchDev b = a;
@@ -1100,8 +1105,6 @@ int render_stream(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, uin
         b.n_blocks = a.blocks_per_frame * fc;
         b.out_rgba8 = a.out_rgba8 + (size_t)f0 * a.frame_stride;
         if (a.out_f32) b.out_f32 = a.out_f32 + (size_t)f0 * a.frame_stride;
-        StreamDev s = ctx->strm[stream_slot(ctx)];
-        s.cap = (uint32_t)ctx->strm_cap[stream_slot(ctx)];
         s.n_rect_wb = (uint32_t)stream_rect_wb(a, fc);
         RR_HIP(launch_render_stream(sc, b, s, need, pl.n_wg, stats, ctx->stream));
     }
@@ -1156,10 +1159,9 @@ int layout_dispatch(rr_context* ctx, uint32_t width, uint32_t height, uint32_t d
         if (int r = ensure_frame_buffers(ctx, o.out_base + o.slice_elems * depth, o.want_f32)) return r;
     if (width != ctx->screen_w || height != ctx->screen_h) {     // new frame size: new tables (nothing in flight may still read the old ones)
         RR_HIP(hipDeviceSynchronize());
-        dfree(ctx->d_screen);
         ctx->screen_w = ctx->screen_h = 0;
-        RR_HIP(hipMalloc(&ctx->d_screen, ((size_t)width + height) * sizeof(float)));
-        RR_HIP(launch_screen_tables(ctx->d_screen, width, height, ctx->stream));
+        RR_HIP(ctx->d_screen.alloc((size_t)width + height));
+        RR_HIP(launch_screen_tables(ctx->d_screen.get(), width, height, ctx->stream));
         RR_HIP(hipStreamSynchronize(ctx->stream));
         ctx->screen_w = width; ctx->screen_h = height;
     }
@@ -1181,7 +1183,7 @@ DispatchDev make_dispatch(const rr_context* ctx, uint32_t width, uint32_t height
 {
     DispatchDev a;
     memset(&a, 0, sizeof a);
-    a.sx = ctx->d_screen; a.sy = ctx->d_screen + width;
+    a.sx = ctx->d_screen.get(); a.sy = ctx->d_screen.get() + width;
     a.async_leaf_num = ctx->dbg_async[0]; a.async_shade_num = ctx->dbg_async[1];
     a.group_trace = ctx->dbg_group_trace ? 1u : 0u;
     uint32_t hr[4];     // where the scene can be seen at all in these slices
@@ -1209,9 +1211,9 @@ DispatchDev make_dispatch(const rr_context* ctx, uint32_t width, uint32_t height
     a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
     a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
     a.tmin_p = p.tmin_primary; a.tmax_p = p.tmax_primary; a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
-    a.out_rgba8 = ext_tiles ? ext_tiles : ctx->d_rgba8 + o.out_base;
-    a.out_f32 = o.want_f32 ? ctx->d_f32 + o.out_base : nullptr;
-    a.counters = ctx->d_cnt->counters; a.ray_shards = ctx->d_cnt->shards; a.error_flag = &ctx->d_cnt->error;
+    a.out_rgba8 = ext_tiles ? ext_tiles : ctx->d_rgba8.get() + o.out_base;
+    a.out_f32 = o.want_f32 ? ctx->d_f32.get() + o.out_base : nullptr;
+    a.counters = ctx->d_cnt.get()->counters; a.ray_shards = ctx->d_cnt.get()->shards; a.error_flag = &ctx->d_cnt.get()->error;
     return a;
 }
 
@@ -1227,8 +1229,8 @@ struct Launch {
 // k_render_lds parks reflected rays in a slab per stream slot (allocated at first use: outside anything that is timed)
 int ensure_lds_park(rr_context* ctx, uint32_t slot, int max_reflect)
 {
-    const size_t park_need = (size_t)ctx->n_cus * 32 * (max_reflect <= 2 ? 2u : 8u) * 8 * 64 * sizeof(uint32_t);     // at most 32 waves per CU
-    return ctx->park_bytes[slot] < park_need ? grow(ctx, ctx->d_park[slot], ctx->park_bytes[slot], park_need, 1) : RR_OK;
+    const size_t park_need = (size_t)ctx->n_cus * 32 * (max_reflect <= 2 ? 2u : 8u) * 8 * 64;     // words: at most 32 waves per CU
+    return ctx->d_park[slot].size() < park_need ? ctx->d_park[slot].grow(ctx, park_need) : RR_OK;
 }
 
 // k_render_lds: the reference's scene with a node array small enough for LDS (its own meshes up to shell.obj): persistent
@@ -1239,10 +1241,10 @@ int launch_lds(rr_context* ctx, const Launch& L, bool stats)
     LdsDispatch q;
     memset(&q, 0, sizeof q);
     const uint32_t slot = stream_slot(ctx);
-    q.tickets = ctx->d_tickets + (size_t)slot * LDS_TICKET_WORDS;
+    q.tickets = ctx->d_tickets.get() + (size_t)slot * LDS_TICKET_WORDS;
     q.park_slots = L.p->max_reflect <= 2 ? 2u : 8u;
     if (int r = ensure_lds_park(ctx, slot, L.p->max_reflect)) return r;
-    q.park = ctx->d_park[slot];
+    q.park = ctx->d_park[slot].get();
     uint32_t rect[4];
     (void)rr_host_screen_rect(m0.bounds, ((ctx->dbg_ticket_blocks & 3) == 1 || (L.p->flags & RR_DISPATCH_DEBUG_NO_CULL)) ? nullptr : L.h_cams, L.a.n_frames,
                      L.a.W, L.a.H, rect);
@@ -1275,20 +1277,20 @@ int time_candidates(rr_context* ctx, Launch L, int cand_a, int cand_b, float ms[
 {
     if (cand_b == K_STREAM) if (int r = ensure_stream_buffers(ctx, stream_plan(ctx, L.a, L.a.n_frames))) return r;
     if (cand_a == K_LDS || cand_b == K_LDS) if (int r = ensure_lds_park(ctx, stream_slot(ctx), L.p->max_reflect)) return r;
-    for (hipEvent_t& e : ctx->ch_ev) if (!e) RR_HIP(hipEventCreate(&e));
-    if (!ctx->d_cnt_trial) RR_HIP(hipMalloc(&ctx->d_cnt_trial, sizeof(CounterBlock)));
+    for (Event& e : ctx->ch_ev) if (!e.get()) RR_HIP(e.create(hipEventDefault));
+    if (!ctx->d_cnt_trial.get()) RR_HIP(ctx->d_cnt_trial.alloc(1));
     RR_HIP(hipDeviceSynchronize());
-    RR_HIP(hipMemsetAsync(ctx->d_cnt_trial, 0, sizeof(CounterBlock), ctx->stream));
-    L.a.counters = ctx->d_cnt_trial->counters; L.a.ray_shards = ctx->d_cnt_trial->shards; L.a.error_flag = &ctx->d_cnt_trial->error;
+    RR_HIP(hipMemsetAsync(ctx->d_cnt_trial.get(), 0, sizeof(CounterBlock), ctx->stream));
+    L.a.counters = ctx->d_cnt_trial.get()->counters; L.a.ray_shards = ctx->d_cnt_trial.get()->shards; L.a.error_flag = &ctx->d_cnt_trial.get()->error;
     if (int r = launch_kernel(ctx, L, cand_a, false)) return r;
     for (int c = 0; c < 2; ++c) {
-        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c], ctx->stream));
+        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c].get(), ctx->stream));
         if (int r = launch_kernel(ctx, L, c == 0 ? cand_a : cand_b, false)) return r;
-        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c + 1], ctx->stream));
+        RR_HIP(hipEventRecord(ctx->ch_ev[2 * c + 1].get(), ctx->stream));
     }
-    RR_HIP(hipEventSynchronize(ctx->ch_ev[3]));
-    RR_HIP(hipEventElapsedTime(&ms[0], ctx->ch_ev[0], ctx->ch_ev[1]));
-    RR_HIP(hipEventElapsedTime(&ms[1], ctx->ch_ev[2], ctx->ch_ev[3]));
+    RR_HIP(hipEventSynchronize(ctx->ch_ev[3].get()));
+    RR_HIP(hipEventElapsedTime(&ms[0], ctx->ch_ev[0].get(), ctx->ch_ev[1].get()));
+    RR_HIP(hipEventElapsedTime(&ms[1], ctx->ch_ev[2].get(), ctx->ch_ev[3].get()));
     return RR_OK;
 }
 
@@ -1323,12 +1325,12 @@ int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t dep
     L.a = make_dispatch(ctx, width, height, depth, d_cams, h_cams, p, ext_tiles, mesh, o);
     L.need = scene_stack_need(ctx); L.h_cams = h_cams; L.p = &p;
 
-    unsigned long long* d_diag = nullptr;       // RR_DEBUG_DIAG: per-wave records of the launch
+    DevBuf<unsigned long long> d_diag;          // RR_DEBUG_DIAG: per-wave records of the launch
     const size_t diag_waves = std::max<size_t>(((size_t)L.a.n_blocks + (size_t)((L.a.hx1 - L.a.hx0) / 8u + 1u) * ((L.a.hy1 - L.a.hy0) / 8u + 1u) * depth) * 4 * 2, (size_t)ctx->n_cus * 32);
     if (!ctx->dbg_diag.empty() && ctx->single_identity) {
-        RR_HIP(hipMalloc(&d_diag, diag_waves * 64));
-        RR_HIP(hipMemsetAsync(d_diag, 0, diag_waves * 64, ctx->stream));
-        L.a.diag = d_diag;
+        RR_HIP(d_diag.alloc(diag_waves * 8));
+        RR_HIP(hipMemsetAsync(d_diag.get(), 0, diag_waves * 64, ctx->stream));
+        L.a.diag = d_diag.get();
     }
     const uint32_t filled = mesh ? o.n_mesh_local : o.local;       // slots of the (gathered) tile buffer this rank writes
     const size_t tile_bytes = (size_t)TILE * TILE * (o.rgb8 ? 3 : 4);
@@ -1345,20 +1347,19 @@ int dispatch_impl(rr_context* ctx, uint32_t width, uint32_t height, uint32_t dep
 
     const bool stats = (p.flags & RR_DISPATCH_COLLECT_STATS) != 0;
     const bool keep = keep_counters || (p.flags & RR_DISPATCH_KEEP_COUNTERS) != 0;
-    if (!keep) RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
+    if (!keep) RR_HIP(hipMemsetAsync(ctx->d_cnt.get(), 0, sizeof(CounterBlock), ctx->stream));
     const bool timed = (p.flags & RR_DISPATCH_TIME_KERNEL) != 0;      // between a pair of rr_kernel_time events
     if (timed) {
         if (ctx->kev_used >= 4096) return fail(ctx, RR_ERR_STATE, "dispatch: 4096 timed dispatches pending, call rr_kernel_time");
-        for (hipEvent_t e; ctx->kev.size() < (size_t)(ctx->kev_used + 1) * 2; ctx->kev.push_back(e)) RR_HIP(hipEventCreate(&e));
-        RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2], ctx->stream));
+        for (Event e; ctx->kev.size() < (size_t)(ctx->kev_used + 1) * 2; ctx->kev.push_back(std::move(e))) RR_HIP(e.create(hipEventDefault));
+        RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2].get(), ctx->stream));
     }
     if (int r = launch_kernel(ctx, L, kernel, stats)) return r;
-    if (timed) { RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2 + 1], ctx->stream)); ++ctx->kev_used; }
-    if (d_diag) {       // experiments only: dump per-wave {start, cycles, max rays per lane, loop trips}
+    if (timed) { RR_HIP(hipEventRecord(ctx->kev[(size_t)ctx->kev_used * 2 + 1].get(), ctx->stream)); ++ctx->kev_used; }
+    if (d_diag.get()) {       // experiments only: dump per-wave {start, cycles, max rays per lane, loop trips}
         std::vector<unsigned long long> h(diag_waves * 8);
         RR_HIP(hipStreamSynchronize(ctx->stream));
-        RR_HIP(hipMemcpy(h.data(), d_diag, h.size() * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_diag);
+        RR_HIP(hipMemcpy(h.data(), d_diag.get(), h.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* f = fopen(ctx->dbg_diag.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
     }
 
@@ -1378,18 +1379,12 @@ int upload_cams(rr_context* ctx, const rr_scene_constants* c, size_t n)
     static_assert(sizeof(CamDev) == sizeof(rr_scene_constants), "constant buffer layout");
     if (int r = ensure_cams(ctx, n)) return r;
     const int slot = (int)(ctx->h_cams_next++ % rr_context::CAM_SLOTS);
-    if (ctx->h_cams_busy[slot]) { RR_HIP(hipEventSynchronize(ctx->h_cams_ev[slot])); ctx->h_cams_busy[slot] = false; }
-    if (ctx->h_cams_cap[slot] < n) {
-        if (ctx->h_cams[slot]) (void)hipHostFree(ctx->h_cams[slot]);
-        ctx->h_cams[slot] = nullptr; ctx->h_cams_cap[slot] = 0;
-        const size_t cap = n < 64 ? 64 : n;
-        RR_HIP(hipHostMalloc(&ctx->h_cams[slot], cap * sizeof(CamDev), hipHostMallocDefault));
-        ctx->h_cams_cap[slot] = cap;
-    }
-    if (!ctx->h_cams_ev[slot]) RR_HIP(hipEventCreateWithFlags(&ctx->h_cams_ev[slot], hipEventDisableTiming));
-    memcpy(ctx->h_cams[slot], c, n * sizeof(CamDev));
-    RR_HIP(hipMemcpyAsync(ctx->d_cams, ctx->h_cams[slot], n * sizeof(CamDev), hipMemcpyHostToDevice, ctx->stream));   // copy_to_buffer, :566
-    RR_HIP(hipEventRecord(ctx->h_cams_ev[slot], ctx->stream));
+    if (ctx->h_cams_busy[slot]) { RR_HIP(hipEventSynchronize(ctx->h_cams_ev[slot].get())); ctx->h_cams_busy[slot] = false; }
+    if (ctx->h_cams[slot].size() < n) RR_HIP(ctx->h_cams[slot].alloc(n < 64 ? 64 : n));
+    if (!ctx->h_cams_ev[slot].get()) RR_HIP(ctx->h_cams_ev[slot].create(hipEventDisableTiming));
+    memcpy(ctx->h_cams[slot].get(), c, n * sizeof(CamDev));
+    RR_HIP(hipMemcpyAsync(ctx->d_cams.get(), ctx->h_cams[slot].get(), n * sizeof(CamDev), hipMemcpyHostToDevice, ctx->stream));   // copy_to_buffer, :566
+    RR_HIP(hipEventRecord(ctx->h_cams_ev[slot].get(), ctx->stream));
     ctx->h_cams_busy[slot] = true;
     return RR_OK;
 }
@@ -1405,7 +1400,7 @@ int check_error_flag(rr_context* ctx, const char* what)
 {
     RR_HIP(hipStreamSynchronize(ctx->stream));
     uint32_t err = 0;
-    RR_HIP(hipMemcpy(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost));
+    RR_HIP(hipMemcpy(&err, &ctx->d_cnt.get()->error, 4, hipMemcpyDeviceToHost));
     return err ? fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, what) : RR_OK;
 }
 
@@ -1423,7 +1418,7 @@ int orbit_cams(rr_context* ctx, const char* what, float& angle, float angle_step
 int zero_counters_before_fork(rr_context* ctx, rr_dispatch_params& p)
 {
     if (p.flags & RR_DISPATCH_KEEP_COUNTERS) return RR_OK;
-    RR_HIP(hipMemsetAsync(ctx->d_cnt, 0, sizeof(CounterBlock), ctx->stream));
+    RR_HIP(hipMemsetAsync(ctx->d_cnt.get(), 0, sizeof(CounterBlock), ctx->stream));
     ctx->accum_pixels = 0; p.flags |= RR_DISPATCH_KEEP_COUNTERS;
     return RR_OK;
 }
@@ -1431,8 +1426,8 @@ int zero_counters_before_fork(rr_context* ctx, rr_dispatch_params& p)
 // the lane starts after everything submitted to the context's stream so far
 int fork_lane(rr_context* ctx, uint32_t lane)
 {
-    RR_HIP(hipEventRecord(ctx->lane_fork[lane], ctx->stream));
-    RR_HIP(hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork[lane], 0));
+    RR_HIP(hipEventRecord(ctx->lane_fork[lane].get(), ctx->stream));
+    RR_HIP(hipStreamWaitEvent(ctx->lane_stream[lane].get(), ctx->lane_fork[lane].get(), 0));
     return RR_OK;
 }
 
@@ -1441,22 +1436,17 @@ int fork_lane(rr_context* ctx, uint32_t lane)
 struct LaneScope {
     rr_context* const ctx;
     const uint32_t lane;
-    const hipStream_t stream; CamDev* const cams; const size_t cams_cap; const uint32_t in_flight;
-    LaneScope(rr_context* c, uint32_t l)
-        : ctx(c), lane(l), stream(c->stream), cams(c->d_cams), cams_cap(c->cams_cap), in_flight(c->frames_in_flight)
+    const hipStream_t stream; const uint32_t in_flight;
+    LaneScope(rr_context* c, uint32_t l) : ctx(c), lane(l), stream(c->stream), in_flight(c->frames_in_flight)
     {
-        ctx->stream = ctx->lane_stream[lane]; ctx->d_cams = ctx->lane_cams[lane]; ctx->cams_cap = ctx->lane_cams_cap[lane];
+        ctx->stream = ctx->lane_stream[lane].get(); std::swap(ctx->d_cams, ctx->lane_cams[lane]);
         ctx->frames_in_flight = 1;
     }
-    ~LaneScope()
-    {
-        ctx->lane_cams[lane] = ctx->d_cams; ctx->lane_cams_cap[lane] = ctx->cams_cap;
-        ctx->stream = stream; ctx->d_cams = cams; ctx->cams_cap = cams_cap; ctx->frames_in_flight = in_flight;
-    }
+    ~LaneScope() { std::swap(ctx->d_cams, ctx->lane_cams[lane]); ctx->stream = stream; ctx->frames_in_flight = in_flight; }
     int done(int rc, const char* what)      // the lane's end, behind what `rc` reports on
     {
         if (rc != RR_OK) return rc;
-        if (hipError_t e = hipEventRecord(ctx->lane_done[lane], ctx->stream)) return fail(ctx, RR_ERR_DEVICE, what, e);
+        if (hipError_t e = hipEventRecord(ctx->lane_done[lane].get(), ctx->stream)) return fail(ctx, RR_ERR_DEVICE, what, e);
         ctx->lane_busy[lane] = true;
         return RR_OK;
     }
@@ -1471,7 +1461,7 @@ int rr_dispatch_rays(rr_context* ctx, uint32_t width, uint32_t height, const rr_
     if (!ctx->cam_set) return fail(ctx, RR_ERR_STATE, "rr_dispatch_rays: rr_set_camera first");
     rr_dispatch_params p = params_or_default(params);
     if (int r = upload_cams(ctx, &ctx->cam, 1)) return r;
-    return dispatch_impl(ctx, width, height, 1, ctx->d_cams, &ctx->cam, p, nullptr, 0, false);
+    return dispatch_impl(ctx, width, height, 1, ctx->d_cams.get(), &ctx->cam, p, nullptr, 0, false);
 }
 
 int rr_dispatch_rays_batch(rr_context* ctx, uint32_t width, uint32_t height, uint32_t depth,
@@ -1481,7 +1471,7 @@ int rr_dispatch_rays_batch(rr_context* ctx, uint32_t width, uint32_t height, uin
     if (!constants || depth == 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_dispatch_rays_batch: need depth >= 1 constants");
     rr_dispatch_params p = params_or_default(params);
     if (int r = upload_cams(ctx, constants, depth)) return r;
-    return dispatch_impl(ctx, width, height, depth, ctx->d_cams, constants, p, nullptr, 0, false);
+    return dispatch_impl(ctx, width, height, depth, ctx->d_cams.get(), constants, p, nullptr, 0, false);
 }
 
 int rr_read_frame_slice(rr_context* ctx, uint32_t slice, uint8_t* rgba8, float* rgba32f)
@@ -1491,13 +1481,13 @@ int rr_read_frame_slice(rr_context* ctx, uint32_t slice, uint8_t* rgba8, float* 
     const size_t n = (size_t)ctx->W * ctx->H;
     if (ctx->have_assembled) {
         if (rgba32f || slice) return fail(ctx, RR_ERR_STATE, "rr_read_frame: only slice 0 / RGBA8 of an assembled frame");
-        if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_assembled, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_assembled.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
     } else {
         if (ctx->frame_world != 1) return fail(ctx, RR_ERR_STATE, "rr_read_frame: sharded frame, gather + rr_assemble_tiles first");
         if (slice >= ctx->frame_depth) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_read_frame: slice beyond the dispatch depth");
         if (rgba32f && !ctx->have_f32) return fail(ctx, RR_ERR_STATE, "rr_read_frame: dispatch with RR_DISPATCH_FLOAT_OUTPUT");
-        if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_rgba8 + ctx->frame_base + slice * n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_f32 + ctx->frame_base + slice * n, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_rgba8.get() + ctx->frame_base + slice * n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_f32.get() + ctx->frame_base + slice * n, n * 16, hipMemcpyDeviceToHost, ctx->stream));
     }
     return check_error_flag(ctx, "traversal stack overflow: frame invalid");
 }
@@ -1510,7 +1500,7 @@ int rr_export_tiles(rr_context* ctx, void* d_dst)
     if (!d_dst) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_export_tiles: null destination");
     if (!ctx->have_frame || ctx->frame_world < 2) return fail(ctx, RR_ERR_STATE, "rr_export_tiles: no sharded frame");
     const Tiles t = tile_counts(ctx->W, ctx->H, ctx->tile_rank, ctx->frame_world);
-    RR_HIP(hipMemcpyAsync(d_dst, ctx->d_rgba8 + ctx->frame_base, (size_t)t.max_local * TILE * TILE * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RR_HIP(hipMemcpyAsync(d_dst, ctx->d_rgba8.get() + ctx->frame_base, (size_t)t.max_local * TILE * TILE * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return RR_OK;
 }
 
@@ -1523,9 +1513,9 @@ int rr_assemble_tiles(rr_context* ctx, const void* d_gathered, uint32_t world, v
     uint32_t* dst = (uint32_t*)d_frame;
     if (!dst) {
         const size_t n = (size_t)ctx->W * ctx->H;
-        if (n > ctx->assembled_elems)
-            if (int r = grow(ctx, ctx->d_assembled, ctx->assembled_elems, n)) return r;
-        dst = ctx->d_assembled;
+        if (n > ctx->d_assembled.size())
+            if (int r = ctx->d_assembled.grow(ctx, n)) return r;
+        dst = ctx->d_assembled.get();
     }
     RR_HIP(launch_assemble_tiles((const uint32_t*)d_gathered, dst, ctx->W, ctx->H, t.tiles_x, t.n_tiles, world, t.max_local, ctx->stream));
     if (!d_frame) ctx->have_assembled = true;
@@ -1578,7 +1568,7 @@ int orbit_impl(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispat
         for (uint32_t k = 0; k < n_frames; k += batch) {
             const uint32_t d = n_frames - k < batch ? n_frames - k : batch;
             uint32_t* ext = ext_tiles ? ext_tiles + (size_t)k * ext_stride_elems : nullptr;
-            if (int rc = dispatch_impl(ctx, width, height, d, ctx->d_cams + k, cams.data() + k, p, ext, ext_stride_elems, k > 0 || keep_first)) return rc;
+            if (int rc = dispatch_impl(ctx, width, height, d, ctx->d_cams.get() + k, cams.data() + k, p, ext, ext_stride_elems, k > 0 || keep_first)) return rc;
         }
         return RR_OK;
     }
@@ -1591,32 +1581,32 @@ int orbit_impl(rr_context* ctx, uint32_t width, uint32_t height, const rr_dispat
     if (int r = zero_counters_before_fork(ctx, p)) return r;
     for (uint32_t l = 0; l < lanes; ++l) {
         if (int r = ensure_lane(ctx, l)) return r;
-        if (ctx->lane_busy[l]) { RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[l], 0)); ctx->lane_busy[l] = false; }
+        if (ctx->lane_busy[l]) { RR_HIP(hipStreamWaitEvent(ctx->stream, ctx->lane_done[l].get(), 0)); ctx->lane_busy[l] = false; }
     }
-    RR_HIP(hipEventRecord(ctx->lane_fork[0], ctx->stream));          // after the constants upload and the counter reset
-    for (uint32_t l = 0; l < lanes; ++l) RR_HIP(hipStreamWaitEvent(ctx->lane_stream[l], ctx->lane_fork[0], 0));
+    RR_HIP(hipEventRecord(ctx->lane_fork[0].get(), ctx->stream));          // after the constants upload and the counter reset
+    for (uint32_t l = 0; l < lanes; ++l) RR_HIP(hipStreamWaitEvent(ctx->lane_stream[l].get(), ctx->lane_fork[0].get(), 0));
     hipStream_t main_stream = ctx->stream;
     int rc = RR_OK;
     for (uint32_t k = 0, b = 0; k < n_frames && rc == RR_OK; k += batch, ++b) {
         const uint32_t d = n_frames - k < batch ? n_frames - k : batch;
         uint32_t* ext = ext_tiles ? ext_tiles + (size_t)k * ext_stride_elems : nullptr;
-        ctx->stream = ctx->lane_stream[b % lanes];
+        ctx->stream = ctx->lane_stream[b % lanes].get();
         // (streaming to host keeps two regions for the copies' sake; the persistent kernel's launches still go one after the other)
-        if (one_kernel_at_a_time && b > 0 && hipStreamWaitEvent(ctx->stream, ctx->lane_fork[(b - 1) % lanes], 0) != hipSuccess)
+        if (one_kernel_at_a_time && b > 0 && hipStreamWaitEvent(ctx->stream, ctx->lane_fork[(b - 1) % lanes].get(), 0) != hipSuccess)
             rc = fail(ctx, RR_ERR_DEVICE, "render_orbit: lane order");
-        if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, d, ctx->d_cams + k, cams.data() + k, p, ext, ext_stride_elems, true, b % lanes, batch);
-        if (rc == RR_OK && one_kernel_at_a_time && hipEventRecord(ctx->lane_fork[b % lanes], ctx->stream) != hipSuccess)
+        if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, d, ctx->d_cams.get() + k, cams.data() + k, p, ext, ext_stride_elems, true, b % lanes, batch);
+        if (rc == RR_OK && one_kernel_at_a_time && hipEventRecord(ctx->lane_fork[b % lanes].get(), ctx->stream) != hipSuccess)
             rc = fail(ctx, RR_ERR_DEVICE, "render_orbit: lane order");
         if (rc == RR_OK && host_out) {      // same lane: the region is not rendered into again before this copy is done
             const size_t fb = (size_t)width * height * 4;
-            hipError_t e = hipMemcpyAsync(host_out + (size_t)k * fb, ctx->d_rgba8 + ctx->frame_base, (size_t)d * fb, hipMemcpyDeviceToHost, ctx->stream);
+            hipError_t e = hipMemcpyAsync(host_out + (size_t)k * fb, ctx->d_rgba8.get() + ctx->frame_base, (size_t)d * fb, hipMemcpyDeviceToHost, ctx->stream);
             if (e != hipSuccess) rc = fail(ctx, RR_ERR_DEVICE, "render_orbit_to_host: copy", e);
         }
         ctx->stream = main_stream;
     }
     for (uint32_t l = 0; l < lanes; ++l) {                          // join: the caller's stream is ordered after every lane
-        hipError_t e = hipEventRecord(ctx->lane_done[l], ctx->lane_stream[l]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lane_done[l], 0);
+        hipError_t e = hipEventRecord(ctx->lane_done[l].get(), ctx->lane_stream[l].get());
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lane_done[l].get(), 0);
         if (e != hipSuccess && rc == RR_OK) rc = fail(ctx, RR_ERR_DEVICE, "render_orbit: lane join", e);
     }
     return rc;
@@ -1712,7 +1702,7 @@ int rr_render_orbit_mesh_sharded_lane(rr_context* ctx, uint32_t width, uint32_t 
     LaneScope scope(ctx, lane);
     int rc = upload_cams(ctx, cams.data(), n_frames);
     const MeshOut mo = { &part, (uint32_t*)d_bg_tiles, (size_t)(bg_stride_bytes / 4) };
-    if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, n_frames, ctx->d_cams, cams.data(), p, (uint32_t*)d_mesh_tiles, (size_t)(mesh_stride_bytes / 4), true, 0, 0, &mo);
+    if (rc == RR_OK) rc = dispatch_impl(ctx, width, height, n_frames, ctx->d_cams.get(), cams.data(), p, (uint32_t*)d_mesh_tiles, (size_t)(mesh_stride_bytes / 4), true, 0, 0, &mo);
     return scope.done(rc, "rr_render_orbit_mesh_sharded_lane: event");
 }
 
@@ -1881,18 +1871,18 @@ int rr_device_read(rr_context* ctx, const void* d_src, void* host_dst, uint64_t 
 int rr_timing_begin(rr_context* ctx)
 {
     if (int r = use_device(ctx)) return r;
-    if (!ctx->ev_begin) { RR_HIP(hipEventCreate(&ctx->ev_begin)); RR_HIP(hipEventCreate(&ctx->ev_end)); }
-    RR_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
+    if (!ctx->ev_end.get()) { RR_HIP(ctx->ev_begin.create(hipEventDefault)); RR_HIP(ctx->ev_end.create(hipEventDefault)); }
+    RR_HIP(hipEventRecord(ctx->ev_begin.get(), ctx->stream));
     return RR_OK;
 }
 
 int rr_timing_end(rr_context* ctx, float* elapsed_ms)
 {
     if (int r = use_device(ctx)) return r;
-    if (!elapsed_ms || !ctx->ev_begin) return fail(ctx, RR_ERR_STATE, "rr_timing_end: rr_timing_begin first");
-    RR_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
-    RR_HIP(hipEventSynchronize(ctx->ev_end));
-    RR_HIP(hipEventElapsedTime(elapsed_ms, ctx->ev_begin, ctx->ev_end));
+    if (!elapsed_ms || !ctx->ev_end.get()) return fail(ctx, RR_ERR_STATE, "rr_timing_end: rr_timing_begin first");
+    RR_HIP(hipEventRecord(ctx->ev_end.get(), ctx->stream));
+    RR_HIP(hipEventSynchronize(ctx->ev_end.get()));
+    RR_HIP(hipEventElapsedTime(elapsed_ms, ctx->ev_begin.get(), ctx->ev_end.get()));
     return RR_OK;
 }
 
@@ -1904,7 +1894,7 @@ int rr_kernel_time(rr_context* ctx, float* sum_ms, uint32_t* n_launches)
     double sum = 0.0;
     for (uint32_t i = 0; i < ctx->kev_used; ++i) {
         float ms = 0.0f;
-        RR_HIP(hipEventElapsedTime(&ms, ctx->kev[(size_t)i * 2], ctx->kev[(size_t)i * 2 + 1]));
+        RR_HIP(hipEventElapsedTime(&ms, ctx->kev[(size_t)i * 2].get(), ctx->kev[(size_t)i * 2 + 1].get()));
         sum += ms;
     }
     *sum_ms = (float)sum;
@@ -1918,31 +1908,28 @@ int rr_get_stats(rr_context* ctx, rr_stats* out)
     if (int r = use_device(ctx)) return r;
     if (!out) return RR_ERR_INVALID_ARGUMENT;
     if (int r = join_lanes(ctx)) return r;
-    CounterBlock* h = (CounterBlock*)malloc(sizeof(CounterBlock));
-    if (!h) return RR_ERR_OUT_OF_MEMORY;
-    hipError_t e = hipMemcpyAsync(h, ctx->d_cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(h); return fail(ctx, RR_ERR_DEVICE, "rr_get_stats", e); }
+    CounterBlock h;
+    RR_HIP_MSG(hipMemcpyAsync(&h, ctx->d_cnt.get(), sizeof(CounterBlock), hipMemcpyDeviceToHost, ctx->stream), "rr_get_stats");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "rr_get_stats");
     memset(out, 0, sizeof *out);
     uint64_t rays = 0;
-    for (int i = 0; i < RAY_SHARDS; ++i) rays += h->shards[i];
+    for (int i = 0; i < RAY_SHARDS; ++i) rays += h.shards[i];
     out->rays = rays;
     out->pixels = ctx->accum_pixels;
     out->primary = ctx->accum_pixels;
     out->secondary = rays - out->primary;
     out->stats_valid = ctx->last_stats ? 1u : 0u;
     if (ctx->last_stats) {
-        out->hits = h->counters[C_HITS]; out->misses = h->counters[C_MISSES]; out->terminal_hits = h->counters[C_TERMINAL];
-        out->tir = h->counters[C_TIR]; out->node_visits = h->counters[C_NODES]; out->tri_tests = h->counters[C_TRIS];
-        out->node_trips = h->counters[C_NODE_TRIPS]; out->leaf_trips = h->counters[C_LEAF_TRIPS];
-        out->shade_passes = h->counters[C_PASSES]; out->waves = h->counters[C_WAVES]; out->background_waves = h->counters[C_BG_WAVES];
-        out->clock_ticks = h->counters[C_CLK_TICKS]; out->clock_ref_ticks = h->counters[C_CLK_REAL];
+        out->hits = h.counters[C_HITS]; out->misses = h.counters[C_MISSES]; out->terminal_hits = h.counters[C_TERMINAL];
+        out->tir = h.counters[C_TIR]; out->node_visits = h.counters[C_NODES]; out->tri_tests = h.counters[C_TRIS];
+        out->node_trips = h.counters[C_NODE_TRIPS]; out->leaf_trips = h.counters[C_LEAF_TRIPS];
+        out->shade_passes = h.counters[C_PASSES]; out->waves = h.counters[C_WAVES]; out->background_waves = h.counters[C_BG_WAVES];
+        out->clock_ticks = h.counters[C_CLK_TICKS]; out->clock_ref_ticks = h.counters[C_CLK_REAL];
     }
     memcpy(out->render_kernel_name, ctx->last_kernel_name, sizeof out->render_kernel_name);
-    out->traversal_overflow = h->error;
+    out->traversal_overflow = h.error;
     out->bvh_depth = scene_stack_need(ctx);
     out->render_kernel = ctx->last_kernel;
-    free(h);
     return RR_OK;
 }
 
@@ -1955,12 +1942,12 @@ int rr_trace_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
     if (int r = ensure_rays(ctx, n)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
-    RR_HIP(hipMemsetAsync(&ctx->d_cnt->error, 0, 4, ctx->stream));
-    RR_HIP(hipMemcpyAsync(ctx->d_rays, rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    RR_HIP(launch_trace_rays(sc, ctx->d_rays, n, ctx->d_hits, &ctx->d_cnt->error, scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
-    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits, (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemsetAsync(&ctx->d_cnt.get()->error, 0, 4, ctx->stream));
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(launch_trace_rays(sc, ctx->d_rays.get(), n, ctx->d_hits.get(), &ctx->d_cnt.get()->error, scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
+    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
     uint32_t err = 0;
-    RR_HIP(hipMemcpyAsync(&err, &ctx->d_cnt->error, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemcpyAsync(&err, &ctx->d_cnt.get()->error, 4, hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     if (err) return fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, "traversal stack overflow");
     return RR_OK;
@@ -1975,9 +1962,9 @@ int rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
     if (int r = ensure_rays(ctx, n)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
-    RR_HIP(hipMemcpyAsync(ctx->d_rays, rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    RR_HIP(launch_query_rays(sc, ctx->d_rays, n, ctx->d_hits, inst0_mask(ctx), scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
-    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits, (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(launch_query_rays(sc, ctx->d_rays.get(), n, ctx->d_hits.get(), inst0_mask(ctx), scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
+    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));
     return RR_OK;
 }
@@ -2001,17 +1988,15 @@ int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)
     if (int r = use_device(ctx)) return r;
     if ((!dirs || !rgb) && n) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_env_lookup: null buffers");
     if (n == 0) return RR_OK;
-    float *d_in = nullptr, *d_out = nullptr;
-    RR_HIP(hipMalloc(&d_in, (size_t)n * 12));
-    hipError_t e = hipMalloc(&d_out, (size_t)n * 12);
+    DevBuf<float> d_in, d_out;
+    RR_HIP(d_in.alloc((size_t)n * 3));
+    RR_HIP_MSG(d_out.alloc((size_t)n * 3), "rr_env_lookup");
     SceneDev sc;
     fill_scene(ctx, sc);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, dirs, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_env_lookup(sc, d_in, n, d_out, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rgb, d_out, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(ctx, RR_ERR_DEVICE, "rr_env_lookup", e);
+    RR_HIP_MSG(hipMemcpyAsync(d_in.get(), dirs, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(launch_env_lookup(sc, d_in.get(), n, d_out.get(), ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(hipMemcpyAsync(rgb, d_out.get(), (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "rr_env_lookup");
     return RR_OK;
 }
 
@@ -2025,8 +2010,8 @@ int rr_download_blas(rr_context* ctx, uint32_t mesh_id, void* nodes, uint32_t* n
     if (n_nodes) *n_nodes = nn;
     if (n_tris) *n_tris = m.n_tris;
     RR_HIP(hipStreamSynchronize(ctx->stream));
-    if (nodes) RR_HIP(hipMemcpy(nodes, m.nodes, (size_t)nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
-    if (tris) RR_HIP(hipMemcpy(tris, m.tris, (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToHost));
+    if (nodes) RR_HIP(hipMemcpy(nodes, m.nodes.get(), (size_t)nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    if (tris) RR_HIP(hipMemcpy(tris, m.tris.get(), (size_t)m.n_tris * sizeof(TriRec), hipMemcpyDeviceToHost));
     return RR_OK;
 }
 
@@ -2056,7 +2041,7 @@ int rr_download_qnodes(rr_context* ctx, uint32_t mesh_id, void* qnodes, uint32_t
     if (n_nodes) *n_nodes = nn;
     if (grid_org_cell) { memcpy(grid_org_cell, m.grid.org, 12); memcpy(grid_org_cell + 3, m.grid.cell, 12); }
     RR_HIP(hipStreamSynchronize(ctx->stream));
-    if (qnodes) RR_HIP(hipMemcpy(qnodes, m.qnodes, (size_t)nn * sizeof(QNode), hipMemcpyDeviceToHost));
+    if (qnodes) RR_HIP(hipMemcpy(qnodes, m.qnodes.get(), (size_t)nn * sizeof(QNode), hipMemcpyDeviceToHost));
     return RR_OK;
 }
 

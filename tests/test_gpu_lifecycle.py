@@ -1,0 +1,169 @@
+"""GPU: rr_destroy gives back what a context allocated.
+
+Four cycles of create -> work -> close() in one process.  The work reaches every resource a context allocates on first use:
+meshes built for update and refitted, a TLAS built for update and updated, the frame / float / assembled buffers, the constant
+buffers and their page-locked staging, the timing events, the render lanes, the trace-rays scratch, the LDS kernel's park slab,
+the stream renderer's buffer sets and a kernel-choice measurement.  Free device memory is read after cycle 1 (which absorbs the
+runtime's own one-time allocations) and again after cycles 2-4: it must not fall by more than 64 MiB.  A leaked 1080p Depth 16
+frame buffer alone would be 130 MB, the LDS park slab 64 MiB per stream.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle as O
+import refraction_raytracing_dxr_amd as rr
+from conftest import procedural_env
+
+pytestmark = pytest.mark.gpu
+
+LEAK_LIMIT = 64 << 20
+LDS = 1             # rr_stats.render_kernel of k_render_lds
+
+
+def load(name):
+    m = rr.Mesh()
+    assert m.load(O.asset(name))
+    return m.verts, m.indices
+
+
+def free_bytes():
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return torch.cuda.mem_get_info(0)[0]
+
+
+def orbit_cams(n, angle=0.3):
+    return [rr.camera_orbit(angle + 0.01 * k) for k in range(n)]
+
+
+def checked_stats(r):
+    st = r.stats()
+    assert st.rays > 0 and st.traversal_overflow == 0
+    return st
+
+
+def two_level_work(r, torch, a, b, verts_a, verts_b):
+    """meshes updated and refitted, a two-instance TLAS built for update and updated, then every kind of launch on it"""
+    W, H = 320, 180
+    r.update_mesh_vertices(a, verts_a)                                     # from the host
+    t = torch.from_numpy(verts_b.view(np.float32).reshape(-1, 8).copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    r.update_mesh_vertices(b, t)                                           # from a tensor
+    r.build_blas(a, update=True)
+    r.build_blas(b, update=True)
+    xf = [np.eye(4, dtype=np.float32)[:3].copy() for _ in range(2)]
+    xf[1][0, 3] = 2.5
+    r.build_tlas(rr.make_instances(transforms=xf, meshes=[a, b]), allow_update=True)
+    xf[1][1, 3] = 0.5
+    r.build_tlas(rr.make_instances(transforms=xf, meshes=[a, b]), update=True)
+
+    # one shape three times: its second dispatch measures the kernel choice, the stream renderer included
+    r.set_camera(rr.camera_orbit(0.2))
+    flags = rr.DISPATCH_FLOAT_OUTPUT | rr.DISPATCH_COLLECT_STATS | rr.DISPATCH_TIME_KERNEL
+    r.timing_begin()
+    for _ in range(3):
+        r.dispatch_rays(W, H, rr.default_params(flags=flags))
+    assert r.timing_end() > 0.0
+    assert r.kernel_time()[1] == 3
+    rgba, f32 = r.read_frame(want_float=True)
+    assert rgba.shape == (H, W, 4) and f32.shape == (H, W, 4)
+    checked_stats(r)
+    r.dispatch_rays_batch(1920, 1080, orbit_cams(16))                      # a 1080p Depth 16 frame buffer
+    checked_stats(r)
+
+    r.set_frames_in_flight(2)
+    r.render_orbit(W, H, 4, frames_per_dispatch=2)
+    r.wait()
+    frames = r.render_orbit_to_host(W, H, 4, frames_per_dispatch=2)
+    assert frames.shape == (4, H, W, 4)
+
+    # world 2 on this one context: rank 0, then rank 1, on a render lane; then the assembly
+    F, world = 2, 2
+    fs = rr.dist.max_local_tiles(W, H, world) * 32 * 32 * 4
+    gat = torch.zeros(world * F * fs, dtype=torch.uint8, device="cuda:0")
+    out = torch.zeros(F * W * H * 4, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    for rank in range(world):
+        r.set_tile_partition(rank, world)
+        r.render_orbit_sharded(W, H, F, gat.data_ptr() + rank * F * fs, fs, lane=0)
+        r.lane_join(0)
+    r.assemble_frames(gat.data_ptr(), world, F * fs, fs, F, W, H, out.data_ptr(), W * H * 4)
+    r.wait()
+    checked_stats(r)
+
+    r.set_tile_partition(0, world)
+    part = r.mesh_partition_for_orbit(W, H, F)
+    fs, bs = max(part.max_mesh_tiles_per_rank, 1) * 3072, max(part.n_bg_tiles, 1) * 3072
+    gat = torch.zeros(world * F * fs, dtype=torch.uint8, device="cuda:0")
+    bg = torch.zeros(F * bs, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    for rank in range(world):
+        r.set_tile_partition(rank, world)
+        r.render_orbit_mesh_sharded(W, H, F, C.c_void_p(gat.data_ptr() + rank * F * fs), fs, C.c_void_p(bg.data_ptr()) if rank == 0 else None,
+                                    bs, lane=1)
+        r.lane_join(1)
+    r.set_tile_partition(0, world)
+    r.assemble_frames_mesh(C.c_void_p(gat.data_ptr()), F * fs, fs, C.c_void_p(bg.data_ptr()), bs, part, F, W, H, C.c_void_p(out.data_ptr()),
+                           W * H * 4)
+    r.wait()
+    checked_stats(r)
+    r.set_tile_partition(0, 1)
+
+    rng = np.random.default_rng(0)
+    o = np.tile(np.float32([0.0, 0.0, -6.0]), (4096, 1))
+    d = rng.normal(size=(4096, 3)).astype(np.float32) * 0.1 + np.float32([0.0, 0.0, 1.0])
+    rays = rr.pack_rays(o, d, 0.0, 100.0)
+    hits = r.trace_rays(rays)
+    assert hits["hit"].any() and r.query_rays(rays).tobytes() == hits.tobytes()
+    t_hits = r.query_rays(rr.pack_rays(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), 0.0, 100.0))
+    r.wait()
+    assert t_hits.cpu().numpy().tobytes() == hits.tobytes()
+    assert r.env_lookup(d).shape == (4096, 3)
+    for m in (a, b):
+        nodes, tris = r.download_blas(m)
+        q, _, _ = r.download_qnodes(m)
+        assert len(nodes) == len(q) and len(tris) > 0
+
+
+def lds_work(r, a):
+    """the single-mesh scene: a 24-slice shape three times -- k_render_lds renders the first, the second measures it against
+    k_render_fused"""
+    r.build_tlas(rr.make_instances(meshes=[a]))
+    W, H = 640, 360
+    cams = orbit_cams(24)
+    r.dispatch_rays_batch(W, H, cams)
+    assert checked_stats(r).render_kernel == LDS
+    for _ in range(2):
+        r.dispatch_rays_batch(W, H, cams)
+    checked_stats(r)
+
+
+def cycle(meshes, env):
+    import torch
+    r = rr.Renderer(0)
+    try:
+        (va, ia), (vb, ib) = meshes
+        a, b = r.upload_mesh(va, ia), r.upload_mesh(vb, ib)
+        r.build_blas(a, allow_update=True)
+        r.build_blas(b, allow_update=True)
+        r.upload_envmap(env)
+        two_level_work(r, torch, a, b, va, vb)
+        lds_work(r, a)
+        r.wait()
+    finally:
+        r.close()
+
+
+def test_destroy_gives_back_what_a_context_allocated():
+    meshes = [load("monkey.obj"), load("sphere.obj")]
+    env = procedural_env(256, 128, seed=5)
+    free = []
+    for _ in range(4):
+        cycle(meshes, env)
+        free.append(free_bytes())
+    drops = [(free[0] - f) / 2**20 for f in free[1:]]
+    print("free device memory after cycle 1: %.1f MiB; fall after cycles 2-4: %s MiB" % (free[0] / 2**20, ", ".join("%.1f" % x for x in drops)))
+    assert max(drops) * 2**20 <= LEAK_LIMIT, drops

@@ -149,7 +149,7 @@ typedef struct rr_hit {
     float    t, u, v;             /* u weights vertex 1, v weights vertex 2 (RayTracing.hlsl:86) */
     uint32_t prim;                /* PrimitiveIndex() */
     uint32_t inst;                /* index into the rr_build_tlas array */
-    uint32_t hit;                 /* 0 = miss */
+    uint32_t hit;                 /* 0 = miss; rr_query_rays_multi: the DXR HitKind of the triangle */
 } rr_hit;
 
 typedef struct rr_context rr_context;
@@ -389,6 +389,25 @@ int  rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits
  * reads the rays after the work queued on that stream before the call, nothing is synchronised and nothing allocated.  The
  * rays must stay valid, and the hits must not be read, until that stream has run the query. */
 int  rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void* d_hits);
+/* Multi-hit queries (DXR's any-hit idiom that records each candidate and calls IgnoreHit), in one walk per ray.  For ray i the
+ * hits are every triangle the closest-hit query's test accepts with t in (tmin, tmax), under the ray's cull flags and instance
+ * mask (instance flags applied as for a closest hit), sorted ascending by (t, inst, prim); each (inst, prim) appears at most
+ * once.  The first min(k, total) of them go to hits[i*k + j]: t, u, v, prim and inst have the bits a closest-hit query reports
+ * for that triangle, and `hit` holds the DXR HitKind -- RR_HIT_KIND_TRIANGLE_FRONT_FACE if det > 0 in object space (swapped by
+ * RR_INSTANCE_FLAG_TRIANGLE_FRONT_COUNTERCLOCKWISE, the rule the cull flags follow), else _BACK_FACE.  The remaining slots are
+ * miss records (hit 0, t = the ray's tmax, u = v = prim = inst = 0).  counts may be NULL; if given, counts[i] is the total
+ * number of accepted triangles (the walk is then not pruned by the k-th hit; the slots are the same either way).
+ * 0 <= k <= RR_QUERY_MAX_HITS, and k == 0 only with counts (an occupancy query); anything else is RR_ERR_INVALID_ARGUMENT.
+ * RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH and _SKIP_CLOSEST_HIT_SHADER are ignored (an any-hit shader that ignores every
+ * hit commits none, so there is nothing to end the search on).  Errors, state and stream order as rr_query_rays[_device]; the
+ * device variant takes 16-byte aligned rays and 4-byte aligned hits (n*k records) and counts (n words), allocates nothing.
+ * NOT a crossing count: the triangle test is Moller-Trumbore, not watertight, so a ray through an edge shared by two
+ * triangles may report both of them or neither. */
+#define RR_QUERY_MAX_HITS 16
+#define RR_HIT_KIND_TRIANGLE_FRONT_FACE 0xFEu   /* DXR HIT_KIND_* values */
+#define RR_HIT_KIND_TRIANGLE_BACK_FACE  0xFFu
+int  rr_query_rays_multi(rr_context* ctx, const rr_ray* rays, uint32_t n, uint32_t k, rr_hit* hits, uint32_t* counts);
+int  rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, uint32_t k, void* d_hits, void* d_counts);
 
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel

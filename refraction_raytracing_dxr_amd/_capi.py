@@ -26,6 +26,9 @@ RAY_FLAG_ACCEPT_FIRST_HIT = 0x4          # RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_
 RAY_FLAG_SKIP_CLOSEST_HIT_SHADER = 0x8   # accepted, no effect
 RAY_FLAG_CULL_BACK = 0x10
 RAY_FLAG_CULL_FRONT = 0x20
+QUERY_MAX_HITS = 16                      # RR_QUERY_MAX_HITS: largest k of query_rays_multi
+HIT_KIND_FRONT_FACE = 0xFE               # RR_HIT_KIND_TRIANGLE_FRONT_FACE (query_rays_multi's hit word)
+HIT_KIND_BACK_FACE = 0xFF
 INSTANCE_FLAG_CULL_DISABLE = 0x1
 INSTANCE_FLAG_FRONT_CCW = 0x2
 
@@ -137,6 +140,8 @@ SYMBOLS = {
     "rr_trace_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_query_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_query_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "rr_query_rays_multi": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "rr_query_rays_multi_device": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

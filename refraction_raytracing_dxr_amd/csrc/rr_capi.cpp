@@ -259,6 +259,7 @@ struct rr_context {
     // trace_rays scratch
     DevBuf<rr_ray_dev> d_rays;
     DevBuf<rr_hit_dev> d_hits;
+    DevBuf<uint32_t>   d_counts;     // rr_query_rays_multi
 };
 
 namespace {
@@ -1980,6 +1981,46 @@ int rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void* 
     fill_scene(ctx, sc);
     RR_HIP(launch_query_rays(sc, static_cast<const rr_ray_dev*>(d_rays), n, static_cast<rr_hit_dev*>(d_hits), inst0_mask(ctx),
                              scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
+    return RR_OK;
+}
+
+int rr_query_rays_multi(rr_context* ctx, const rr_ray* rays, uint32_t n, uint32_t k, rr_hit* hits, uint32_t* counts)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_multi: build the BLAS and TLAS first");
+    if (k > RR_QUERY_MAX_HITS || (k == 0 && !counts))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi: need 1 <= k <= 16, or k == 0 with counts");
+    if (n == 0) return RR_OK;
+    if (!rays || (k && !hits)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi: null arrays");
+    const size_t nk = (size_t)n * k;
+    if (int r = ensure_rays(ctx, n)) return r;
+    if (nk > ctx->d_hits.size()) if (int r = ctx->d_hits.grow(ctx, nk)) return r;
+    if (counts && n > ctx->d_counts.size()) if (int r = ctx->d_counts.grow(ctx, n)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(launch_query_multi(sc, ctx->d_rays.get(), n, k, ctx->d_hits.get(), counts ? ctx->d_counts.get() : nullptr, inst0_mask(ctx),
+                              scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
+    if (k) RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), nk * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) RR_HIP(hipMemcpyAsync(counts, ctx->d_counts.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, uint32_t k, void* d_hits, void* d_counts)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_multi_device: build the BLAS and TLAS first");
+    if (k > RR_QUERY_MAX_HITS || (k == 0 && !d_counts))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi_device: need 1 <= k <= 16, or k == 0 with counts");
+    if (n == 0) return RR_OK;
+    if (!d_rays || (k && !d_hits) || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_query_rays_multi_device: need a 16-byte aligned ray and 4-byte aligned hit and count pointers");
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(launch_query_multi(sc, static_cast<const rr_ray_dev*>(d_rays), n, k, static_cast<rr_hit_dev*>(d_hits),
+                              static_cast<uint32_t*>(d_counts), inst0_mask(ctx), scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
     return RR_OK;
 }
 

@@ -273,20 +273,20 @@ __device__ __forceinline__ void diag_trip(const Diag& d, int which = 0)
 }
 
 
-// scaled Moller-Trumbore; front-facing <=> det > 0.  Equal-t ties go to the lower
-// (instance, primitive) so that the result does not depend on traversal order.
-__device__ __forceinline__ void tri_test(const TriRec* __restrict__ tris, uint32_t leaf, f3 O, f3 D, float tmin,
-                                         uint32_t cull, uint32_t inst, HitRec& best)
+// scaled Moller-Trumbore; front-facing <=> det > 0.  tri_accept: does the triangle pass the cull test and
+// the edge tests with t > tmin?  (t: its distance, prim: its primitive index.)
+__device__ __forceinline__ bool tri_accept(const TriRec* __restrict__ tris, uint32_t leaf, f3 O, f3 D, float tmin, uint32_t cull,
+                                           float& t, uint32_t& prim)
 {
     const float4* q = reinterpret_cast<const float4*>(tris + leaf);
     float4 a = q[0], b = q[1], c = q[2];
     f3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
-    uint32_t prim = __float_as_uint(a.w);
+    prim = __float_as_uint(a.w);
     f3 pv = cross3(D, e2);
     float det = dot3(e1, pv);
-    if (cull & CULL_BACK) { if (!(det > 0.0f)) return; }
-    else if (cull & CULL_FRONT) { if (!(det < 0.0f)) return; }
-    else if (!(det != 0.0f)) return;
+    if (cull & CULL_BACK) { if (!(det > 0.0f)) return false; }
+    else if (cull & CULL_FRONT) { if (!(det < 0.0f)) return false; }
+    else if (!(det != 0.0f)) return false;
     f3 tv = sub3(O, v0);
     float U = dot3(tv, pv);
     f3 qv = cross3(tv, e1);
@@ -294,9 +294,18 @@ __device__ __forceinline__ void tri_test(const TriRec* __restrict__ tris, uint32
     float T = dot3(e2, qv);
     float ad = det;
     if (det < 0.0f) { U = -U; V = -V; T = -T; ad = -det; }
-    if (U < 0.0f || V < 0.0f || U + V > ad) return;
-    float t = T / ad;
-    if (!(t > tmin)) return;
+    if (U < 0.0f || V < 0.0f || U + V > ad) return false;
+    t = T / ad;
+    return t > tmin;
+}
+
+// The closest hit.  Equal-t ties go to the lower (instance, primitive) so that the result does not depend on traversal order.
+__device__ __forceinline__ void tri_test(const TriRec* __restrict__ tris, uint32_t leaf, f3 O, f3 D, float tmin,
+                                         uint32_t cull, uint32_t inst, HitRec& best)
+{
+    float t;
+    uint32_t prim;
+    if (!tri_accept(tris, leaf, O, D, tmin, cull, t, prim)) return;
     // (the barycentrics of the winner are recomputed once, after the traversal: hit_attributes.  Carrying them through
     // the loops costs four registers per lane; an exact tie needs the other triangle's primitive index, a rare load.)
     if (t < best.t || (t == best.t && best.hit && (inst < best.inst || (inst == best.inst && prim < tris[best.leaf].prim)))) {
@@ -306,8 +315,9 @@ __device__ __forceinline__ void tri_test(const TriRec* __restrict__ tris, uint32
 }
 
 // Attributes of the closest hit: the same operations, in the same order, as the test that accepted it (O, D: the ray in
-// the space of the triangle's BLAS), so U, V, ad have the very bits tri_test computed.
-__device__ __forceinline__ void hit_attributes(const TriRec* __restrict__ tris, f3 O, f3 D, HitRec& best)
+// the space of the triangle's BLAS), so U, V, ad have the very bits tri_test computed.  Returns det (> 0: front-facing in
+// object space).
+__device__ __forceinline__ float hit_attributes(const TriRec* __restrict__ tris, f3 O, f3 D, HitRec& best)
 {
     const float4* q = reinterpret_cast<const float4*>(tris + best.leaf);
     float4 a = q[0], b = q[1], c = q[2];
@@ -321,7 +331,81 @@ __device__ __forceinline__ void hit_attributes(const TriRec* __restrict__ tris, 
     float ad = det;
     if (det < 0.0f) { U = -U; V = -V; ad = -det; }
     best.U = U; best.V = V; best.ad = ad; best.prim = __float_as_uint(a.w);
+    return det;
 }
+
+// ---- hit policies: what the walks keep of the triangles they accept ------------------------------------------------------
+// walk_blas / trace_scene take the hit record by type; each record type supplies
+//   hits_begin(h, tmax)           before the walk
+//   hit_bound(h)                  the far distance the box tests cull with (inclusive)
+//   leaf_test(tris, leaf, ... h)  the triangle test of a leaf
+//   hit_found(h)                  a first-hit lane may end its walk (RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH)
+//   hits_end_blas / hits_end_scene  after the walk (the closest hit's attributes)
+// HitRec is the closest hit of the render, trace and query kernels: these are the very operations the walks had inline.
+__device__ __forceinline__ void hits_begin(HitRec& best, float tmax)
+{
+    best.t = tmax; best.hit = false; best.prim = 0; best.leaf = 0; best.inst = 0; best.U = 0.0f; best.V = 0.0f;
+    best.ad = 1.0f;
+}
+__device__ __forceinline__ float hit_bound(const HitRec& best) { return best.t; }
+__device__ __forceinline__ bool hit_found(const HitRec& best) { return best.hit; }
+__device__ __forceinline__ void leaf_test(const TriRec* __restrict__ tris, uint32_t leaf, f3 O, f3 D, float tmin, uint32_t cull,
+                                          uint32_t inst, HitRec& best)
+{
+    tri_test(tris, leaf, O, D, tmin, cull, inst, best);
+}
+__device__ __forceinline__ void hits_end_blas(const TriRec* __restrict__ tris, f3 O, f3 D, HitRec& best)
+{
+    if (best.hit) hit_attributes(tris, O, D, best);
+}
+
+// Multi-hit (rr_query_rays_multi): the KB first accepted triangles in (t, inst, prim) order, in registers -- every index below
+// is a compile-time constant once the loops are unrolled, so the slots never go to scratch.  An empty slot holds t = tmax,
+// which no accepted triangle reaches (t < tmax), so the slots stay sorted with the empty ones last.  The box tests cull with
+// the last slot's t (tmax until KB triangles are in: inclusive, so a tie with a lower (inst, prim) still reaches its leaf);
+// COUNT also counts every accepted triangle and so culls with tmax throughout.  The primitive index of a slot is loaded only
+// on an exact tie, as tri_test does.
+template <int KB, bool COUNT>
+struct MultiHits {
+    float t[KB];
+    uint32_t leaf[KB], inst[KB];
+    float tmax;
+    uint32_t count;
+};
+template <int KB, bool COUNT>
+__device__ __forceinline__ void hits_begin(MultiHits<KB, COUNT>& m, float tmax)
+{
+#pragma unroll
+    for (int j = 0; j < KB; ++j) { m.t[j] = tmax; m.leaf[j] = 0; m.inst[j] = 0; }
+    m.tmax = tmax; m.count = 0;
+}
+template <int KB, bool COUNT>
+__device__ __forceinline__ float hit_bound(const MultiHits<KB, COUNT>& m) { return COUNT ? m.tmax : m.t[KB - 1]; }
+template <int KB, bool COUNT>
+__device__ __forceinline__ bool hit_found(const MultiHits<KB, COUNT>&) { return false; }
+template <int KB, bool COUNT>
+__device__ __forceinline__ void leaf_test(const TriRec* __restrict__ tris, uint32_t leaf, f3 O, f3 D, float tmin, uint32_t cull,
+                                          uint32_t inst, MultiHits<KB, COUNT>& m)
+{
+    float t;
+    uint32_t prim;
+    if (!tri_accept(tris, leaf, O, D, tmin, cull, t, prim) || !(t < m.tmax)) return;
+    if (COUNT) m.count++;
+    // before[j]: the triangle goes before slot j (false ... false true ... true, the slots being sorted)
+    bool before[KB];
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+        before[j] = t < m.t[j] || (t == m.t[j] && (inst < m.inst[j] || (inst == m.inst[j] && prim < tris[m.leaf[j]].prim)));
+    if (!before[KB - 1]) return;
+#pragma unroll
+    for (int j = KB - 1; j > 0; --j) {
+        if (before[j - 1]) { m.t[j] = m.t[j - 1]; m.leaf[j] = m.leaf[j - 1]; m.inst[j] = m.inst[j - 1]; }
+        else if (before[j]) { m.t[j] = t; m.leaf[j] = leaf; m.inst[j] = inst; }
+    }
+    if (before[0]) { m.t[0] = t; m.leaf[0] = leaf; m.inst[0] = inst; }
+}
+template <int KB, bool COUNT>
+__device__ __forceinline__ void hits_end_blas(const TriRec* __restrict__, f3, f3, MultiHits<KB, COUNT>&) {}
 
 // "while-while" traversal with an early hand-over: called by the lanes still descending (exec = those lanes, so
 // the count is a scalar s_bcnt1 of exec, no VALU work); true once max(2, n_in/4) of the n_in lanes that entered the
@@ -342,9 +426,10 @@ __device__ __forceinline__ bool leaf_phase_due(int n_in)
 // all lanes that hold a leaf.
 // ANY (the query kernels): a lane with any_lane set ends its walk at the first triangle it accepts (DXR
 // RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH); ANY = false is the closest-hit loop of the render and trace kernels.
-template <bool STATS, class E, class NS = GlobalNodes, bool ANY = false>
+// H: the hit policy (HitRec: closest hit; MultiHits: rr_query_rays_multi).
+template <bool STATS, class E, class NS = GlobalNodes, bool ANY = false, class H = HitRec>
 __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const TriRec* __restrict__ tris, int root, const BoxRay& br,
-                                          f3 O, f3 D, float tmin, uint32_t cull, uint32_t inst, HitRec& best, E* stk,
+                                          f3 O, f3 D, float tmin, uint32_t cull, uint32_t inst, H& best, E* stk,
                                           TravCounters& cnt, const Diag dg = Diag{ nullptr }, const NS ns = NS{},
                                           bool any_lane = false)
 {
@@ -360,7 +445,7 @@ __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const
             diag_trip(dg);
             const NodeQ q = ns.load(nodes, node);
             if (STATS) { cnt.nodes++; if (first_active_lane()) cnt.node_trips++; }
-            node = node_step(br, q, tmin, best.t, top, stk);
+            node = node_step(br, q, tmin, hit_bound(best), top, stk);
 #ifdef RR_EXP_EXTRA_VALU      // experiment: what do N more VALU instructions per visit cost?
             { float dv = br.inv.x;
 #pragma unroll
@@ -372,22 +457,22 @@ __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const
         if (node < 0 && node != TRAV_DONE) {
             diag_trip(dg, 1);
             if (STATS) { cnt.tris++; if (first_active_lane()) cnt.leaf_trips++; }
-            tri_test(tris, (uint32_t)~node, O, D, tmin, cull, inst, best);
-            if (ANY && any_lane && best.hit) { top = stk; node = TRAV_DONE; }
+            leaf_test(tris, (uint32_t)~node, O, D, tmin, cull, inst, best);
+            if (ANY && any_lane && hit_found(best)) { top = stk; node = TRAV_DONE; }
             else if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
         }
         if (__ballot(node != TRAV_DONE) == 0ull) break;
     }
 }
 
-template <bool STATS, class E, class NS = GlobalNodes>
+template <bool STATS, class E, class NS = GlobalNodes, class H = HitRec>
 __device__ __forceinline__ void trace_blas(const BlasDev& bl, f3 O, f3 D, float tmin, uint32_t cull, uint32_t inst,
-                                           HitRec& best, E* stk, TravCounters& cnt, const Diag dg = Diag{ nullptr },
+                                           H& best, E* stk, TravCounters& cnt, const Diag dg = Diag{ nullptr },
                                            const NS ns = NS{})
 {
     const BoxRay br = box_ray(O, D, bl.scale, bl.grid);
     walk_blas<STATS, E, NS>(bl.nodes, bl.tris, 0, br, O, D, tmin, cull, inst, best, stk, cnt, dg, ns);
-    if (best.hit) hit_attributes(bl.tris, O, D, best);
+    hits_end_blas(bl.tris, O, D, best);
 }
 
 // ---- group-parallel traversal: G lanes (an aligned group of 2 or 4) walk ONE ray's tree ------------------------------
@@ -515,6 +600,25 @@ __device__ __forceinline__ InstDev inst_record(const InstDev* __restrict__ insts
     return r;
 }
 
+// the ray in the space of instance ii's BLAS
+__device__ __forceinline__ void ray_in_instance(const InstDev& in, f3 O, f3 D, f3& Oc, f3& Dc)
+{
+    Oc = O; Dc = D;
+    if (!in.identity) { Oc = xform_point(in.inv, O); Dc = xform_dir(in.inv, D); }
+}
+// the end of a two-level walk (hit policies, see hits_begin)
+__device__ __forceinline__ void hits_end_scene(const SceneDev& sc, f3 O, f3 D, HitRec& best)
+{
+    if (best.hit) {
+        const InstDev in = inst_record(sc.insts, best.inst);
+        f3 Oh = O, Dh = D;
+        if (!in.identity) { Oh = xform_point(in.inv, O); Dh = xform_dir(in.inv, D); }
+        hit_attributes(sc.pool_tris, Oh, Dh, best);
+    }
+}
+template <int KB, bool COUNT>
+__device__ __forceinline__ void hits_end_scene(const SceneDev&, f3, f3, MultiHits<KB, COUNT>&) {}
+
 // TraceRay(Scene, flags, 0xff, 0,0,0, ray, payload): closest hit over TLAS -> BLAS.
 // TLAS = false: the reference's scene, one BLAS.  TLAS = true: the wave walks the top level in world space until every lane
 // holds an instance leaf or has finished; the lanes at a leaf then walk their instances (walk_blas: the single-BLAS loop with
@@ -528,19 +632,19 @@ __device__ __forceinline__ InstDev inst_record(const InstDev* __restrict__ insts
 // (InstanceMask & ray_mask) != 0; with TLAS = false the caller has already tested the one instance's mask, and ray_mask == 0
 // means the lane's ray passes nothing.  any_lane: the lane ends its walk, both levels, at the first triangle it accepts.
 // QUERY = false is the render and trace kernels' code (mask 0xff, closest hit).
-template <bool STATS, bool TLAS, class E = uint32_t, class NS = GlobalNodes, bool QUERY = false>
+// H: the hit policy (HitRec: closest hit, and attributes of the hit on return; MultiHits: rr_query_rays_multi, slots only).
+template <bool STATS, bool TLAS, class E = uint32_t, class NS = GlobalNodes, bool QUERY = false, class H = HitRec>
 __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, float tmin, float tmax, uint32_t flags,
-                                            HitRec& best, E* stk_e, TravCounters& cnt,
+                                            H& best, E* stk_e, TravCounters& cnt,
                                             const Diag dg = Diag{ nullptr }, const NS ns = NS{},
                                             uint32_t ray_mask = 0xffu, bool any_lane = false)
 {
-    best.t = tmax; best.hit = false; best.prim = 0; best.leaf = 0; best.inst = 0; best.U = 0.0f; best.V = 0.0f;
-    best.ad = 1.0f;
+    hits_begin(best, tmax);
     if (!TLAS && QUERY) {
         const BoxRay br = box_ray(O, D, sc.blas0.scale, sc.blas0.grid);
         walk_blas<STATS, E, NS, true>(sc.blas0.nodes, sc.blas0.tris, (ray_mask & 0xffu) ? 0 : TRAV_DONE, br, O, D, tmin, flags, 0u,
                                       best, stk_e, cnt, dg, ns, any_lane);
-        if (best.hit) hit_attributes(sc.blas0.tris, O, D, best);
+        hits_end_blas(sc.blas0.tris, O, D, best);
         return;
     }
     if (!TLAS) {      // the reference's scene: one identity instance, mask 1, flags 0 (RefractionDemo.cpp:324-334)
@@ -556,7 +660,7 @@ __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, floa
         while (node >= 0) {
             const NodeQ q = load_node(nodes, node);
             if (STATS) { cnt.nodes++; if (first_active_lane()) cnt.node_trips++; }
-            node = node_step(br, q, tmin, best.t, top, stk);
+            node = node_step(br, q, tmin, hit_bound(best), top, stk);
         }
         if (node == TRAV_DONE) break;
         if (STATS && first_active_lane()) cnt.leaf_trips++;
@@ -575,15 +679,10 @@ __device__ __forceinline__ void trace_scene(const SceneDev& sc, f3 O, f3 D, floa
             walk_blas<STATS, E, GlobalNodes, QUERY>(nodes, sc.pool_tris, (int)in.root, bi, Oc, Dc, tmin, f, ii, best, top, cnt,
                                                     Diag{ nullptr }, GlobalNodes{}, any_lane);
         }
-        if (QUERY && any_lane && best.hit) node = TRAV_DONE;
+        if (QUERY && any_lane && hit_found(best)) node = TRAV_DONE;
         else if (top > stk) { top -= STACK_STRIDE; node = StackCodec<E>::dec(*top); } else node = TRAV_DONE;
     }
-    if (best.hit) {
-        const InstDev in = inst_record(sc.insts, best.inst);
-        f3 Oh = O, Dh = D;
-        if (!in.identity) { Oh = xform_point(in.inv, O); Dh = xform_dir(in.inv, D); }
-        hit_attributes(sc.pool_tris, Oh, Dh, best);
-    }
+    hits_end_scene(sc, O, D, best);
 }
 
 // ---- Miss: RayTracing.hlsl:127-137 -------------------------------------------------------------

@@ -33,6 +33,11 @@ hipError_t launch_trace_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_
 // a single-identity scene's instance
 hipError_t launch_query_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t inst0_mask, int stack,
                              hipStream_t s);
+// ---- rr_query_multi.hip: multi-hit queries (rr_query_rays_multi[_device]): the first k accepted triangles per ray, k slots of
+// hits per ray; counts (may be null) receives the number of accepted triangles.  0 <= k <= RR_QUERY_MULTI_MAX_K, k == 0 only with counts
+constexpr uint32_t RR_QUERY_MULTI_MAX_K = 16;
+hipError_t launch_query_multi(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, uint32_t k, rr_hit_dev* hits, uint32_t* counts,
+                              uint32_t inst0_mask, int stack, hipStream_t s);
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

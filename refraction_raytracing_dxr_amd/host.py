@@ -82,7 +82,7 @@ def make_instances(transforms=None, meshes=None, masks=None, flags=None):
 
 
 def pack_rays(origin, dir, tmin, tmax, flags=0, instance_mask=0xff):
-    """Ray records for Renderer.query_rays / trace_rays.  origin, dir: [n, 3]; tmin, tmax, flags, instance_mask: [n] or
+    """Ray records for Renderer.query_rays / query_rays_multi / trace_rays.  origin, dir: [n, 3]; tmin, tmax, flags, instance_mask: [n] or
     scalars.  numpy inputs give a RAY_DTYPE array; torch tensors give a contiguous [n, 12] int32 tensor holding the raw
     48-byte records (the float fields as their bits) on the inputs' device.  The default mask, 0xff, passes every instance."""
     if type(origin).__module__.startswith("torch"):
@@ -426,6 +426,41 @@ class Renderer:
         hits = np.zeros(len(rays), HIT_DTYPE)
         self._ck(self._L.rr_query_rays(self._h, rays.ctypes.data, len(rays), hits.ctypes.data), "rr_query_rays")
         return hits
+
+    def query_rays_multi(self, rays, k, counts=False):
+        """Multi-hit query (rr_query_rays_multi): for each ray the first k of the triangles a closest-hit query would accept, in
+        ascending (t, inst, prim) order, each with the closest-hit query's t, u, v, prim, inst and its DXR HitKind in the hit word
+        (HIT_KIND_FRONT_FACE / HIT_KIND_BACK_FACE); unused slots are miss records.  counts=True also returns the number of accepted
+        triangles per ray (k may then be 0).  Ray flags ACCEPT_FIRST_HIT and 0x8 are ignored.
+
+        rays: a RAY_DTYPE numpy array -> a HIT_DTYPE array of shape [n, k] (and uint32 [n] counts), blocking; or a contiguous
+        [n, 12] int32 or float32 torch tensor on this renderer's GPU -> a [n, k, 6] tensor of the same dtype and device (and int32
+        [n] counts), computed on the renderer's stream without waiting for it (stream order as query_rays)."""
+        k = int(k)
+        if k < 0 or k > _capi.QUERY_MAX_HITS or (k == 0 and not counts):
+            raise ValueError("query_rays_multi: need 1 <= k <= %d, or k == 0 with counts=True" % _capi.QUERY_MAX_HITS)
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("query_rays_multi: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("query_rays_multi: need a contiguous [n, 12] int32 or float32 tensor")
+            n = t.shape[0]
+            hits = torch.empty((n, k, 6), dtype=t.dtype, device=t.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=t.device) if counts else None
+            self._ck(self._L.rr_query_rays_multi_device(self._h, C.c_void_p(t.data_ptr()), n, k,
+                                                        C.c_void_p(hits.data_ptr() if k and n else None),
+                                                        C.c_void_p(cnt.data_ptr() if cnt is not None and n else None)),
+                     "rr_query_rays_multi_device")
+            return (hits, cnt) if counts else hits
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        n = len(rays)
+        hits = np.zeros((n, k), HIT_DTYPE)
+        cnt = np.zeros(n, np.uint32) if counts else None
+        self._ck(self._L.rr_query_rays_multi(self._h, rays.ctypes.data, n, k, hits.ctypes.data if k else None,
+                                             cnt.ctypes.data if counts else None), "rr_query_rays_multi")
+        return (hits, cnt) if counts else hits
 
     def env_lookup(self, dirs):
         """Miss (RayTracing.hlsl:127-137) on an [n,3] array of directions -> [n,3] texels."""

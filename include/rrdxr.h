@@ -409,6 +409,30 @@ int  rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void*
 int  rr_query_rays_multi(rr_context* ctx, const rr_ray* rays, uint32_t n, uint32_t k, rr_hit* hits, uint32_t* counts);
 int  rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, uint32_t k, void* d_hits, void* d_counts);
 
+/* ---- radiance queries: a RayGen shader of the caller's own --------------------------------------
+ * The shader's whole ray tree (RayTracing.hlsl:42-137) on caller rays instead of GenerateCameraRay's: ray i starts as RayGen's
+ * payload {colour 0, weight 1, outside = true, count 0} with origin, dir, tmin, tmax taken from rays[i] as they are (dir is
+ * NOT normalised, exactly as TraceRay takes it), CULL_BACK; every secondary ray is the shader's (tmin/tmax_secondary,
+ * max_refract, max_reflect, ior of *params; NULL = defaults).  rr_ray.flags, instance_mask and pad are ignored: the shader's
+ * TraceRay calls fix them.  Outputs, each optional, but at least one of rgba32f / rgba8 must be given:
+ *   rgba32f[i]   float4 (r, g, b, 1): the un-quantised colour, the bits RR_DISPATCH_FLOAT_OUTPUT gives for that ray
+ *   rgba8[i]     the R8G8B8A8_UNORM store of it (honours RR_DISPATCH_TONEMAP_REINHARD in params->flags)
+ *   n_rays[i]    uint32: TraceRay calls of ray i's tree, the primary included
+ * Of params->flags only RR_DISPATCH_TONEMAP_REINHARD is honoured, the others are ignored.  max_reflect > 8 is
+ * RR_ERR_UNSUPPORTED and bad bounce limits RR_ERR_INVALID_ARGUMENT, as for rr_dispatch_rays.  Errors and state as the ray
+ * queries: RR_ERR_STATE until the scene is built and after a BLAS build or update until rr_build_tlas_ex follows it; n == 0
+ * is RR_OK.  A radiance query is not a dispatch: the context's frame (rr_read_frame), the rr_get_stats counters and
+ * render_kernel[_name] and the measured kernel choices stay as the last dispatch left them.  Rays with non-finite or zero
+ * directions give an unspecified colour; the tree of every ray is bounded by max_refract and max_reflect whatever its
+ * arithmetic yields.
+ * rr_shade_rays: host arrays, blocking.  rr_shade_rays_device: rays and d_rgba32f 16-byte aligned, d_rgba8 and d_n_rays 4-byte
+ * aligned device pointers (RR_ERR_INVALID_ARGUMENT otherwise); stream-ordered on the context's stream (rr_set_stream) like
+ * rr_query_rays_device: nothing is synchronised and nothing allocated. */
+int  rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params,
+                   float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params,
+                          void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */

@@ -142,6 +142,8 @@ SYMBOLS = {
     "rr_query_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_query_rays_multi": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "rr_query_rays_multi_device": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "rr_shade_rays": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_shade_rays_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

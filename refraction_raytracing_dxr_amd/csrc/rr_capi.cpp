@@ -260,6 +260,9 @@ struct rr_context {
     DevBuf<rr_ray_dev> d_rays;
     DevBuf<rr_hit_dev> d_hits;
     DevBuf<uint32_t>   d_counts;     // rr_query_rays_multi
+    // rr_shade_rays scratch (the host variant's outputs; the frame buffers belong to the dispatches)
+    DevBuf<float4>     d_shade_f32;
+    DevBuf<uint32_t>   d_shade_rgba8, d_shade_n;
 };
 
 namespace {
@@ -2022,6 +2025,73 @@ int rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, 
     RR_HIP(launch_query_multi(sc, static_cast<const rr_ray_dev*>(d_rays), n, k, static_cast<rr_hit_dev*>(d_hits),
                               static_cast<uint32_t*>(d_counts), inst0_mask(ctx), scene_stack_need(ctx) <= 31 ? 31 : 64, ctx->stream));
     return RR_OK;
+}
+
+extern "C++" {
+namespace {
+
+// checks a radiance query's parameters and launches it: d_* are device pointers, any output may be null.  Touches nothing of
+// the context but its error text: no counters, no frame, no kernel choice.
+int shade_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, float4* d_f32,
+               uint32_t* d_rgba8, uint32_t* d_n)
+{
+    if (p.max_refract < 0 || p.max_refract > 65535 || p.max_reflect < 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "shade_rays: negative bounce limit");
+    if (p.max_reflect > 8) return fail(ctx, RR_ERR_UNSUPPORTED, "shade_rays: max_reflect > 8 (parked-ray registers)");
+    if (!(p.ior > 0.0f)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "shade_rays: ior must be > 0");
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    DispatchDev a;                  // what shade_ray and store_pixel read
+    memset(&a, 0, sizeof a);
+    a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
+    a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
+    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
+    a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
+    // the kernel of a launch of many slices: a batch of rays is that, not a frame that ends on its longest wave
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_shade_rays(sc, a, d_rays, n, d_f32, d_rgba8, d_n, v.stack, v.pend, v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+
+} // namespace
+} // extern "C++"
+
+int rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
+                  uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: need rgba32f or rgba8");
+    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: null rays");
+    const rr_dispatch_params p = params_or_default(params);
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    if (rgba32f && n > ctx->d_shade_f32.size()) if (int r = ctx->d_shade_f32.grow(ctx, n)) return r;
+    if (rgba8 && n > ctx->d_shade_rgba8.size()) if (int r = ctx->d_shade_rgba8.grow(ctx, n)) return r;
+    if (n_rays && n > ctx->d_shade_n.size()) if (int r = ctx->d_shade_n.grow(ctx, n)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_impl(ctx, "rr_shade_rays", ctx->d_rays.get(), n, p, rgba32f ? ctx->d_shade_f32.get() : nullptr,
+                           rgba8 ? ctx->d_shade_rgba8.get() : nullptr, n_rays ? ctx->d_shade_n.get() : nullptr)) return r;
+    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_shade_f32.get(), (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_shade_rgba8.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_shade_n.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
+                         void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_device: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: need d_rgba32f or d_rgba8");
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 ||
+        ((uintptr_t)d_n_rays & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers");
+    return shade_impl(ctx, "rr_shade_rays_device", static_cast<const rr_ray_dev*>(d_rays), n, params_or_default(params),
+                      static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays));
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -38,6 +38,11 @@ hipError_t launch_query_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_
 constexpr uint32_t RR_QUERY_MULTI_MAX_K = 16;
 hipError_t launch_query_multi(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, uint32_t k, rr_hit_dev* hits, uint32_t* counts,
                               uint32_t inst0_mask, int stack, hipStream_t s);
+// ---- rr_shade_rays.hip: radiance queries (rr_shade_rays[_device]): the render kernels' ray tree on caller rays.  a: the fields
+// shade_ray and store_pixel read; f32 / rgba8 / n_rays: n entries each, any of them may be null; stack, pend, stack16: the scene's
+// FusedVariant (rr_choice.h)
+hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
+                             uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

@@ -1,0 +1,103 @@
+// rr_shade_rays.hip -- radiance queries (rr_shade_rays[_device]) for gfx950: the shader's whole ray tree on caller rays.
+//
+// A RayGen shader of the caller's own: where k_render_fused starts a lane on GenerateCameraRay's ray of its pixel, a lane here
+// starts on the 48-byte record the caller wrote (origin, tmin, dir, tmax as they are; flags, mask and pad are not read), as
+// RayGen's payload {colour 0, weight 1, outside, count 0}, and from there on runs render_pixel's loop (rr_render_common.h:
+// trace_scene, then shade_ray -- ClosestHit / Miss, the refracted child followed, the reflected one parked
+// in registers).  The arithmetic is that shared device code and nothing else, so the colour of a ray has the bits a dispatch
+// gives the pixel with that primary ray.  One lane per ray, a wave is 64 consecutive rays: what coherence the batch has is the
+// caller's order (DESIGN 5.5 has the cost of the orders measured).
+#include <hip/hip_runtime.h>
+#include "rr_render_common.h"
+
+namespace rr {
+
+// waves per SIMD an instantiation is built for: those of the k_render_fused build with the same stack (its LDS footprint is the
+// same, 4 * STACK * 64 * sizeof(E) per workgroup, and so is what stays live across a traversal)
+template <int STACK, bool TLAS, class E> struct ShadeWaves {
+    static constexpr int value = TLAS ? (sizeof(E) == 2 ? (STACK <= 30 ? 7 : 5) : RR_TLAS_WAVES_PER_SIMD(STACK))
+                                      : (sizeof(E) == 2 ? 8 : RR_FUSED_WAVES_PER_SIMD(STACK));
+};
+
+// render_pixel's loop behind its RayGen: the tree of primary ray r, depth-first; returns the sum of its leaves in the recursion's
+// order.  Bounded whatever the arithmetic yields (NaN directions included): a ray's count grows by one per level and ends the
+// branch at max_refract, and a ray is parked only while count < max_reflect, one per level, so never more than max_reflect <=
+// PEND wait at once; a walk visits each node of a finite tree at most once.
+template <bool TLAS, class E, class PK>
+__device__ __forceinline__ f3 ray_tree(const SceneDev& sc, const DispatchDev& a, RayState r, E* stk, PK& park, LaneStats& st)
+{
+    f3 acc = mk3(0.0f, 0.0f, 0.0f);
+    int np = 0;
+    for (;;) {
+        HitRec h;
+        trace_scene<false, TLAS, E, GlobalNodes>(sc, r.O, r.D, r.tmin, r.tmax, r.outside ? CULL_BACK : CULL_FRONT, h, stk, st.cnt,
+                                                 Diag{ nullptr }, GlobalNodes{});
+        ++st.rays;
+        if (!shade_ray<false, TLAS>(sc, a, h, r, acc, np, park, st)) break;
+    }
+    return acc;
+}
+
+// a: only what shade_ray and store_pixel read (bounce limits, ior, secondary interval, tonemap; compact_out = 0).
+// Each output is written only if its pointer is given (wave-uniform branches on kernel arguments).
+template <int STACK, int PEND, bool TLAS, class E>
+__global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_shade_rays(SceneDev sc, DispatchDev a, const rr_ray_dev* rays, uint32_t n,
+                                                                                         float4* out_f32, uint32_t* out_rgba8, uint32_t* out_n)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;      // wave: uniform, so that everything derived from it is scalar
+    E* stk = reinterpret_cast<E*>(lds) + wave * (STACK * 64) + lane;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4* q = reinterpret_cast<const uint4*>(rays + i);
+    const uint4 o = q[0], d = q[1];                             // (q[2]: flags, instance_mask, pad -- the shader's TraceRay calls fix them)
+    RayState r;
+    r.O = mk3(__uint_as_float(o.x), __uint_as_float(o.y), __uint_as_float(o.z));
+    r.D = mk3(__uint_as_float(d.x), __uint_as_float(d.y), __uint_as_float(d.z));
+    r.tmin = __uint_as_float(o.w); r.tmax = __uint_as_float(d.w);
+    r.w = 1.0f; r.count = 0; r.outside = true;                  // RayGen's payload (RayTracing.hlsl:57-60)
+    LaneStats st;
+    RegPark<PEND> park;
+    const f3 acc = ray_tree<TLAS, E>(sc, a, r, stk, park, st);
+    if (out_f32) out_f32[i] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+    if (out_rgba8) store_pixel(a, out_rgba8, nullptr, i, acc);
+    if (out_n) out_n[i] = st.rays;
+}
+
+template <int STACK, int PEND, bool TLAS, class E>
+static hipError_t launch_shade(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
+                               uint32_t* n_rays, hipStream_t s)
+{
+    const size_t lds = (size_t)4 * STACK * 64 * sizeof(E);
+    hipLaunchKernelGGL((k_shade_rays<STACK, PEND, TLAS, E>), dim3((n + 255u) / 256u), dim3(256), lds, s, sc, a, rays, n, f32, rgba8, n_rays);
+    return hipGetLastError();
+}
+
+template <int STACK, int PEND>
+static hipError_t launch_shade_sp(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
+                                  uint32_t* n_rays, hipStream_t s)
+{
+    if (!sc.single_identity) return launch_shade<STACK, PEND, true, uint32_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    return launch_shade<STACK, PEND, false, uint32_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
+}
+
+// stack, pend, stack16: a FusedVariant (rr_choice.h) of the scene -- the ladder of launch_render_fused without its 22-entry
+// rung (seven waves per SIMD against six: DESIGN 5.5)
+hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
+                             uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    if (stack > 64 || pend > 8) return hipErrorInvalidValue;
+    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 30) return launch_shade<30, 2, true, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 39) return launch_shade<39, 2, true, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack16 && sc.single_identity && stack <= 39)
+        return pend <= 2 ? launch_shade<39, 2, false, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s)
+                         : launch_shade<39, 8, false, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack <= 19 && pend <= 2) return launch_shade_sp<19, 2>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack <= 26 && pend <= 2) return launch_shade_sp<26, 2>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack <= 31) return pend <= 2 ? launch_shade_sp<31, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<31, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    if (stack <= 39) return pend <= 2 ? launch_shade_sp<39, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<39, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    return pend <= 2 ? launch_shade_sp<64, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<64, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
+}
+
+} // namespace rr

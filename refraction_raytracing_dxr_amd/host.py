@@ -462,6 +462,46 @@ class Renderer:
                                              cnt.ctypes.data if counts else None), "rr_query_rays_multi")
         return (hits, cnt) if counts else hits
 
+    def shade_rays(self, rays, params=None, rgba8=False, ray_counts=False):
+        """Radiance query (rr_shade_rays): the shader's whole ray tree -- RayGen's payload, ClosestHit's refraction / reflection tree,
+        Miss's env-map lookup -- on caller rays instead of the pinhole camera's, i.e. a RayGen shader of your own.  Ray i starts
+        with origin, dir (not normalised), tmin and tmax of its record (pack_rays; flags and instance_mask are ignored), outside the
+        glass with weight 1; params (default_params()) gives the bounce limits, ior, the secondary rays' interval and, for the RGBA8
+        output, DISPATCH_TONEMAP_REINHARD.  The colour of a ray has the bits dispatch_rays gives a pixel with that primary ray.
+        Not a dispatch: read_frame and stats() stay as the last dispatch left them.
+
+        rays: a RAY_DTYPE numpy array -> float32 [n, 4] (r, g, b, 1), blocking; or a contiguous [n, 12] int32 or float32 torch
+        tensor on this renderer's GPU -> a new float32 [n, 4] tensor on that device, computed on the renderer's stream without
+        waiting for it (stream order as query_rays).  rgba8=True adds the R8G8B8A8_UNORM store (uint8 [n, 4]), ray_counts=True the
+        TraceRay calls of each ray's tree, the primary included (uint32 [n]; torch: int32 [n]); the result is then a tuple in
+        that order."""
+        p = params if params is not None else default_params()
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("shade_rays: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("shade_rays: need a contiguous [n, 12] int32 or float32 tensor")
+            n = t.shape[0]
+            f32 = torch.empty((n, 4), dtype=torch.float32, device=t.device)
+            u8 = torch.empty((n, 4), dtype=torch.uint8, device=t.device) if rgba8 else None
+            cnt = torch.empty((n,), dtype=torch.int32, device=t.device) if ray_counts else None
+            self._ck(self._L.rr_shade_rays_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p),
+                                                  C.c_void_p(f32.data_ptr() if n else None),
+                                                  C.c_void_p(u8.data_ptr() if u8 is not None and n else None),
+                                                  C.c_void_p(cnt.data_ptr() if cnt is not None and n else None)), "rr_shade_rays_device")
+        else:
+            rays = np.ascontiguousarray(rays, RAY_DTYPE)
+            n = len(rays)
+            f32 = np.zeros((n, 4), np.float32)
+            u8 = np.zeros((n, 4), np.uint8) if rgba8 else None
+            cnt = np.zeros(n, np.uint32) if ray_counts else None
+            self._ck(self._L.rr_shade_rays(self._h, rays.ctypes.data, n, C.byref(p), f32.ctypes.data,
+                                           u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_shade_rays")
+        out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
+        return out if len(out) > 1 else f32
+
     def env_lookup(self, dirs):
         """Miss (RayTracing.hlsl:127-137) on an [n,3] array of directions -> [n,3] texels."""
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)

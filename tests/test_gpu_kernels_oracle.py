@@ -74,7 +74,8 @@ class Scene:
         self.single = instances is None
         lo, hi = [], []
         for k in range(1 if instances is None else len(instances)):
-            P = meshes[0 if instances is None else int(instances["blas"][k])][0]["position"].astype(np.float64)
+            V, I = meshes[0 if instances is None else int(instances["blas"][k])]
+            P = V["position"][np.asarray(I, np.int64)].astype(np.float64)      # the referenced vertices: what the BLAS bounds
             if instances is not None:
                 T = instances["transform"][k].reshape(3, 4).astype(np.float64)
                 P = P @ T[:, :3].T + T[:, 3]

@@ -1,0 +1,189 @@
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_env_lookup.
+// A host variant stages its arrays through the context's scratch around the launch its device variant makes.
+#include "rr_context.h"
+
+namespace {
+// trace_rays scratch for n rays
+int ensure_rays(rr_context* ctx, size_t n)
+{
+    if (n > ctx->d_hits.size()) if (int r = ctx->d_hits.grow(ctx, n)) return r;
+    return n > ctx->d_rays.size() ? ctx->d_rays.grow(ctx, n) : RR_OK;
+}
+
+// stack entries of the query kernels' instantiation
+int query_stack(const rr_context* ctx) { return scene_stack_need(ctx) <= 31 ? 31 : 64; }
+
+// the launches of rr_query_rays* and rr_query_rays_multi*: d_* are device pointers
+int query_impl(rr_context* ctx, const rr_ray_dev* d_rays, uint32_t n, rr_hit_dev* d_hits)
+{
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(launch_query_rays(sc, d_rays, n, d_hits, inst0_mask(ctx), query_stack(ctx), ctx->stream));
+    return RR_OK;
+}
+
+int query_multi_impl(rr_context* ctx, const rr_ray_dev* d_rays, uint32_t n, uint32_t k, rr_hit_dev* d_hits, uint32_t* d_counts)
+{
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(launch_query_multi(sc, d_rays, n, k, d_hits, d_counts, inst0_mask(ctx), query_stack(ctx), ctx->stream));
+    return RR_OK;
+}
+
+// a radiance query's outputs (device pointers, any may be null)
+struct ShadeOut { float4* f32; uint32_t* rgba8; uint32_t* n_rays; };
+
+// checks a radiance query's parameters and launches it: d_rays is a device pointer.  Touches nothing of
+// the context but its error text: no counters, no frame, no kernel choice.
+int shade_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+{
+    if (int r = check_shading_params(ctx, "shade_rays", p)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    DispatchDev a;                  // what shade_ray and store_pixel read
+    memset(&a, 0, sizeof a);
+    a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
+    a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
+    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
+    a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
+    // the kernel of a launch of many slices: a batch of rays is that, not a frame that ends on its longest wave
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_shade_rays(sc, a, d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+} // namespace
+
+extern "C" {
+int rr_trace_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_trace_rays: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!rays || !hits) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_trace_rays: null arrays");
+    if (int r = ensure_rays(ctx, n)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP(hipMemsetAsync(&ctx->d_cnt.get()->error, 0, 4, ctx->stream));
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(launch_trace_rays(sc, ctx->d_rays.get(), n, ctx->d_hits.get(), &ctx->d_cnt.get()->error, query_stack(ctx), ctx->stream));
+    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    uint32_t err = 0;
+    RR_HIP(hipMemcpyAsync(&err, &ctx->d_cnt.get()->error, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    if (err) return fail(ctx, RR_ERR_TRAVERSAL_OVERFLOW, "traversal stack overflow");
+    return RR_OK;
+}
+
+int rr_query_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, rr_hit* hits)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!rays || !hits) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays: null arrays");
+    if (int r = ensure_rays(ctx, n)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = query_impl(ctx, ctx->d_rays.get(), n, ctx->d_hits.get())) return r;
+    RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), (size_t)n * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_query_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, void* d_hits)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_device: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!d_rays || !d_hits || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_device: need a 16-byte aligned ray and a 4-byte aligned hit pointer");
+    return query_impl(ctx, static_cast<const rr_ray_dev*>(d_rays), n, static_cast<rr_hit_dev*>(d_hits));
+}
+
+int rr_query_rays_multi(rr_context* ctx, const rr_ray* rays, uint32_t n, uint32_t k, rr_hit* hits, uint32_t* counts)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_multi: build the BLAS and TLAS first");
+    if (k > RR_QUERY_MAX_HITS || (k == 0 && !counts))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi: need 1 <= k <= 16, or k == 0 with counts");
+    if (n == 0) return RR_OK;
+    if (!rays || (k && !hits)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi: null arrays");
+    const size_t nk = (size_t)n * k;
+    if (int r = ensure_rays(ctx, n)) return r;
+    if (nk > ctx->d_hits.size()) if (int r = ctx->d_hits.grow(ctx, nk)) return r;
+    if (counts && n > ctx->d_counts.size()) if (int r = ctx->d_counts.grow(ctx, n)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = query_multi_impl(ctx, ctx->d_rays.get(), n, k, ctx->d_hits.get(), counts ? ctx->d_counts.get() : nullptr)) return r;
+    if (k) RR_HIP(hipMemcpyAsync(hits, ctx->d_hits.get(), nk * sizeof(rr_hit_dev), hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) RR_HIP(hipMemcpyAsync(counts, ctx->d_counts.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, uint32_t k, void* d_hits, void* d_counts)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_query_rays_multi_device: build the BLAS and TLAS first");
+    if (k > RR_QUERY_MAX_HITS || (k == 0 && !d_counts))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_query_rays_multi_device: need 1 <= k <= 16, or k == 0 with counts");
+    if (n == 0) return RR_OK;
+    if (!d_rays || (k && !d_hits) || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_hits & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_query_rays_multi_device: need a 16-byte aligned ray and 4-byte aligned hit and count pointers");
+    return query_multi_impl(ctx, static_cast<const rr_ray_dev*>(d_rays), n, k, static_cast<rr_hit_dev*>(d_hits), static_cast<uint32_t*>(d_counts));
+}
+
+int rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
+                  uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: need rgba32f or rgba8");
+    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: null rays");
+    const rr_dispatch_params p = params_or_default(params);
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    if (rgba32f && n > ctx->d_shade_f32.size()) if (int r = ctx->d_shade_f32.grow(ctx, n)) return r;
+    if (rgba8 && n > ctx->d_shade_rgba8.size()) if (int r = ctx->d_shade_rgba8.grow(ctx, n)) return r;
+    if (n_rays && n > ctx->d_shade_n.size()) if (int r = ctx->d_shade_n.grow(ctx, n)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_impl(ctx, "rr_shade_rays", ctx->d_rays.get(), n, p, { rgba32f ? ctx->d_shade_f32.get() : nullptr,
+                           rgba8 ? ctx->d_shade_rgba8.get() : nullptr, n_rays ? ctx->d_shade_n.get() : nullptr })) return r;
+    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_shade_f32.get(), (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_shade_rgba8.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_shade_n.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
+                         void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_device: build the BLAS and TLAS first");
+    if (n == 0) return RR_OK;
+    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: need d_rgba32f or d_rgba8");
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 ||
+        ((uintptr_t)d_n_rays & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers");
+    return shade_impl(ctx, "rr_shade_rays_device", static_cast<const rr_ray_dev*>(d_rays), n, params_or_default(params),
+                      { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)
+{
+    if (int r = use_device(ctx)) return r;
+    if ((!dirs || !rgb) && n) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_env_lookup: null buffers");
+    if (n == 0) return RR_OK;
+    DevBuf<float> d_in, d_out;
+    RR_HIP(d_in.alloc((size_t)n * 3));
+    RR_HIP_MSG(d_out.alloc((size_t)n * 3), "rr_env_lookup");
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    RR_HIP_MSG(hipMemcpyAsync(d_in.get(), dirs, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(launch_env_lookup(sc, d_in.get(), n, d_out.get(), ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(hipMemcpyAsync(rgb, d_out.get(), (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream), "rr_env_lookup");
+    RR_HIP_MSG(hipStreamSynchronize(ctx->stream), "rr_env_lookup");
+    return RR_OK;
+}
+} // extern "C"

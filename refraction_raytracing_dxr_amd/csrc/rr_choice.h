@@ -6,8 +6,8 @@
 // shape only if it took under 98 % of the default's time over both.  rr_build_tlas starts afresh; a shape (choice_key: frame
 // size, bounce limits, launch depth 1 / 2 / 3-7 / 8-23 / 24-47 / 48+) keeps its choice -- a class remembers its four most
 // recent shapes -- until its rectangle share doubles or halves.  Classes: two-level scenes (fused / k_stream_*), many slices of
-// the reference's scene (fused / k_render_lds), one or two slices (fused / k_render_paths).  rr_capi.cpp gathers the facts,
-// times the candidates and launches; every rule is stated here.
+// the reference's scene (fused / k_render_lds), one or two slices (fused / k_render_paths).  rr_capi_dispatch.cpp gathers the facts
+// (pick_launch), times the candidates and launches; every rule is stated here.
 #pragma once
 #include <cstdint>
 #include "../../include/rrdxr.h"

@@ -433,6 +433,36 @@ int  rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dis
 int  rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params,
                           void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
+/* ---- supersampled frames: n_samples primary rays per pixel, resolved in the kernel --------------
+ * Each pixel of a width x height frame takes n_samples primary rays through n_samples sub-pixel positions, every one with the
+ * shader's whole ray tree, and their colours are averaged into one per pixel.  offsets: host array of 2 * n_samples floats
+ * (x0, y0, x1, y1, ...) in pixel units inside the pixel -- (0.5, 0.5) is the centre -- every value finite and in [0, 1], with
+ * 1 <= n_samples <= RR_MAX_SAMPLES; NULL: the built-in pattern of rr_host_sample_pattern(n_samples).  Sample (ox, oy) of
+ * pixel (x, y) is GenerateCameraRay (RayTracing.hlsl:27-40) with its literal 0.5 replaced:
+ *   sx = ((float)x + ox) / (float)width * 2 - 1,  sy = -(((float)y + oy) / (float)height * 2 - 1)
+ * from camera_loc over params' primary interval with RayGen's payload: the rays of rr_host_camera_rays.  With c_s the
+ * colour rr_shade_rays gives sample s's ray, a channel resolves in fp32 as ((c_0 + c_1) + ... + c_(S-1)) / (float)S.
+ * Outputs, row-major width * height, each optional, but at least one of rgba32f / rgba8 must be given:
+ *   rgba32f[i]   float4 (resolved r, g, b, 1)
+ *   rgba8[i]     the R8G8B8A8_UNORM store of it (honours RR_DISPATCH_TONEMAP_REINHARD)
+ *   n_rays[i]    uint32: TraceRay calls of all the trees of pixel i
+ * Of params->flags only RR_DISPATCH_TONEMAP_REINHARD and RR_DISPATCH_DEBUG_NO_CULL are read (blocks of 8 x 8 pixels outside
+ * rr_host_screen_rect of the scene are shaded as one Miss per sample without TraceRay; the flag traces them, with the same
+ * output).  constants, params and offsets are host pointers in both variants; width and height are 1..32768.  Like a radiance
+ * query this is not a dispatch: the context's frame, the rr_get_stats counters, render_kernel[_name] and the measured kernel
+ * choices stay as the last dispatch left them, and rr_set_tile_partition is ignored (the whole frame is rendered).  Errors and
+ * state as rr_shade_rays[_device].
+ * rr_render_samples: host arrays, blocking.  rr_render_samples_device: d_rgba32f 16-byte, d_rgba8 and d_n_rays 4-byte aligned
+ * device pointers (RR_ERR_INVALID_ARGUMENT otherwise); stream-ordered on the context's stream, nothing is synchronised and
+ * nothing allocated. */
+#define RR_MAX_SAMPLES 64
+int  rr_render_samples(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                       const rr_dispatch_params* params, const float* offsets, uint32_t n_samples,
+                       float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                              const rr_dispatch_params* params, const float* offsets, uint32_t n_samples,
+                              void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */
@@ -473,6 +503,14 @@ uint32_t rr_host_mesh_tiles_of_rank(const rr_mesh_partition* part, uint32_t rank
  * fov_y = float(52.0/180.0*3.1415), aspect = 1.333f, zn = 1, zf = 125; frame k uses angle 0.01*(k+1). */
 int  rr_host_camera_orbit(float angle, float fov_y, float aspect, float zn, float zf,
                           rr_scene_constants* out);
+/* D3D's standard multisample patterns for n_samples = 1, 2, 4, 8, 16 (RR_ERR_INVALID_ARGUMENT otherwise): 2 * n_samples floats
+ * x0, y0, x1, y1, ..., sample i at 0.5 + k / 16 per axis, k in -8..7.  What rr_render_samples uses for offsets == NULL. */
+int  rr_host_sample_pattern(uint32_t n_samples, float* offsets);
+/* GenerateCameraRay for every pixel of a width x height frame (row-major) with its literal 0.5 replaced by (ox, oy), both in
+ * [0, 1]: the primary rays rr_render_samples takes for that offset -- with (0.5, 0.5) those of a dispatch -- as rr_ray records
+ * over [tmin, tmax] with flags 0 and instance_mask 0xff.  width, height: 1..32768. */
+int  rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,
+                         rr_ray* rays);
 /* Mesh::load, Mesh.cpp:6-37.  Arrays are malloc'ed, release with rr_host_free.  A file that cannot
  * be opened returns RR_ERR_IO (Mesh::load returns false). */
 int  rr_host_mesh_load_obj(const char* filename, rr_vertex** verts, uint32_t* n_verts,

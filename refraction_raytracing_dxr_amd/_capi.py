@@ -26,6 +26,7 @@ RAY_FLAG_ACCEPT_FIRST_HIT = 0x4          # RR_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_
 RAY_FLAG_SKIP_CLOSEST_HIT_SHADER = 0x8   # accepted, no effect
 RAY_FLAG_CULL_BACK = 0x10
 RAY_FLAG_CULL_FRONT = 0x20
+MAX_SAMPLES = 64                         # RR_MAX_SAMPLES: most samples per pixel of render_samples
 QUERY_MAX_HITS = 16                      # RR_QUERY_MAX_HITS: largest k of query_rays_multi
 HIT_KIND_FRONT_FACE = 0xFE               # RR_HIT_KIND_TRIANGLE_FRONT_FACE (query_rays_multi's hit word)
 HIT_KIND_BACK_FACE = 0xFF
@@ -144,6 +145,9 @@ SYMBOLS = {
     "rr_query_rays_multi_device": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "rr_shade_rays": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
     "rr_shade_rays_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_render_samples": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_render_samples_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P,
+                                           _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -158,6 +162,8 @@ SYMBOLS = {
     "rr_download_qnodes": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rr_default_dispatch_params": (None, [C.POINTER(DispatchParams)]),
     "rr_host_camera_orbit": (C.c_int, [C.c_float] * 5 + [C.POINTER(SceneConstants)]),
+    "rr_host_sample_pattern": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "rr_host_camera_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "rr_host_screen_rect": (C.c_int, [C.POINTER(C.c_float), C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rr_host_mesh_tile_home": (C.c_int, [C.POINTER(MeshPartition), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rr_host_mesh_tiles_of_rank": (C.c_uint32, [C.POINTER(MeshPartition), C.c_uint32]),

@@ -75,6 +75,20 @@ int drawFrame()
     return RR_OK;
 }
 
+int drawFrameSamples(int spp)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameSamples: spp must be 1, 2, 4, 8 or 16");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    if ((rc = rr_render_samples(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)spp, nullptr,
+                                g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_samples");
+    return RR_OK;
+}
+
 // `for (;;) drawFrame();` (WinMain.cpp:49-59) without the per-frame fence wait and read-back: n_frames of the
 // orbit, frames_per_dispatch depth slices per launch, in_flight launches overlapping.  The last frame lands in
 // backBuffer().  The reference notes the missing overlap itself (RefractionDemo.cpp:519-521).

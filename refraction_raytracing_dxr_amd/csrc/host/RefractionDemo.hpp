@@ -27,6 +27,9 @@ struct Options {
 
 int initialize(const Options& opt);       // RefractionDemo.cpp:513-553; returns rr_status
 int drawFrame();                          // RefractionDemo.cpp:557-612; returns rr_status
+// drawFrame with spp primary rays per pixel (rr_render_samples, the built-in pattern of 1, 2, 4, 8 or 16 samples): the orbit
+// advances as in drawFrame and the resolved frame lands in backBuffer()
+int drawFrameSamples(int spp);
 // the frame loop as one call: no per-frame wait or read-back, `in_flight` launches overlapping (1..4)
 int pump(int n_frames, int frames_per_dispatch, int in_flight, rr_stats* stats);
 // the frame loop with every frame copied to host memory while the next ones render; frames: n_frames*w*h*4 bytes

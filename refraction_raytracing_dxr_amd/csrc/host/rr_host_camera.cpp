@@ -133,3 +133,44 @@ extern "C" int rr_host_camera_orbit(float angle, float fov_y, float aspect, floa
     std::memcpy(out->camera_loc, loc, 16);
     return RR_OK;
 }
+
+// D3D's standard multisample patterns: sample i at 0.5 + k / 16 per axis
+extern "C" int rr_host_sample_pattern(uint32_t n_samples, float* offsets)
+{
+    static const int8_t p1[] = { 0, 0 };
+    static const int8_t p2[] = { 4, 4, -4, -4 };
+    static const int8_t p4[] = { -2, -6, 6, -2, -6, 2, 2, 6 };
+    static const int8_t p8[] = { 1, -3, -1, 3, 5, 1, -3, -5, -5, 5, -7, -1, 3, 7, 7, -7 };
+    static const int8_t p16[] = { 1, 1, -1, -3, -3, 2, 4, -1, -5, -2, 2, 5, 5, 3, 3, -5, -2, 6, 0, -7, -4, -6, -6, 4, -8, 0, 7, -4, 6, 7, -7, -8 };
+    const int8_t* k = n_samples == 1 ? p1 : n_samples == 2 ? p2 : n_samples == 4 ? p4 : n_samples == 8 ? p8 : n_samples == 16 ? p16 : nullptr;
+    if (!k || !offsets) return RR_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < 2 * n_samples; ++i) offsets[i] = 0.5f + (float)k[i] / 16.0f;
+    return RR_OK;
+}
+
+// GenerateCameraRay (RayTracing.hlsl:27-40) for every pixel of a frame, with the literal 0.5 replaced by (ox, oy): the
+// arithmetic of k_render_samples' sample ray (screen_coord and camera_ray_dir of rr_device.h), operation by operation
+extern "C" int rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,
+                                   rr_ray* rays)
+{
+    if (!c || !rays || width == 0 || height == 0 || width > 32768u || height > 32768u) return RR_ERR_INVALID_ARGUMENT;
+    if (!(ox >= 0.0f && ox <= 1.0f && oy >= 0.0f && oy <= 1.0f)) return RR_ERR_INVALID_ARGUMENT;        // (NaN fails every comparison)
+    const float* M = c->proj_inv;
+    for (uint32_t y = 0; y < height; ++y) {
+        const float py = (float)y + oy;
+        const float sy = -(py / (float)height * 2.0f - 1.0f);
+        for (uint32_t x = 0; x < width; ++x) {
+            const float px = (float)x + ox;
+            const float sx = px / (float)width * 2.0f - 1.0f;
+            const Vec3 d = normalized(Vec3{ (sx * M[0] + sy * M[1]) + M[3], (sx * M[4] + sy * M[5]) + M[7], (sx * M[8] + sy * M[9]) + M[11] });
+            rr_ray& r = rays[(size_t)y * width + x];
+            std::memset(&r, 0, sizeof r);
+            r.origin[0] = c->camera_loc[0]; r.origin[1] = c->camera_loc[1]; r.origin[2] = c->camera_loc[2];
+            r.tmin = tmin;
+            r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
+            r.tmax = tmax;
+            r.instance_mask = 0xffu;
+        }
+    }
+    return RR_OK;
+}

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -30,6 +30,18 @@ int query_multi_impl(rr_context* ctx, const rr_ray_dev* d_rays, uint32_t n, uint
     return RR_OK;
 }
 
+// the fields of a radiance query's or a supersampled frame's DispatchDev that shade_ray and store_pixel read
+DispatchDev shading_args(const rr_dispatch_params& p)
+{
+    DispatchDev a;
+    memset(&a, 0, sizeof a);
+    a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
+    a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
+    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
+    a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
+    return a;
+}
+
 // a radiance query's outputs (device pointers, any may be null)
 struct ShadeOut { float4* f32; uint32_t* rgba8; uint32_t* n_rays; };
 
@@ -40,16 +52,66 @@ int shade_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint3
     if (int r = check_shading_params(ctx, "shade_rays", p)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
-    DispatchDev a;                  // what shade_ray and store_pixel read
-    memset(&a, 0, sizeof a);
-    a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
-    a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
-    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
-    a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
+    const DispatchDev a = shading_args(p);
     // the kernel of a launch of many slices: a batch of rays is that, not a frame that ends on its longest wave
     const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
     if (hipError_t e = launch_shade_rays(sc, a, d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+
+// a supersampled frame as its two entry points take it (pointers of the caller's: host memory)
+struct SamplesReq {
+    const char* who;
+    uint32_t width, height;
+    const rr_scene_constants* constants; const rr_dispatch_params* params; const float* offsets; uint32_t n_samples;
+};
+
+// what both variants of rr_render_samples refuse before they look at their outputs' memory or allocate anything (bounce limits
+// and ior included); fills the offsets
+int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, SampleOffsets& off)
+{
+    const std::string w(q.who);
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (w + ": build the BLAS and TLAS first").c_str());
+    if (!q.constants) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null constants").c_str());
+    if (q.width == 0 || q.height == 0 || q.width > 32768u || q.height > 32768u)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": width and height must be 1..32768").c_str());
+    if (!have_colour) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need rgba32f or rgba8").c_str());
+    if (int r = check_shading_params(ctx, "render_samples", params_or_default(q.params))) return r;
+    memset(&off, 0, sizeof off);
+    if (!q.offsets) {
+        if (rr_host_sample_pattern(q.n_samples, off.v)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": the built-in patterns have 1, 2, 4, 8 or 16 samples").c_str());
+        return RR_OK;
+    }
+    if (q.n_samples == 0 || q.n_samples > RR_MAX_SAMPLES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need 1 <= n_samples <= 64").c_str());
+    for (uint32_t i = 0; i < 2 * q.n_samples; ++i) {
+        if (!(q.offsets[i] >= 0.0f && q.offsets[i] <= 1.0f))        // (NaN fails both comparisons)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": offsets must lie in [0, 1]").c_str());
+        off.v[i] = q.offsets[i];
+    }
+    return RR_OK;
+}
+
+// launches a checked supersampled frame: out holds device pointers.  Like shade_impl it touches nothing of the context but its
+// error text, and it allocates and copies nothing: constants and offsets travel as kernel arguments.
+int samples_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+{
+    const rr_dispatch_params p = params_or_default(q.params);
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    DispatchDev a = shading_args(p);
+    a.W = q.width; a.H = q.height;
+    a.tmin_p = p.tmin_primary; a.tmax_p = p.tmax_primary;
+    uint32_t hr[4];
+    (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants, 1, q.width, q.height, hr);
+    a.hx0 = hr[0]; a.hy0 = hr[1]; a.hx1 = hr[2]; a.hy1 = hr[3];
+    CamDev cam;
+    memcpy(cam.M, q.constants->proj_inv, sizeof cam.M);
+    memcpy(cam.cam, q.constants->camera_loc, sizeof cam.cam);
+    // the kernel of a launch of many slices, as a radiance query's: S trees per lane, not a frame that ends on its longest wave
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_render_samples(sc, a, cam, off, q.n_samples, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.who, e);
     return RR_OK;
 }
 } // namespace
@@ -168,6 +230,38 @@ int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const 
                     "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers");
     return shade_impl(ctx, "rr_shade_rays_device", static_cast<const rr_ray_dev*>(d_rays), n, params_or_default(params),
                       { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_samples(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                      const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const SamplesReq q = { "rr_render_samples", width, height, constants, params, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
+    const size_t n = (size_t)width * height;
+    if (rgba32f && n > ctx->d_samples_f32.size()) if (int r = ctx->d_samples_f32.grow(ctx, n)) return r;
+    if (rgba8 && n > ctx->d_samples_rgba8.size()) if (int r = ctx->d_samples_rgba8.grow(ctx, n)) return r;
+    if (n_rays && n > ctx->d_samples_n.size()) if (int r = ctx->d_samples_n.grow(ctx, n)) return r;
+    if (int r = samples_impl(ctx, q, off, { rgba32f ? ctx->d_samples_f32.get() : nullptr, rgba8 ? ctx->d_samples_rgba8.get() : nullptr,
+                                            n_rays ? ctx->d_samples_n.get() : nullptr })) return r;
+    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_samples_f32.get(), n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_samples_rgba8.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_samples_n.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+int rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                             const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const SamplesReq q = { "rr_render_samples_device", width, height, constants, params, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
+    if (((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 || ((uintptr_t)d_n_rays & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_samples_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers");
+    return samples_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

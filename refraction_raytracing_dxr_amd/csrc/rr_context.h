@@ -227,6 +227,9 @@ struct rr_context {
     // rr_shade_rays scratch (the host variant's outputs; the frame buffers belong to the dispatches)
     DevBuf<float4>     d_shade_f32;
     DevBuf<uint32_t>   d_shade_rgba8, d_shade_n;
+    // rr_render_samples scratch (the host variant's outputs)
+    DevBuf<float4>     d_samples_f32;
+    DevBuf<uint32_t>   d_samples_rgba8, d_samples_n;
 };
 
 namespace rr {

@@ -43,6 +43,14 @@ hipError_t launch_query_multi(const SceneDev& sc, const rr_ray_dev* rays, uint32
 // FusedVariant (rr_choice.h)
 hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
                              uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+// ---- rr_render_samples.hip: supersampled frames (rr_render_samples[_device]): n_samples primary rays per pixel of an a.W x a.H
+// frame through the sub-pixel positions off (pixel units), each with the ray tree of a radiance query, averaged in the kernel.
+// a: the fields shade_ray and store_pixel read, W, H, tmin_p, tmax_p and the scene's screen rectangle hx0..hy1; f32 / rgba8 /
+// n_rays: W * H rasters, any of them may be null; stack, pend, stack16: the scene's FusedVariant.  The offsets travel as a
+// kernel argument: 512 bytes
+struct SampleOffsets { static constexpr uint32_t MAX = 64; float v[2 * MAX]; };     // x0, y0, x1, y1, ...
+hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_samples,
+                                 float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

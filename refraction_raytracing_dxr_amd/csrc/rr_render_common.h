@@ -1,4 +1,5 @@
-// rr_render_common.h -- device code shared by the render kernels (rr_render.hip, rr_render_stream.hip): a pixel's ray tree as the lanes walk it (RayGen, ClosestHit / Miss, the parked
+// rr_render_common.h -- device code shared by the render kernels (rr_render.hip, rr_render_stream.hip, rr_shade_rays.hip,
+// rr_render_samples.hip): a pixel's ray tree as the lanes walk it (RayGen, ClosestHit / Miss, the parked
 // reflected rays), the frame store, the counters, and the numbering of a dispatch's 8x8 pixel blocks.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -206,6 +207,33 @@ __device__ __forceinline__ f3 render_pixel(const SceneDev& sc, const DispatchDev
         if (STATS && first_active_lane()) ++st.passes;
         if (DIAG) diag_trip(dg, 2);
         if (!shade_ray<STATS, TLAS>(sc, a, h, r, acc, np, park, st)) break;
+    }
+    return acc;
+}
+
+// k_shade_rays and k_render_samples (a ray tree per lane behind a RayGen of their own): waves per SIMD an instantiation is built
+// for, those of the k_render_fused build with the same stack (its LDS footprint is the same, 4 * STACK * 64 * sizeof(E) per
+// workgroup, and so is what stays live across a traversal)
+template <int STACK, bool TLAS, class E> struct ShadeWaves {
+    static constexpr int value = TLAS ? (sizeof(E) == 2 ? (STACK <= 30 ? 7 : 5) : RR_TLAS_WAVES_PER_SIMD(STACK))
+                                      : (sizeof(E) == 2 ? 8 : RR_FUSED_WAVES_PER_SIMD(STACK));
+};
+
+// render_pixel's loop behind its RayGen: the tree of primary ray r, depth-first; returns the sum of its leaves in the recursion's
+// order.  Bounded whatever the arithmetic yields (NaN directions included): a ray's count grows by one per level and ends the
+// branch at max_refract, and a ray is parked only while count < max_reflect, one per level, so never more than max_reflect <=
+// PEND wait at once; a walk visits each node of a finite tree at most once.
+template <bool TLAS, class E, class PK>
+__device__ __forceinline__ f3 ray_tree(const SceneDev& sc, const DispatchDev& a, RayState r, E* stk, PK& park, LaneStats& st)
+{
+    f3 acc = mk3(0.0f, 0.0f, 0.0f);
+    int np = 0;
+    for (;;) {
+        HitRec h;
+        trace_scene<false, TLAS, E, GlobalNodes>(sc, r.O, r.D, r.tmin, r.tmax, r.outside ? CULL_BACK : CULL_FRONT, h, stk, st.cnt,
+                                                 Diag{ nullptr }, GlobalNodes{});
+        ++st.rays;
+        if (!shade_ray<false, TLAS>(sc, a, h, r, acc, np, park, st)) break;
     }
     return acc;
 }

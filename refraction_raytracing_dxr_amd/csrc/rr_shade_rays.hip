@@ -12,32 +12,6 @@
 
 namespace rr {
 
-// waves per SIMD an instantiation is built for: those of the k_render_fused build with the same stack (its LDS footprint is the
-// same, 4 * STACK * 64 * sizeof(E) per workgroup, and so is what stays live across a traversal)
-template <int STACK, bool TLAS, class E> struct ShadeWaves {
-    static constexpr int value = TLAS ? (sizeof(E) == 2 ? (STACK <= 30 ? 7 : 5) : RR_TLAS_WAVES_PER_SIMD(STACK))
-                                      : (sizeof(E) == 2 ? 8 : RR_FUSED_WAVES_PER_SIMD(STACK));
-};
-
-// render_pixel's loop behind its RayGen: the tree of primary ray r, depth-first; returns the sum of its leaves in the recursion's
-// order.  Bounded whatever the arithmetic yields (NaN directions included): a ray's count grows by one per level and ends the
-// branch at max_refract, and a ray is parked only while count < max_reflect, one per level, so never more than max_reflect <=
-// PEND wait at once; a walk visits each node of a finite tree at most once.
-template <bool TLAS, class E, class PK>
-__device__ __forceinline__ f3 ray_tree(const SceneDev& sc, const DispatchDev& a, RayState r, E* stk, PK& park, LaneStats& st)
-{
-    f3 acc = mk3(0.0f, 0.0f, 0.0f);
-    int np = 0;
-    for (;;) {
-        HitRec h;
-        trace_scene<false, TLAS, E, GlobalNodes>(sc, r.O, r.D, r.tmin, r.tmax, r.outside ? CULL_BACK : CULL_FRONT, h, stk, st.cnt,
-                                                 Diag{ nullptr }, GlobalNodes{});
-        ++st.rays;
-        if (!shade_ray<false, TLAS>(sc, a, h, r, acc, np, park, st)) break;
-    }
-    return acc;
-}
-
 // a: only what shade_ray and store_pixel read (bounce limits, ior, secondary interval, tonemap; compact_out = 0).
 // Each output is written only if its pointer is given (wave-uniform branches on kernel arguments).
 template <int STACK, int PEND, bool TLAS, class E>

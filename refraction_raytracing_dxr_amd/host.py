@@ -67,6 +67,29 @@ def write_hdr(filename, rgb):
         raise RRError(rc, "rr_host_image_write_hdr")
 
 
+def sample_pattern(n):
+    """-> float32 [n, 2]: the built-in sub-pixel positions of render_samples(samples=n), D3D's standard multisample pattern for
+    n = 1, 2, 4, 8 or 16, in pixel units ((0.5, 0.5) is the pixel centre)"""
+    n = int(n)
+    out = np.zeros((max(n, 1), 2), np.float32)
+    rc = _capi.lib().rr_host_sample_pattern(n if n >= 0 else 0, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise RRError(rc, "rr_host_sample_pattern(%d)" % n)
+    return out
+
+
+def camera_rays(camera, w, h, ox=0.5, oy=0.5, tmin=1e-4, tmax=100.0):
+    """-> RAY_DTYPE [w * h], row-major: the primary ray of every pixel of a w x h frame through the sub-pixel position (ox, oy)
+    (pixel units, in [0, 1]) -- with the default, the pixel centre, the rays of a dispatch; what render_samples traces for
+    that offset.  camera: SceneConstants (camera_orbit, scene_constants)."""
+    rays = np.zeros(int(w) * int(h), RAY_DTYPE)
+    rc = _capi.lib().rr_host_camera_rays(C.byref(camera), int(w), int(h), float(ox), float(oy), float(np.float32(tmin)),
+                                         float(np.float32(tmax)), rays.ctypes.data)
+    if rc:
+        raise RRError(rc, "rr_host_camera_rays")
+    return rays
+
+
 def make_instances(transforms=None, meshes=None, masks=None, flags=None):
     """64-byte instance records (RefractionDemo.cpp:324-334 fills exactly one: identity, mask 1, flags 0)."""
     if transforms is None:
@@ -499,6 +522,50 @@ class Renderer:
             cnt = np.zeros(n, np.uint32) if ray_counts else None
             self._ck(self._L.rr_shade_rays(self._h, rays.ctypes.data, n, C.byref(p), f32.ctypes.data,
                                            u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_shade_rays")
+        out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
+        return out if len(out) > 1 else f32
+
+    def render_samples(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
+        """Supersampled frame (rr_render_samples): every pixel of a width x height frame takes S primary rays through S sub-pixel
+        positions, each with the shader's whole ray tree, averaged on the GPU in sample order: ((c_0 + c_1) + ...) / S in fp32, c_s
+        being what shade_rays gives the ray camera_rays(camera, width, height, *offset_s) has for the pixel.  samples: an int
+        (1, 2, 4, 8, 16) for the built-in pattern sample_pattern(samples), or an [S, 2] float32 array of offsets in [0, 1],
+        S <= 64.  camera: SceneConstants.  params (default_params()): bounce limits, ior, the ray intervals, and of the flags
+        DISPATCH_TONEMAP_REINHARD (RGBA8 output only) and DISPATCH_DEBUG_NO_CULL.  Not a dispatch: read_frame, stats() and the
+        tile partition are neither used nor changed.
+
+        -> float32 [height, width, 4] (r, g, b, 1); rgba8=True adds the R8G8B8A8_UNORM store (uint8 [height, width, 4]),
+        ray_counts=True the TraceRay calls of the pixel's S trees (uint32 [height, width]); the result is then a tuple in that
+        order.  device=False: numpy arrays, blocking.  device=True: new torch tensors on this renderer's GPU (the counts as
+        int32), computed on the renderer's stream without waiting for it (stream order as query_rays)."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        if isinstance(samples, (int, np.integer)):
+            off, n = None, int(samples)
+        else:
+            off = np.ascontiguousarray(samples, np.float32)
+            if off.ndim != 2 or off.shape[1] != 2:
+                raise ValueError("render_samples: samples must be an int or an [S, 2] array")
+            n = off.shape[0]
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_samples: negative size")
+        offp = off.ctypes.data if off is not None and n else None
+        shape = (max(h, 0), max(w, 0))
+        if device:
+            import torch
+            dev = "cuda:%d" % self.device
+            f32 = torch.empty(shape + (4,), dtype=torch.float32, device=dev)
+            u8 = torch.empty(shape + (4,), dtype=torch.uint8, device=dev) if rgba8 else None
+            cnt = torch.empty(shape, dtype=torch.int32, device=dev) if ray_counts else None
+            self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, C.c_void_p(f32.data_ptr() if w * h else None),
+                                                      C.c_void_p(u8.data_ptr() if u8 is not None and w * h else None),
+                                                      C.c_void_p(cnt.data_ptr() if cnt is not None and w * h else None)), "rr_render_samples_device")
+        else:
+            f32 = np.zeros(shape + (4,), np.float32)
+            u8 = np.zeros(shape + (4,), np.uint8) if rgba8 else None
+            cnt = np.zeros(shape, np.uint32) if ray_counts else None
+            self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, f32.ctypes.data,
+                                               u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_render_samples")
         out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
         return out if len(out) > 1 else f32
 

@@ -463,6 +463,45 @@ int  rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, 
                               const rr_dispatch_params* params, const float* offsets, uint32_t n_samples,
                               void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
+/* ---- adaptive supersampling: n_base samples everywhere, n_max where the frame has contrast (present from ABI version 3) ------
+ * A supersampled frame whose pixels take the first n_base samples of the pattern, and the remaining ones up to n_max only where
+ * the base samples show contrast.  width, height, constants, params and offsets[n_max][2] as for rr_render_samples (offsets ==
+ * NULL: rr_host_sample_pattern(n_max), so n_max is 1, 2, 4, 8 or 16); 1 <= n_base <= n_max <= RR_MAX_SAMPLES; threshold finite and
+ * >= 0 (RR_ERR_INVALID_ARGUMENT otherwise).  The base samples are samples 0 .. n_base-1 of the one pattern.  With c_s(p) the
+ * colour rr_shade_rays gives sample s of pixel p (the rays of rr_host_camera_rays with offset s), all in fp32 and per channel:
+ *   1. sum_b(p) = ((c_0 + c_1) + ...) + c_(n_base-1), starting at c_0: the resolve rule of rr_render_samples.
+ *   2. the display value of a channel value c: v(c) = fminf(fmaxf(c, 0), 1); with RR_DISPATCH_TONEMAP_REINHARD m = fmaxf(c, 0),
+ *      v = fminf(m / (1 + m), 1).  fmaxf / fminf return the operand that is a number: NaN shows as 0, +inf as 1.
+ *   3. own contrast: r_own(p) = max over channels of (max_s v(c_s) - min_s v(c_s)) over the base samples.
+ *   4. neighbour contrast: b(p) = v(sum_b(p) / (float)n_base); r_nb(p) = max over the 4-neighbours q of p inside the frame and
+ *      over channels of fabsf(b(p) - b(q)).
+ *   5. p is refined iff r_own(p) > threshold || r_nb(p) > threshold.
+ *   6. an unrefined pixel resolves to sum_b / (float)n_base; a refined one continues the fold, sum_b + c_(n_base) + ... +
+ *      c_(n_max-1), and divides by (float)n_max.
+ * No operation of 2 to 5 is fused with another.  So every pixel is, bit for bit, that pixel of rr_render_samples(offsets, n_base)
+ * or of rr_render_samples(offsets, n_max); n_base == n_max is rr_render_samples(n_max), and a threshold >= 1 refines nothing.
+ * Outputs, row-major width * height, each optional, but at least one of rgba32f / rgba8 must be given:
+ *   rgba32f[i]   float4 (resolved r, g, b, 1)
+ *   rgba8[i]     the R8G8B8A8_UNORM store of it (honours RR_DISPATCH_TONEMAP_REINHARD)
+ *   n_rays[i]    uint32: TraceRay calls of all the trees pixel i ran
+ *   n_taken[i]   uint32: n_base or n_max
+ * Of params->flags only RR_DISPATCH_TONEMAP_REINHARD and RR_DISPATCH_DEBUG_NO_CULL are read; background blocks take part in
+ * the rule like any other, and the flag changes no byte of any output.  Not a dispatch, exactly as rr_render_samples: frame,
+ * rr_get_stats, render_kernel[_name] and the kernel choices stay, rr_set_tile_partition is ignored.  Errors and state as
+ * rr_render_samples[_device].
+ * rr_render_adaptive: host arrays, blocking; n_refined (may be NULL) receives the number of refined pixels.
+ * rr_render_adaptive_device: device pointers aligned as for rr_render_samples_device, d_n_taken 4-byte aligned; stream-ordered
+ * on the context's stream: nothing is synchronised, allocated or read back.  The intermediate state lives in d_workspace, 16-byte
+ * aligned device memory of workspace_bytes >= rr_host_adaptive_workspace_bytes(width, height) (RR_ERR_INVALID_ARGUMENT
+ * otherwise), which needs no clearing and may be reused by the next call on the same stream. */
+int  rr_render_adaptive(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                        const rr_dispatch_params* params, const float* offsets, uint32_t n_base, uint32_t n_max, float threshold,
+                        float* rgba32f, uint8_t* rgba8, uint32_t* n_rays, uint32_t* n_taken, uint64_t* n_refined);
+int  rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                               const rr_dispatch_params* params, const float* offsets, uint32_t n_base, uint32_t n_max,
+                               float threshold, void* d_rgba32f, void* d_rgba8, void* d_n_rays, void* d_n_taken,
+                               void* d_workspace, uint64_t workspace_bytes);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */
@@ -506,6 +545,9 @@ int  rr_host_camera_orbit(float angle, float fov_y, float aspect, float zn, floa
 /* D3D's standard multisample patterns for n_samples = 1, 2, 4, 8, 16 (RR_ERR_INVALID_ARGUMENT otherwise): 2 * n_samples floats
  * x0, y0, x1, y1, ..., sample i at 0.5 + k / 16 per axis, k in -8..7.  What rr_render_samples uses for offsets == NULL. */
 int  rr_host_sample_pattern(uint32_t n_samples, float* offsets);
+/* Bytes of the workspace rr_render_adaptive_device needs for a width x height frame; 0 for a width or height that is 0 or above
+ * 32768.  Monotone in both. */
+uint64_t rr_host_adaptive_workspace_bytes(uint32_t width, uint32_t height);
 /* GenerateCameraRay for every pixel of a width x height frame (row-major) with its literal 0.5 replaced by (ox, oy), both in
  * [0, 1]: the primary rays rr_render_samples takes for that offset -- with (0.5, 0.5) those of a dispatch -- as rr_ray records
  * over [tmin, tmax] with flags 0 and instance_mask 0xff.  width, height: 1..32768. */

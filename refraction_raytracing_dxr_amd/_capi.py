@@ -148,6 +148,11 @@ SYMBOLS = {
     "rr_render_samples": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
     "rr_render_samples_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P,
                                            _P]),
+    "rr_render_adaptive": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, C.c_uint32,
+                                     C.c_float, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "rr_render_adaptive_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                            C.c_uint32, C.c_float, _P, _P, _P, _P, _P, C.c_uint64]),
+    "rr_host_adaptive_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -89,6 +89,20 @@ int drawFrameSamples(int spp)
     return RR_OK;
 }
 
+int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (base <= 0 || spp < base) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameAdaptive: need 1 <= base <= spp");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    if ((rc = rr_render_adaptive(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)base, (uint32_t)spp,
+                                 threshold, nullptr, g_back.data(), nullptr, nullptr, refined)) != RR_OK)
+        return fail(rc, "rr_render_adaptive");
+    return RR_OK;
+}
+
 // `for (;;) drawFrame();` (WinMain.cpp:49-59) without the per-frame fence wait and read-back: n_frames of the
 // orbit, frames_per_dispatch depth slices per launch, in_flight launches overlapping.  The last frame lands in
 // backBuffer().  The reference notes the missing overlap itself (RefractionDemo.cpp:519-521).

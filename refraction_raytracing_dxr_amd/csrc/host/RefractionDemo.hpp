@@ -30,6 +30,9 @@ int drawFrame();                          // RefractionDemo.cpp:557-612; returns
 // drawFrame with spp primary rays per pixel (rr_render_samples, the built-in pattern of 1, 2, 4, 8 or 16 samples): the orbit
 // advances as in drawFrame and the resolved frame lands in backBuffer()
 int drawFrameSamples(int spp);
+// drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
+// threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
+int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);
 // the frame loop as one call: no per-frame wait or read-back, `in_flight` launches overlapping (1..4)
 int pump(int n_frames, int frames_per_dispatch, int in_flight, rr_stats* stats);
 // the frame loop with every frame copied to host memory while the next ones render; frames: n_frames*w*h*4 bytes

@@ -168,6 +168,7 @@ int rr_create(int device_ordinal, rr_context** out)
     if (const char* e = getenv("RR_DEBUG_STACK")) ctx->dbg.stack = atoi(e);
     if (const char* e = getenv("RR_DEBUG_TICKET")) ctx->dbg_ticket_blocks = atoi(e);
     if (const char* e = getenv("RR_DEBUG_SHAPE")) ctx->dbg_shape = atoi(e);
+    if (const char* e = getenv("RR_DEBUG_REFINE_GROUPS")) ctx->dbg_refine_groups = std::max(atoi(e), 0);
     if (const char* e = getenv("RR_DEBUG_TLAS32")) ctx->dbg.tlas32 = atoi(e) != 0;
     if (const char* e = getenv("RR_DEBUG_TILE_ORDER")) ctx->dbg_tile_order = atoi(e) != 0;
     if (const char* e = getenv("RR_DEBUG_ASYNC")) { unsigned l = 2, sh = 2; if (sscanf(e, "%u,%u", &l, &sh) == 2 && l >= 1 && sh >= 1) { ctx->dbg_async[0] = l; ctx->dbg_async[1] = sh; ctx->dbg_async_set = true; } }

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -92,26 +92,59 @@ int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, Sample
     return RR_OK;
 }
 
+// what the launch of a checked supersampled or adaptive frame takes: the scene, the frame's shading arguments with its screen
+// rectangle, the camera and the scene's kernel variant
+struct FrameArgs { SceneDev sc; DispatchDev a; CamDev cam; FusedVariant v; };
+FrameArgs frame_args(rr_context* ctx, const SamplesReq& q)
+{
+    const rr_dispatch_params p = params_or_default(q.params);
+    FrameArgs f;
+    fill_scene(ctx, f.sc);
+    f.a = shading_args(p);
+    f.a.W = q.width; f.a.H = q.height;
+    f.a.tmin_p = p.tmin_primary; f.a.tmax_p = p.tmax_primary;
+    uint32_t hr[4];
+    (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants, 1, q.width, q.height, hr);
+    f.a.hx0 = hr[0]; f.a.hy0 = hr[1]; f.a.hx1 = hr[2]; f.a.hy1 = hr[3];
+    memcpy(f.cam.M, q.constants->proj_inv, sizeof f.cam.M);
+    memcpy(f.cam.cam, q.constants->camera_loc, sizeof f.cam.cam);
+    // the kernel of a launch of many slices, as a radiance query's: S trees per lane, not a frame that ends on its longest wave
+    f.v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    return f;
+}
+
 // launches a checked supersampled frame: out holds device pointers.  Like shade_impl it touches nothing of the context but its
 // error text, and it allocates and copies nothing: constants and offsets travel as kernel arguments.
 int samples_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
 {
-    const rr_dispatch_params p = params_or_default(q.params);
-    SceneDev sc;
-    fill_scene(ctx, sc);
-    DispatchDev a = shading_args(p);
-    a.W = q.width; a.H = q.height;
-    a.tmin_p = p.tmin_primary; a.tmax_p = p.tmax_primary;
-    uint32_t hr[4];
-    (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants, 1, q.width, q.height, hr);
-    a.hx0 = hr[0]; a.hy0 = hr[1]; a.hx1 = hr[2]; a.hy1 = hr[3];
-    CamDev cam;
-    memcpy(cam.M, q.constants->proj_inv, sizeof cam.M);
-    memcpy(cam.cam, q.constants->camera_loc, sizeof cam.cam);
-    // the kernel of a launch of many slices, as a radiance query's: S trees per lane, not a frame that ends on its longest wave
-    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
-    if (hipError_t e = launch_render_samples(sc, a, cam, off, q.n_samples, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
+    const FrameArgs f = frame_args(ctx, q);
+    if (hipError_t e = launch_render_samples(f.sc, f.a, f.cam, off, q.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.who, e);
+    return RR_OK;
+}
+
+// an adaptive frame: a supersampled frame of n_samples = n_max samples, of which every pixel takes the first n_base
+struct AdaptiveReq { SamplesReq s; uint32_t n_base; float threshold; };
+
+// what both variants of rr_render_adaptive refuse before they look at device memory or allocate anything; fills the offsets
+int check_adaptive(rr_context* ctx, const AdaptiveReq& q, bool have_colour, SampleOffsets& off)
+{
+    if (int r = check_samples(ctx, q.s, have_colour, off)) return r;
+    const std::string w(q.s.who);
+    if (q.n_base == 0 || q.n_base > q.s.n_samples) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need 1 <= n_base <= n_max").c_str());
+    if (!(q.threshold >= 0.0f) || std::isinf(q.threshold))      // (NaN fails the comparison)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": threshold must be finite and >= 0").c_str());
+    return RR_OK;
+}
+
+// launches a checked adaptive frame: device pointers, a workspace of at least rr_host_adaptive_workspace_bytes.  Allocates,
+// copies and synchronises nothing.
+int adaptive_impl(rr_context* ctx, const AdaptiveReq& q, const SampleOffsets& off, const ShadeOut& out, uint32_t* n_taken, const AdaptiveWorkspace& ws)
+{
+    const FrameArgs f = frame_args(ctx, q.s);
+    if (hipError_t e = launch_render_adaptive(f.sc, f.a, f.cam, off, q.n_base, q.s.n_samples, q.threshold, ws, out.f32, out.rgba8, out.n_rays, n_taken,
+                                              f.v.stack, f.v.pend, f.v.stack16, (uint32_t)ctx->dbg_refine_groups, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
 } // namespace
@@ -262,6 +295,59 @@ int rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, c
     if (((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 || ((uintptr_t)d_n_rays & 3u) != 0)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_samples_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers");
     return samples_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+uint64_t rr_host_adaptive_workspace_bytes(uint32_t width, uint32_t height)
+{
+    if (width == 0 || height == 0 || width > 32768u || height > 32768u) return 0;
+    return AdaptiveWorkspace(nullptr, width, height).bytes;
+}
+
+int rr_render_adaptive(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                       const float* offsets, uint32_t n_base, uint32_t n_max, float threshold, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays,
+                       uint32_t* n_taken, uint64_t* n_refined)
+{
+    if (int r = use_device(ctx)) return r;
+    const AdaptiveReq q = { { "rr_render_adaptive", width, height, constants, params, offsets, n_max }, n_base, threshold };
+    SampleOffsets off;
+    if (int r = check_adaptive(ctx, q, rgba32f || rgba8, off)) return r;
+    const size_t n = (size_t)width * height;
+    const size_t ws_units = (size_t)(rr_host_adaptive_workspace_bytes(width, height) / 16u);
+    if (rgba32f && n > ctx->d_adaptive_f32.size()) if (int r = ctx->d_adaptive_f32.grow(ctx, n)) return r;
+    if (rgba8 && n > ctx->d_adaptive_rgba8.size()) if (int r = ctx->d_adaptive_rgba8.grow(ctx, n)) return r;
+    if (n_rays && n > ctx->d_adaptive_n.size()) if (int r = ctx->d_adaptive_n.grow(ctx, n)) return r;
+    if (n_taken && n > ctx->d_adaptive_taken.size()) if (int r = ctx->d_adaptive_taken.grow(ctx, n)) return r;
+    if (ws_units > ctx->d_adaptive_ws.size()) if (int r = ctx->d_adaptive_ws.grow(ctx, ws_units)) return r;
+    const AdaptiveWorkspace ws(ctx->d_adaptive_ws.get(), width, height);
+    if (int r = adaptive_impl(ctx, q, off, { rgba32f ? ctx->d_adaptive_f32.get() : nullptr, rgba8 ? ctx->d_adaptive_rgba8.get() : nullptr,
+                                             n_rays ? ctx->d_adaptive_n.get() : nullptr }, n_taken ? ctx->d_adaptive_taken.get() : nullptr, ws)) return r;
+    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_adaptive_f32.get(), n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_adaptive_rgba8.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_adaptive_n.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_taken) RR_HIP(hipMemcpyAsync(n_taken, ctx->d_adaptive_taken.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    uint32_t total = 0;
+    const uint32_t n_blocks = ((width + 7u) / 8u) * ((height + 7u) / 8u);
+    if (n_refined) RR_HIP(hipMemcpyAsync(&total, ws.base + n_blocks, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    if (n_refined) *n_refined = total;
+    return RR_OK;
+}
+
+int rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                              const float* offsets, uint32_t n_base, uint32_t n_max, float threshold, void* d_rgba32f, void* d_rgba8, void* d_n_rays,
+                              void* d_n_taken, void* d_workspace, uint64_t workspace_bytes)
+{
+    if (int r = use_device(ctx)) return r;
+    const AdaptiveReq q = { { "rr_render_adaptive_device", width, height, constants, params, offsets, n_max }, n_base, threshold };
+    SampleOffsets off;
+    if (int r = check_adaptive(ctx, q, d_rgba32f || d_rgba8, off)) return r;
+    if (((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 || ((uintptr_t)d_n_rays & 3u) != 0 || ((uintptr_t)d_n_taken & 3u) != 0)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_adaptive_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers");
+    if (!d_workspace || ((uintptr_t)d_workspace & 15u) != 0 || workspace_bytes < rr_host_adaptive_workspace_bytes(width, height))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
+                    "rr_render_adaptive_device: need a 16-byte aligned workspace of at least rr_host_adaptive_workspace_bytes(width, height) bytes");
+    return adaptive_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) },
+                         static_cast<uint32_t*>(d_n_taken), AdaptiveWorkspace(d_workspace, width, height));
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -205,6 +205,7 @@ struct rr_context {
     uint32_t dbg_async[2] = { 2, 2 };    // RR_DEBUG_ASYNC="step,shade": issue thresholds of k_stream_rays in sixteenths of the live lanes
     bool dbg_tile_order = true;      // RR_DEBUG_TILE_ORDER=0: tiles in image order (DispatchDev::rt_*)
     int  dbg_shape = 0;              // RR_DEBUG_SHAPE: first k_render_lds workgroup shape to consider (rr_launch.h)
+    int  dbg_refine_groups = 0;      // RR_DEBUG_REFINE_GROUPS: workgroups of k_adaptive_refine, which then loops over the list (0: the worst-case grid)
     std::string dbg_diag;            // RR_DEBUG_DIAG: file that receives per-wave diagnostics of Depth-1 dispatches
 
     // timing
@@ -230,6 +231,9 @@ struct rr_context {
     // rr_render_samples scratch (the host variant's outputs)
     DevBuf<float4>     d_samples_f32;
     DevBuf<uint32_t>   d_samples_rgba8, d_samples_n;
+    // rr_render_adaptive scratch (the host variant's outputs and its workspace, in units of 16 bytes)
+    DevBuf<float4>     d_adaptive_f32, d_adaptive_ws;
+    DevBuf<uint32_t>   d_adaptive_rgba8, d_adaptive_n, d_adaptive_taken;
 };
 
 namespace rr {

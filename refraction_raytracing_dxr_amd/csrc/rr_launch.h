@@ -51,6 +51,32 @@ hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_
 struct SampleOffsets { static constexpr uint32_t MAX = 64; float v[2 * MAX]; };     // x0, y0, x1, y1, ...
 hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_samples,
                                  float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+// ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
+// rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
+// n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).
+// The stages' state lives in a caller's workspace of AdaptiveWorkspace(nullptr, W, H).bytes bytes, 16-byte aligned, laid out as:
+//   rec    W * H float4     sum of the base samples (r, g, b) and the pixel's own contrast
+//   cnt    W * H uint32     TraceRay calls of the base samples
+//   list   W * H uint32     the refined pixels' indices, the first base[n_blocks] entries
+//   masks  n_blocks uint64  per 8x8 block (raster order): bit l = the block's pixel l in Morton order is refined
+//   base   n_blocks + 1     exclusive scan of the masks' popcounts; base[n_blocks] = refined pixels of the frame
+struct AdaptiveWorkspace {
+    float4* rec; uint32_t* cnt; uint32_t* list; unsigned long long* masks; uint32_t* base;
+    uint64_t bytes;
+    // p may be null (sizes only); W, H: 1..32768
+    AdaptiveWorkspace(void* p, uint32_t W, uint32_t H)
+    {
+        const uint64_t n = (uint64_t)W * H, nb = (uint64_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+        const uint64_t o_cnt = 16u * n, o_list = o_cnt + 4u * n, o_masks = (o_list + 4u * n + 15u) & ~(uint64_t)15u, o_base = o_masks + 8u * nb;
+        const uintptr_t c = reinterpret_cast<uintptr_t>(p);
+        rec = static_cast<float4*>(p); cnt = reinterpret_cast<uint32_t*>(c + o_cnt); list = reinterpret_cast<uint32_t*>(c + o_list);
+        masks = reinterpret_cast<unsigned long long*>(c + o_masks); base = reinterpret_cast<uint32_t*>(c + o_base);
+        bytes = (o_base + 4u * (nb + 1u) + 15u) & ~(uint64_t)15u;
+    }
+};
+hipError_t launch_render_adaptive(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_base,
+                                  uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, float4* f32, uint32_t* rgba8, uint32_t* n_rays,
+                                  uint32_t* n_taken, int stack, int pend, bool stack16, uint32_t refine_groups, hipStream_t s);
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

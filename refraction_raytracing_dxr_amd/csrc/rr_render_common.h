@@ -125,6 +125,23 @@ __device__ __forceinline__ RayState primary_ray(const DispatchDev& a, const CamD
     return r;
 }
 
+// Sample s of pixel (fx, fy) of an fw x fh frame, for k_render_samples and the k_adaptive_* kernels: GenerateCameraRay
+// (RayTracing.hlsl:27-40) with the literal 0.5 replaced by offset s, screen_coord's operations in its order, and RayGen's payload
+// (hlsl:57-60)
+__device__ __forceinline__ RayState sample_ray(const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t s, float fx, float fy,
+                                               float fw, float fh)
+{
+    const float px = fx + off.v[2u * s], py = fy + off.v[2u * s + 1u];
+    const float sx = px / fw * 2.0f - 1.0f;
+    const float sy = -(py / fh * 2.0f - 1.0f);
+    RayState r;
+    r.O = mk3(cam.cam[0], cam.cam[1], cam.cam[2]);
+    r.D = camera_ray_dir(cam.M, sx, sy);
+    r.w = 1.0f; r.count = 0; r.outside = true;
+    r.tmin = a.tmin_p; r.tmax = a.tmax_p;
+    return r;
+}
+
 // ClosestHit (hlsl:79-125) / Miss (hlsl:127-137) for the ray just traced: adds a leaf to acc, or spawns the refracted child
 // (followed at once) and the reflected one (parked).  Returns false once the pixel's tree is exhausted; otherwise r is the
 // next ray of the pixel in the recursion's depth-first order.

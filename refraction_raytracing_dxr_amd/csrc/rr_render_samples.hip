@@ -40,15 +40,7 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_re
     LaneStats st;
     f3 sum = mk3(0.0f, 0.0f, 0.0f);
     for (uint32_t s = 0; s < n_samples; ++s) {
-        // GenerateCameraRay (RayTracing.hlsl:27-40) with the literal 0.5 replaced: screen_coord's operations in its order
-        const float px = fx + off.v[2u * s], py = fy + off.v[2u * s + 1u];
-        const float sx = px / fw * 2.0f - 1.0f;
-        const float sy = -(py / fh * 2.0f - 1.0f);
-        RayState r;
-        r.O = mk3(cam.cam[0], cam.cam[1], cam.cam[2]);
-        r.D = camera_ray_dir(cam.M, sx, sy);
-        r.w = 1.0f; r.count = 0; r.outside = true;              // RayGen's payload (RayTracing.hlsl:57-60)
-        r.tmin = a.tmin_p; r.tmax = a.tmax_p;
+        const RayState r = sample_ray(a, cam, off, s, fx, fy, fw, fh);      // (rr_render_common.h)
         f3 c;
         if (!may_hit) {                                         // payload.color = 0 + 1 * texel (hlsl:57-62, 127-137)
             const f3 e = env_lookup(sc, r.D);

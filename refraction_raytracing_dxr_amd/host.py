@@ -17,6 +17,8 @@ from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP
 FOV_Y = float(np.float32(52.0 / 180.0 * 3.1415))     # RefractionDemo.cpp:559
 ASPECT = float(np.float32(1.333))
 TILE = 32
+# render_adaptive's default threshold, in display units (1 = the whole range of a channel): DESIGN 5.7 has how it was chosen
+ADAPTIVE_THRESHOLD = 0.05
 
 
 def default_params(**kw):
@@ -205,9 +207,11 @@ class Renderer:
     def set_stream(self, hip_stream):
         """run on a caller-owned hipStream_t handle (0 / None = HIP's default stream)"""
         self._ck(self._L.rr_set_stream(self._h, C.c_void_p(hip_stream or None)), "rr_set_stream")
+        self._stream_key = int(hip_stream or 0)
 
     def reset_stream(self):
         self._ck(self._L.rr_reset_stream(self._h), "rr_reset_stream")
+        self._stream_key = None
 
     def wait(self):
         self._ck(self._L.rr_wait(self._h), "rr_wait")
@@ -568,6 +572,68 @@ class Renderer:
                                                u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_render_samples")
         out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
         return out if len(out) > 1 else f32
+
+    def render_adaptive(self, width, height, camera, samples=(4, 16), threshold=ADAPTIVE_THRESHOLD, params=None, rgba8=False, ray_counts=False,
+                        sample_counts=False, device=False):
+        """Adaptively supersampled frame (rr_render_adaptive): every pixel takes the first n_base samples of the pattern, and the
+        rest up to n_max only where its base samples show contrast -- the displayed values (clamped to [0, 1], after Reinhard if
+        params asks for it) of its own base samples spread by more than threshold in some channel, or its base colour differs by
+        more than threshold from a 4-neighbour's.  Each pixel is bit for bit that pixel of render_samples with n_base or with n_max
+        samples (include/rrdxr.h has the rule).  samples: (n_base, n_max) ints for the built-in pattern sample_pattern(n_max), or
+        (n_base, offsets [S, 2]) with n_max = S.  The other arguments as render_samples; not a dispatch either.
+
+        -> float32 [height, width, 4]; rgba8=True adds the uint8 [height, width, 4] store, ray_counts=True the TraceRay calls of the
+        trees each pixel ran, sample_counts=True n_base or n_max per pixel (uint32 [height, width]); a tuple in that order, with the
+        number of refined pixels last when device=False.  device=True: torch tensors (counts as int32) on the renderer's stream,
+        the workspace (a tensor the renderer keeps per stream it is put on) included, nothing synchronised -- and no refined-pixel count, which only a read-back could give."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        n_base, top = samples
+        n_base = int(n_base)
+        if isinstance(top, (int, np.integer)):
+            off, n_max = None, int(top)
+        else:
+            off = np.ascontiguousarray(top, np.float32)
+            if off.ndim != 2 or off.shape[1] != 2:
+                raise ValueError("render_adaptive: samples must be (n_base, n_max) or (n_base, [S, 2] array)")
+            n_max = off.shape[0]
+        if n_base < 0 or n_max < 0 or w < 0 or h < 0:
+            raise ValueError("render_adaptive: negative size")
+        offp = off.ctypes.data if off is not None and n_max else None
+        shape = (h, w)
+        if device:
+            import torch
+            dev = "cuda:%d" % self.device
+            f32 = torch.empty(shape + (4,), dtype=torch.float32, device=dev)
+            u8 = torch.empty(shape + (4,), dtype=torch.uint8, device=dev) if rgba8 else None
+            cnt = torch.empty(shape, dtype=torch.int32, device=dev) if ray_counts else None
+            taken = torch.empty(shape, dtype=torch.int32, device=dev) if sample_counts else None
+            nbytes = int(self._L.rr_host_adaptive_workspace_bytes(w, h))
+            # one workspace per stream the renderer has been put on, reused call after call: the calls on a stream are ordered,
+            # calls on different streams are not and never share one.  Before a larger one replaces it that stream is waited
+            # for, since the stages in flight still read the old one
+            key = getattr(self, "_stream_key", None)
+            pool = self.__dict__.setdefault("_adaptive_ws", {})
+            ws = pool.get(key)
+            if ws is None or ws.numel() * 4 < nbytes:
+                if ws is not None:
+                    self.wait()
+                ws = pool[key] = torch.empty((max(nbytes, 16) // 16, 4), dtype=torch.float32, device=dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and w * h else None)
+            self._ck(self._L.rr_render_adaptive_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), ptr(f32),
+                                                       ptr(u8), ptr(cnt), ptr(taken), C.c_void_p(ws.data_ptr()), ws.numel() * 4),
+                     "rr_render_adaptive_device")
+            out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ()) + ((taken,) if sample_counts else ())
+            return out if len(out) > 1 else f32
+        f32 = np.zeros(shape + (4,), np.float32)
+        u8 = np.zeros(shape + (4,), np.uint8) if rgba8 else None
+        cnt = np.zeros(shape, np.uint32) if ray_counts else None
+        taken = np.zeros(shape, np.uint32) if sample_counts else None
+        n_ref = C.c_uint64(0)
+        self._ck(self._L.rr_render_adaptive(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), f32.ctypes.data,
+                                            u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None,
+                                            taken.ctypes.data if sample_counts else None, C.byref(n_ref)), "rr_render_adaptive")
+        return (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ()) + ((taken,) if sample_counts else ()) + (int(n_ref.value),)
 
     def env_lookup(self, dirs):
         """Miss (RayTracing.hlsl:127-137) on an [n,3] array of directions -> [n,3] texels."""

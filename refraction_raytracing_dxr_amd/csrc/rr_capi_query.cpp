@@ -45,6 +45,32 @@ DispatchDev shading_args(const rr_dispatch_params& p)
 // a radiance query's outputs (device pointers, any may be null)
 struct ShadeOut { float4* f32; uint32_t* rgba8; uint32_t* n_rays; };
 
+// The host variants' outputs pass through the context's one staged set (rr_context.h).  stage: grows what the call wants to n
+// elements and gives the launch its device pointers.  fetch: copies back to the caller's arrays (null: not wanted) and waits.
+int stage(rr_context* ctx, size_t n, bool want_f32, bool want_rgba8, bool want_n, ShadeOut& out)
+{
+    if (want_f32 && n > ctx->d_out_f32.size()) if (int r = ctx->d_out_f32.grow(ctx, n)) return r;
+    if (want_rgba8 && n > ctx->d_out_rgba8.size()) if (int r = ctx->d_out_rgba8.grow(ctx, n)) return r;
+    if (want_n && n > ctx->d_out_n.size()) if (int r = ctx->d_out_n.grow(ctx, n)) return r;
+    out = { want_f32 ? ctx->d_out_f32.get() : nullptr, want_rgba8 ? ctx->d_out_rgba8.get() : nullptr, want_n ? ctx->d_out_n.get() : nullptr };
+    return RR_OK;
+}
+int fetch(rr_context* ctx, size_t n, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_out_f32.get(), n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_out_rgba8.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_out_n.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    return RR_OK;
+}
+
+// what the _device variants refuse of their output pointers (null passes: not wanted), with the entry point's own message
+int check_out_alignment(rr_context* ctx, const void* d_rgba32f, const void* d_rgba8, const void* d_n_rays, const void* d_n_taken, const char* what)
+{
+    const bool ok = ((uintptr_t)d_rgba32f & 15u) == 0 && (((uintptr_t)d_rgba8 | (uintptr_t)d_n_rays | (uintptr_t)d_n_taken) & 3u) == 0;
+    return ok ? RR_OK : fail(ctx, RR_ERR_INVALID_ARGUMENT, what);
+}
+
 // checks a radiance query's parameters and launches it: d_rays is a device pointer.  Touches nothing of
 // the context but its error text: no counters, no frame, no kernel choice.
 int shade_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
@@ -235,19 +261,12 @@ int rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_disp
     if (n == 0) return RR_OK;
     if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: need rgba32f or rgba8");
     if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: null rays");
-    const rr_dispatch_params p = params_or_default(params);
     if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
-    if (rgba32f && n > ctx->d_shade_f32.size()) if (int r = ctx->d_shade_f32.grow(ctx, n)) return r;
-    if (rgba8 && n > ctx->d_shade_rgba8.size()) if (int r = ctx->d_shade_rgba8.grow(ctx, n)) return r;
-    if (n_rays && n > ctx->d_shade_n.size()) if (int r = ctx->d_shade_n.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
     RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    if (int r = shade_impl(ctx, "rr_shade_rays", ctx->d_rays.get(), n, p, { rgba32f ? ctx->d_shade_f32.get() : nullptr,
-                           rgba8 ? ctx->d_shade_rgba8.get() : nullptr, n_rays ? ctx->d_shade_n.get() : nullptr })) return r;
-    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_shade_f32.get(), (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_shade_rgba8.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_shade_n.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipStreamSynchronize(ctx->stream));
-    return RR_OK;
+    if (int r = shade_impl(ctx, "rr_shade_rays", ctx->d_rays.get(), n, params_or_default(params), out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
 }
 
 int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
@@ -257,10 +276,9 @@ int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const 
     if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_device: build the BLAS and TLAS first");
     if (n == 0) return RR_OK;
     if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: need d_rgba32f or d_rgba8");
-    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0 || ((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 ||
-        ((uintptr_t)d_n_rays & 3u) != 0)
-        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
-                    "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers");
+    const char* const align = "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
     return shade_impl(ctx, "rr_shade_rays_device", static_cast<const rr_ray_dev*>(d_rays), n, params_or_default(params),
                       { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
@@ -273,16 +291,10 @@ int rr_render_samples(rr_context* ctx, uint32_t width, uint32_t height, const rr
     SampleOffsets off;
     if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
     const size_t n = (size_t)width * height;
-    if (rgba32f && n > ctx->d_samples_f32.size()) if (int r = ctx->d_samples_f32.grow(ctx, n)) return r;
-    if (rgba8 && n > ctx->d_samples_rgba8.size()) if (int r = ctx->d_samples_rgba8.grow(ctx, n)) return r;
-    if (n_rays && n > ctx->d_samples_n.size()) if (int r = ctx->d_samples_n.grow(ctx, n)) return r;
-    if (int r = samples_impl(ctx, q, off, { rgba32f ? ctx->d_samples_f32.get() : nullptr, rgba8 ? ctx->d_samples_rgba8.get() : nullptr,
-                                            n_rays ? ctx->d_samples_n.get() : nullptr })) return r;
-    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_samples_f32.get(), n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_samples_rgba8.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_samples_n.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipStreamSynchronize(ctx->stream));
-    return RR_OK;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = samples_impl(ctx, q, off, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
 }
 
 int rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
@@ -292,8 +304,8 @@ int rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, c
     const SamplesReq q = { "rr_render_samples_device", width, height, constants, params, offsets, n_samples };
     SampleOffsets off;
     if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 || ((uintptr_t)d_n_rays & 3u) != 0)
-        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_samples_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers");
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_samples_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return samples_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
@@ -313,22 +325,16 @@ int rr_render_adaptive(rr_context* ctx, uint32_t width, uint32_t height, const r
     if (int r = check_adaptive(ctx, q, rgba32f || rgba8, off)) return r;
     const size_t n = (size_t)width * height;
     const size_t ws_units = (size_t)(rr_host_adaptive_workspace_bytes(width, height) / 16u);
-    if (rgba32f && n > ctx->d_adaptive_f32.size()) if (int r = ctx->d_adaptive_f32.grow(ctx, n)) return r;
-    if (rgba8 && n > ctx->d_adaptive_rgba8.size()) if (int r = ctx->d_adaptive_rgba8.grow(ctx, n)) return r;
-    if (n_rays && n > ctx->d_adaptive_n.size()) if (int r = ctx->d_adaptive_n.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
     if (n_taken && n > ctx->d_adaptive_taken.size()) if (int r = ctx->d_adaptive_taken.grow(ctx, n)) return r;
     if (ws_units > ctx->d_adaptive_ws.size()) if (int r = ctx->d_adaptive_ws.grow(ctx, ws_units)) return r;
     const AdaptiveWorkspace ws(ctx->d_adaptive_ws.get(), width, height);
-    if (int r = adaptive_impl(ctx, q, off, { rgba32f ? ctx->d_adaptive_f32.get() : nullptr, rgba8 ? ctx->d_adaptive_rgba8.get() : nullptr,
-                                             n_rays ? ctx->d_adaptive_n.get() : nullptr }, n_taken ? ctx->d_adaptive_taken.get() : nullptr, ws)) return r;
-    if (rgba32f) RR_HIP(hipMemcpyAsync(rgba32f, ctx->d_adaptive_f32.get(), n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba8) RR_HIP(hipMemcpyAsync(rgba8, ctx->d_adaptive_rgba8.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_rays) RR_HIP(hipMemcpyAsync(n_rays, ctx->d_adaptive_n.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int r = adaptive_impl(ctx, q, off, out, n_taken ? ctx->d_adaptive_taken.get() : nullptr, ws)) return r;
     if (n_taken) RR_HIP(hipMemcpyAsync(n_taken, ctx->d_adaptive_taken.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
     uint32_t total = 0;
-    const uint32_t n_blocks = ((width + 7u) / 8u) * ((height + 7u) / 8u);
-    if (n_refined) RR_HIP(hipMemcpyAsync(&total, ws.base + n_blocks, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipStreamSynchronize(ctx->stream));
+    if (n_refined) RR_HIP(hipMemcpyAsync(&total, ws.total, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int r = fetch(ctx, n, rgba32f, rgba8, n_rays)) return r;
     if (n_refined) *n_refined = total;
     return RR_OK;
 }
@@ -341,8 +347,8 @@ int rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height, 
     const AdaptiveReq q = { { "rr_render_adaptive_device", width, height, constants, params, offsets, n_max }, n_base, threshold };
     SampleOffsets off;
     if (int r = check_adaptive(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (((uintptr_t)d_rgba32f & 15u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0 || ((uintptr_t)d_n_rays & 3u) != 0 || ((uintptr_t)d_n_taken & 3u) != 0)
-        return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_render_adaptive_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers");
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, d_n_taken,
+                                    "rr_render_adaptive_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     if (!d_workspace || ((uintptr_t)d_workspace & 15u) != 0 || workspace_bytes < rr_host_adaptive_workspace_bytes(width, height))
         return fail(ctx, RR_ERR_INVALID_ARGUMENT,
                     "rr_render_adaptive_device: need a 16-byte aligned workspace of at least rr_host_adaptive_workspace_bytes(width, height) bytes");

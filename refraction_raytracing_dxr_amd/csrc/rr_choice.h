@@ -51,6 +51,37 @@ void record_timings(KernelChoice& ch, float ms_a, float ms_b, double rect_share)
 // k_render_fused's instantiation: stack entries, parked-ray slots and 16-bit stack entries
 struct FusedVariant { int stack, pend; bool stack16; };
 FusedVariant fused_variant(const SceneFacts& s, uint32_t depth, int max_reflect, const DebugFacts& d);
+
+// The ray-tree kernels (k_shade_rays, k_render_samples, k_adaptive_base / _refine: ray_tree on a lane behind a RayGen of their own)
+// are built as <STACK, PEND, TLAS, E>: stack entries, parked-ray slots, two-level scene, stack entry type.  TreeVariant names one
+// instantiation, as a tag a generic lambda takes; a workgroup's four stacks take lds_bytes of LDS.
+template <int STACK, int PEND, bool TLAS, class E> struct TreeVariant {
+    static constexpr int stack = STACK, pend = PEND;
+    static constexpr bool tlas = TLAS;
+    using entry = E;
+    static constexpr uint32_t lds_bytes = 4u * STACK * 64u * sizeof(E);
+};
+template <int STACK, int PEND, class F> auto tree_variant32(bool single_identity, F&& f)
+{
+    return !single_identity ? f(TreeVariant<STACK, PEND, true, uint32_t>{}) : f(TreeVariant<STACK, PEND, false, uint32_t>{});
+}
+// The one ladder of those kernels: f(TreeVariant) of the instantiation that runs a scene's FusedVariant (stack <= 64, pend <= 8: the
+// launchers check) -- launch_render_fused's ladder without its 22-entry rung (seven waves per SIMD against six: DESIGN 5.5).  20
+// instantiations in all; tests/test_kernel_choice.py walks every rung.  The other ladders stay where they are: launch_render_fused's
+// has that rung and branches on its diag and stats builds with waves per SIMD of its own per rung (rr_render.hip); the trace, query
+// and multi-hit kernels are <STACK, TLAS> builds of two stack sizes without parked rays, two lines each.
+template <class F> auto for_tree_variant(bool single_identity, FusedVariant v, F&& f)
+{
+    const bool si = single_identity;
+    if (v.stack16 && !si && v.pend <= 2 && v.stack <= 30) return f(TreeVariant<30, 2, true, uint16_t>{});
+    if (v.stack16 && !si && v.pend <= 2 && v.stack <= 39) return f(TreeVariant<39, 2, true, uint16_t>{});
+    if (v.stack16 && si && v.stack <= 39) return v.pend <= 2 ? f(TreeVariant<39, 2, false, uint16_t>{}) : f(TreeVariant<39, 8, false, uint16_t>{});
+    if (v.stack <= 19 && v.pend <= 2) return tree_variant32<19, 2>(si, f);
+    if (v.stack <= 26 && v.pend <= 2) return tree_variant32<26, 2>(si, f);
+    if (v.stack <= 31) return v.pend <= 2 ? tree_variant32<31, 2>(si, f) : tree_variant32<31, 8>(si, f);
+    if (v.stack <= 39) return v.pend <= 2 ? tree_variant32<39, 2>(si, f) : tree_variant32<39, 8>(si, f);
+    return v.pend <= 2 ? tree_variant32<64, 2>(si, f) : tree_variant32<64, 8>(si, f);
+}
 // pixels of one slice that rank `rank` renders (edge tiles counted exactly): round robin tiles, or the mesh partition's
 uint64_t owned_pixels(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, const rr_mesh_partition* part);
 

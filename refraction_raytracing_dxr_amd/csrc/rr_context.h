@@ -225,15 +225,14 @@ struct rr_context {
     DevBuf<rr_ray_dev> d_rays;
     DevBuf<rr_hit_dev> d_hits;
     DevBuf<uint32_t>   d_counts;     // rr_query_rays_multi
-    // rr_shade_rays scratch (the host variant's outputs; the frame buffers belong to the dispatches)
-    DevBuf<float4>     d_shade_f32;
-    DevBuf<uint32_t>   d_shade_rgba8, d_shade_n;
-    // rr_render_samples scratch (the host variant's outputs)
-    DevBuf<float4>     d_samples_f32;
-    DevBuf<uint32_t>   d_samples_rgba8, d_samples_n;
-    // rr_render_adaptive scratch (the host variant's outputs and its workspace, in units of 16 bytes)
-    DevBuf<float4>     d_adaptive_f32, d_adaptive_ws;
-    DevBuf<uint32_t>   d_adaptive_rgba8, d_adaptive_n, d_adaptive_taken;
+    // the outputs of the host variants of rr_shade_rays, rr_render_samples and rr_render_adaptive (the frame buffers belong to the
+    // dispatches).  One set for the three: each runs on the context's stream and synchronises before it returns, and grow waits
+    // for that stream, so at most one call uses the set at any time
+    DevBuf<float4>     d_out_f32;
+    DevBuf<uint32_t>   d_out_rgba8, d_out_n;
+    // rr_render_adaptive's own: its sample counts and its workspace, in units of 16 bytes
+    DevBuf<uint32_t>   d_adaptive_taken;
+    DevBuf<float4>     d_adaptive_ws;
 };
 
 namespace rr {

@@ -40,7 +40,8 @@ hipError_t launch_query_multi(const SceneDev& sc, const rr_ray_dev* rays, uint32
                               uint32_t inst0_mask, int stack, hipStream_t s);
 // ---- rr_shade_rays.hip: radiance queries (rr_shade_rays[_device]): the render kernels' ray tree on caller rays.  a: the fields
 // shade_ray and store_pixel read; f32 / rgba8 / n_rays: n entries each, any of them may be null; stack, pend, stack16: the scene's
-// FusedVariant (rr_choice.h)
+// FusedVariant (rr_choice.h), which for_tree_variant (there) maps to the instantiation launched -- here and in the two launchers
+// below; stack > 64 or pend > 8 is hipErrorInvalidValue
 hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
                              uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
 // ---- rr_render_samples.hip: supersampled frames (rr_render_samples[_device]): n_samples primary rays per pixel of an a.W x a.H
@@ -59,9 +60,9 @@ hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const
 //   cnt    W * H uint32     TraceRay calls of the base samples
 //   list   W * H uint32     the refined pixels' indices, the first base[n_blocks] entries
 //   masks  n_blocks uint64  per 8x8 block (raster order): bit l = the block's pixel l in Morton order is refined
-//   base   n_blocks + 1     exclusive scan of the masks' popcounts; base[n_blocks] = refined pixels of the frame
+//   base   n_blocks + 1     exclusive scan of the masks' popcounts; base[n_blocks] (total) = refined pixels of the frame
 struct AdaptiveWorkspace {
-    float4* rec; uint32_t* cnt; uint32_t* list; unsigned long long* masks; uint32_t* base;
+    float4* rec; uint32_t* cnt; uint32_t* list; unsigned long long* masks; uint32_t* base; uint32_t* total;
     uint64_t bytes;
     // p may be null (sizes only); W, H: 1..32768
     AdaptiveWorkspace(void* p, uint32_t W, uint32_t H)
@@ -70,7 +71,7 @@ struct AdaptiveWorkspace {
         const uint64_t o_cnt = 16u * n, o_list = o_cnt + 4u * n, o_masks = (o_list + 4u * n + 15u) & ~(uint64_t)15u, o_base = o_masks + 8u * nb;
         const uintptr_t c = reinterpret_cast<uintptr_t>(p);
         rec = static_cast<float4*>(p); cnt = reinterpret_cast<uint32_t*>(c + o_cnt); list = reinterpret_cast<uint32_t*>(c + o_list);
-        masks = reinterpret_cast<unsigned long long*>(c + o_masks); base = reinterpret_cast<uint32_t*>(c + o_base);
+        masks = reinterpret_cast<unsigned long long*>(c + o_masks); base = reinterpret_cast<uint32_t*>(c + o_base); total = base + nb;
         bytes = (o_base + 4u * (nb + 1u) + 15u) & ~(uint64_t)15u;
     }
 };

@@ -16,6 +16,7 @@
 // Nothing is appended by atomics and nothing is counted in place, so a workspace is reusable without clearing and the list's
 // order -- the refine pass's coherence -- is the same in every run.
 #include <hip/hip_runtime.h>
+#include "rr_choice.h"
 #include "rr_render_common.h"
 
 namespace rr {
@@ -38,9 +39,8 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_ad
     E* stk = reinterpret_cast<E*>(lds) + wave * (STACK * 64) + lane;
     const uint32_t wb = blockIdx.x * 4u + wave;                 // the wave's 8x8 block, in raster order
     if (wb >= n_blocks) return;
-    const uint32_t by = wb / blocks_x, bx = wb - by * blocks_x;
-    const uint32_t x0 = bx * 8u, y0 = by * 8u;
-    const uint32_t x = x0 + compact1by1(lane), y = y0 + compact1by1(lane >> 1);
+    const WavePixel px = wave_pixel(wb, blocks_x, lane);
+    const uint32_t x0 = px.x0, y0 = px.y0, x = px.x, y = px.y;
     if (x >= a.W || y >= a.H) return;
     const bool may_hit = x0 + 8u > a.hx0 && x0 < a.hx1 && y0 + 8u > a.hy0 && y0 < a.hy1;      // k_render_samples' background branch
     const bool tm = a.tonemap != 0u;
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256) void k_adaptive_classify(DispatchDev a, uint32
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const uint32_t wb = blockIdx.x * 4u + wave;
     if (wb >= n_blocks) return;                                 // (wave-uniform)
-    const uint32_t by = wb / blocks_x, bx = wb - by * blocks_x;
-    const uint32_t x = bx * 8u + compact1by1(lane), y = by * 8u + compact1by1(lane >> 1);
+    const WavePixel px = wave_pixel(wb, blocks_x, lane);
+    const uint32_t x = px.x, y = px.y;
     const bool inside = x < a.W && y < a.H;
     const bool tm = a.tonemap != 0u;
     const float fb = (float)n_base;
@@ -143,8 +143,8 @@ __global__ __launch_bounds__(256) void k_adaptive_list(uint32_t W, uint32_t bloc
     if (wb >= n_blocks) return;
     const unsigned long long m = masks[wb];
     if (!((m >> lane) & 1ull)) return;                          // (set only for lanes inside the frame)
-    const uint32_t by = wb / blocks_x, bx = wb - by * blocks_x;
-    const uint32_t x = bx * 8u + compact1by1(lane), y = by * 8u + compact1by1(lane >> 1);
+    const WavePixel px = wave_pixel(wb, blocks_x, lane);
+    const uint32_t x = px.x, y = px.y;
     const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     list[base[wb] + rank] = y * W + x;                          // (W * H <= 2^30)
 }
@@ -185,74 +185,38 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_ad
     }
 }
 
-struct AdaptiveLaunch {
-    const SceneDev& sc; const DispatchDev& a; const CamDev& cam; const SampleOffsets& off; uint32_t n_base, n_max;
-    const AdaptiveWorkspace& ws; float4* f32; uint32_t* rgba8; uint32_t* n_rays; uint32_t refine_groups; hipStream_t s;
-    uint32_t blocks_x() const { return (a.W + 7u) / 8u; }
-    uint32_t n_blocks() const { return blocks_x() * ((a.H + 7u) / 8u); }      // <= 4096 * 4096
-};
-
-struct BaseStage {
-    template <int STACK, int PEND, bool TLAS, class E> static hipError_t go(const AdaptiveLaunch& q)
-    {
-        const size_t lds = (size_t)4 * STACK * 64 * sizeof(E);
-        hipLaunchKernelGGL((k_adaptive_base<STACK, PEND, TLAS, E>), dim3((q.n_blocks() + 3u) / 4u), dim3(256), lds, q.s, q.sc, q.a, q.cam, q.off,
-                           q.n_base, q.blocks_x(), q.n_blocks(), q.ws.rec, q.ws.cnt);
-        return hipGetLastError();
-    }
-};
-
-struct RefineStage {
-    template <int STACK, int PEND, bool TLAS, class E> static hipError_t go(const AdaptiveLaunch& q)
-    {
-        const size_t lds = (size_t)4 * STACK * 64 * sizeof(E);
-        hipLaunchKernelGGL((k_adaptive_refine<STACK, PEND, TLAS, E>), dim3(q.refine_groups), dim3(256), lds, q.s, q.sc, q.a, q.cam, q.off,
-                           q.n_base, q.n_max, q.ws.list, q.ws.base + q.n_blocks(), q.ws.rec, q.ws.cnt, q.f32, q.rgba8, q.n_rays);
-        return hipGetLastError();
-    }
-};
-
-template <class Stage, int STACK, int PEND>
-static hipError_t launch_stage_sp(const AdaptiveLaunch& q)
-{
-    if (!q.sc.single_identity) return Stage::template go<STACK, PEND, true, uint32_t>(q);
-    return Stage::template go<STACK, PEND, false, uint32_t>(q);
-}
-
-// launch_shade_rays' ladder
-template <class Stage>
-static hipError_t launch_stage(const AdaptiveLaunch& q, int stack, int pend, bool stack16)
-{
-    const bool si = q.sc.single_identity != 0u;
-    if (stack16 && !si && pend <= 2 && stack <= 30) return Stage::template go<30, 2, true, uint16_t>(q);
-    if (stack16 && !si && pend <= 2 && stack <= 39) return Stage::template go<39, 2, true, uint16_t>(q);
-    if (stack16 && si && stack <= 39) return pend <= 2 ? Stage::template go<39, 2, false, uint16_t>(q) : Stage::template go<39, 8, false, uint16_t>(q);
-    if (stack <= 19 && pend <= 2) return launch_stage_sp<Stage, 19, 2>(q);
-    if (stack <= 26 && pend <= 2) return launch_stage_sp<Stage, 26, 2>(q);
-    if (stack <= 31) return pend <= 2 ? launch_stage_sp<Stage, 31, 2>(q) : launch_stage_sp<Stage, 31, 8>(q);
-    if (stack <= 39) return pend <= 2 ? launch_stage_sp<Stage, 39, 2>(q) : launch_stage_sp<Stage, 39, 8>(q);
-    return pend <= 2 ? launch_stage_sp<Stage, 64, 2>(q) : launch_stage_sp<Stage, 64, 8>(q);
-}
-
 hipError_t launch_render_adaptive(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_base,
                                   uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, float4* f32, uint32_t* rgba8, uint32_t* n_rays,
                                   uint32_t* n_taken, int stack, int pend, bool stack16, uint32_t refine_groups, hipStream_t s)
 {
     if (a.W == 0 || a.H == 0 || a.W > 32768u || a.H > 32768u || n_base == 0 || n_base > n_max || n_max > SampleOffsets::MAX) return hipErrorInvalidValue;
     if (stack > 64 || pend > 8) return hipErrorInvalidValue;
-    const uint32_t worst = (uint32_t)(((size_t)a.W * a.H + 255u) / 256u);
-    const AdaptiveLaunch q = { sc, a, cam, off, n_base, n_max, ws, f32, rgba8, n_rays, refine_groups ? std::min(refine_groups, worst) : worst, s };
-    if (hipError_t e = launch_stage<BaseStage>(q, stack, pend, stack16)) return e;
-    const uint32_t groups = (q.n_blocks() + 3u) / 4u;
-    hipLaunchKernelGGL(k_adaptive_classify, dim3(groups), dim3(256), 0, s, a, n_base, n_max, threshold, q.blocks_x(), q.n_blocks(), ws.rec, ws.cnt,
-                       ws.masks, f32, rgba8, n_rays, n_taken);
+    const uint32_t blocks_x = (a.W + 7u) / 8u, n_blocks = blocks_x * ((a.H + 7u) / 8u);         // <= 4096 * 4096
+    const uint32_t groups = (n_blocks + 3u) / 4u, worst = (uint32_t)(((size_t)a.W * a.H + 255u) / 256u);
+    if (refine_groups == 0 || refine_groups > worst) refine_groups = worst;
+    // both traced stages take the scene's FusedVariant through the ray-tree kernels' ladder (for_tree_variant, rr_choice.h)
+    const bool si = sc.single_identity != 0u;
+    const FusedVariant v = { stack, pend, stack16 };
+    if (hipError_t e = for_tree_variant(si, v, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_adaptive_base<T::stack, T::pend, T::tlas, typename T::entry>), dim3(groups), dim3(256), T::lds_bytes, s, sc, a, cam, off,
+                               n_base, blocks_x, n_blocks, ws.rec, ws.cnt);
+            return hipGetLastError();
+        })) return e;
+    hipLaunchKernelGGL(k_adaptive_classify, dim3(groups), dim3(256), 0, s, a, n_base, n_max, threshold, blocks_x, n_blocks, ws.rec, ws.cnt, ws.masks, f32,
+                       rgba8, n_rays, n_taken);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(1024), 0, s, ws.masks, q.n_blocks(), ws.base);
+    hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(1024), 0, s, ws.masks, n_blocks, ws.base);
     if (hipError_t e = hipGetLastError()) return e;
     if (n_base == n_max) return hipSuccess;                     // no samples are left to take: classify has made every pixel final
-    hipLaunchKernelGGL(k_adaptive_list, dim3(groups), dim3(256), 0, s, a.W, q.blocks_x(), q.n_blocks(), ws.masks, ws.base, ws.list);
+    hipLaunchKernelGGL(k_adaptive_list, dim3(groups), dim3(256), 0, s, a.W, blocks_x, n_blocks, ws.masks, ws.base, ws.list);
     if (hipError_t e = hipGetLastError()) return e;
-    return launch_stage<RefineStage>(q, stack, pend, stack16);
+    return for_tree_variant(si, v, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_adaptive_refine<T::stack, T::pend, T::tlas, typename T::entry>), dim3(refine_groups), dim3(256), T::lds_bytes, s, sc, a, cam,
+                           off, n_base, n_max, ws.list, ws.total, ws.rec, ws.cnt, f32, rgba8, n_rays);
+        return hipGetLastError();
+    });
 }
 
 } // namespace rr

@@ -255,6 +255,19 @@ __device__ __forceinline__ f3 ray_tree(const SceneDev& sc, const DispatchDev& a,
     return acc;
 }
 
+// The frame kernels behind a RayGen of their own (k_render_samples, k_adaptive_base / _classify / _list): wave-block wb of a
+// raster of 8x8 blocks, blocks_x to a row, in raster order -> the block's corner (x0, y0) and this lane's pixel (x, y), Morton
+// order inside the block
+struct WavePixel { uint32_t x0, y0, x, y; };
+__device__ __forceinline__ WavePixel wave_pixel(uint32_t wb, uint32_t blocks_x, uint32_t lane)
+{
+    const uint32_t by = wb / blocks_x, bx = wb - by * blocks_x;
+    WavePixel p;
+    p.x0 = bx * 8u; p.y0 = by * 8u;
+    p.x = p.x0 + compact1by1(lane); p.y = p.y0 + compact1by1(lane >> 1);
+    return p;
+}
+
 // RenderTarget[xy] = float4(color,1) -> R8G8B8A8_UNORM (hlsl:62); o: element index inside the slice
 __device__ __forceinline__ void store_pixel(const DispatchDev& a, uint32_t* out_rgba8, float4* out_f32, size_t o, f3 acc)
 {

@@ -9,6 +9,7 @@
 // rays has only if the caller orders it so -- and nothing of a sample ever exists in memory: no ray records, no per-sample
 // colours.  The offsets arrive as kernel arguments and are read with scalar loads (the sample index is wave-uniform).
 #include <hip/hip_runtime.h>
+#include "rr_choice.h"
 #include "rr_render_common.h"
 
 namespace rr {
@@ -26,9 +27,8 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_re
     E* stk = reinterpret_cast<E*>(lds) + wave * (STACK * 64) + lane;
     const uint32_t wb = blockIdx.x * 4u + wave;                 // the wave's 8x8 block, in raster order
     if (wb >= n_blocks) return;
-    const uint32_t by = wb / blocks_x, bx = wb - by * blocks_x;
-    const uint32_t x0 = bx * 8u, y0 = by * 8u;
-    const uint32_t x = x0 + compact1by1(lane), y = y0 + compact1by1(lane >> 1);
+    const WavePixel px = wave_pixel(wb, blocks_x, lane);
+    const uint32_t x0 = px.x0, y0 = px.y0, x = px.x, y = px.y;
     if (x >= a.W || y >= a.H) return;                           // lanes outside the frame trace nothing and store nothing
     // A block outside the scene's screen rectangle is background: every sample is RayGen and one Miss on its own direction,
     // without TraceRay (k_render_fused's branch).  The rectangle (rr_host_screen_rect) holds the projection of the scene's box
@@ -61,43 +61,19 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_re
     if (out_n) out_n[o] = st.rays;
 }
 
-struct SamplesLaunch {
-    const SceneDev& sc; const DispatchDev& a; const CamDev& cam; const SampleOffsets& off; uint32_t n_samples;
-    float4* f32; uint32_t* rgba8; uint32_t* n_rays; hipStream_t s;
-};
-
-template <int STACK, int PEND, bool TLAS, class E>
-static hipError_t launch_samples(const SamplesLaunch& q)
-{
-    const size_t lds = (size_t)4 * STACK * 64 * sizeof(E);
-    const uint32_t blocks_x = (q.a.W + 7u) / 8u, n_blocks = blocks_x * ((q.a.H + 7u) / 8u);     // <= 4096 * 4096
-    hipLaunchKernelGGL((k_render_samples<STACK, PEND, TLAS, E>), dim3((n_blocks + 3u) / 4u), dim3(256), lds, q.s, q.sc, q.a, q.cam, q.off,
-                       q.n_samples, blocks_x, n_blocks, q.f32, q.rgba8, q.n_rays);
-    return hipGetLastError();
-}
-
-template <int STACK, int PEND>
-static hipError_t launch_samples_sp(const SamplesLaunch& q)
-{
-    if (!q.sc.single_identity) return launch_samples<STACK, PEND, true, uint32_t>(q);
-    return launch_samples<STACK, PEND, false, uint32_t>(q);
-}
-
-// stack, pend, stack16: a FusedVariant (rr_choice.h) of the scene -- launch_shade_rays' ladder
+// stack, pend, stack16: a FusedVariant of the scene, through the ray-tree kernels' ladder (for_tree_variant, rr_choice.h)
 hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_samples,
                                  float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s)
 {
     if (a.W == 0 || a.H == 0 || a.W > 32768u || a.H > 32768u || n_samples == 0 || n_samples > SampleOffsets::MAX) return hipErrorInvalidValue;
     if (stack > 64 || pend > 8) return hipErrorInvalidValue;
-    const SamplesLaunch q = { sc, a, cam, off, n_samples, f32, rgba8, n_rays, s };
-    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 30) return launch_samples<30, 2, true, uint16_t>(q);
-    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 39) return launch_samples<39, 2, true, uint16_t>(q);
-    if (stack16 && sc.single_identity && stack <= 39) return pend <= 2 ? launch_samples<39, 2, false, uint16_t>(q) : launch_samples<39, 8, false, uint16_t>(q);
-    if (stack <= 19 && pend <= 2) return launch_samples_sp<19, 2>(q);
-    if (stack <= 26 && pend <= 2) return launch_samples_sp<26, 2>(q);
-    if (stack <= 31) return pend <= 2 ? launch_samples_sp<31, 2>(q) : launch_samples_sp<31, 8>(q);
-    if (stack <= 39) return pend <= 2 ? launch_samples_sp<39, 2>(q) : launch_samples_sp<39, 8>(q);
-    return pend <= 2 ? launch_samples_sp<64, 2>(q) : launch_samples_sp<64, 8>(q);
+    const uint32_t blocks_x = (a.W + 7u) / 8u, n_blocks = blocks_x * ((a.H + 7u) / 8u);         // <= 4096 * 4096
+    return for_tree_variant(sc.single_identity != 0u, FusedVariant{ stack, pend, stack16 }, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_render_samples<T::stack, T::pend, T::tlas, typename T::entry>), dim3((n_blocks + 3u) / 4u), dim3(256), T::lds_bytes, s, sc, a,
+                           cam, off, n_samples, blocks_x, n_blocks, f32, rgba8, n_rays);
+        return hipGetLastError();
+    });
 }
 
 } // namespace rr

@@ -8,6 +8,7 @@
 // gives the pixel with that primary ray.  One lane per ray, a wave is 64 consecutive rays: what coherence the batch has is the
 // caller's order (DESIGN 5.5 has the cost of the orders measured).
 #include <hip/hip_runtime.h>
+#include "rr_choice.h"
 #include "rr_render_common.h"
 
 namespace rr {
@@ -38,40 +39,18 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_sh
     if (out_n) out_n[i] = st.rays;
 }
 
-template <int STACK, int PEND, bool TLAS, class E>
-static hipError_t launch_shade(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
-                               uint32_t* n_rays, hipStream_t s)
-{
-    const size_t lds = (size_t)4 * STACK * 64 * sizeof(E);
-    hipLaunchKernelGGL((k_shade_rays<STACK, PEND, TLAS, E>), dim3((n + 255u) / 256u), dim3(256), lds, s, sc, a, rays, n, f32, rgba8, n_rays);
-    return hipGetLastError();
-}
-
-template <int STACK, int PEND>
-static hipError_t launch_shade_sp(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
-                                  uint32_t* n_rays, hipStream_t s)
-{
-    if (!sc.single_identity) return launch_shade<STACK, PEND, true, uint32_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    return launch_shade<STACK, PEND, false, uint32_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
-}
-
-// stack, pend, stack16: a FusedVariant (rr_choice.h) of the scene -- the ladder of launch_render_fused without its 22-entry
-// rung (seven waves per SIMD against six: DESIGN 5.5)
+// stack, pend, stack16: a FusedVariant of the scene, through the ray-tree kernels' ladder (for_tree_variant, rr_choice.h)
 hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
                              uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
     if (stack > 64 || pend > 8) return hipErrorInvalidValue;
-    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 30) return launch_shade<30, 2, true, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack16 && !sc.single_identity && pend <= 2 && stack <= 39) return launch_shade<39, 2, true, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack16 && sc.single_identity && stack <= 39)
-        return pend <= 2 ? launch_shade<39, 2, false, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s)
-                         : launch_shade<39, 8, false, uint16_t>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack <= 19 && pend <= 2) return launch_shade_sp<19, 2>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack <= 26 && pend <= 2) return launch_shade_sp<26, 2>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack <= 31) return pend <= 2 ? launch_shade_sp<31, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<31, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    if (stack <= 39) return pend <= 2 ? launch_shade_sp<39, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<39, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
-    return pend <= 2 ? launch_shade_sp<64, 2>(sc, a, rays, n, f32, rgba8, n_rays, s) : launch_shade_sp<64, 8>(sc, a, rays, n, f32, rgba8, n_rays, s);
+    return for_tree_variant(sc.single_identity != 0u, FusedVariant{ stack, pend, stack16 }, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_shade_rays<T::stack, T::pend, T::tlas, typename T::entry>), dim3((n + 255u) / 256u), dim3(256), T::lds_bytes, s, sc, a, rays,
+                           n, f32, rgba8, n_rays);
+        return hipGetLastError();
+    });
 }
 
 } // namespace rr

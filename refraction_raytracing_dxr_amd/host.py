@@ -138,6 +138,38 @@ def pack_rays(origin, dir, tmin, tmax, flags=0, instance_mask=0xff):
     return rays
 
 
+def _outputs(shape, rgba8, counts, device=None):
+    """The outputs of shade_rays, render_samples and render_adaptive for `shape` rays or pixels: float32 shape + (4,), the uint8
+    store of the same shape if rgba8, and one count array of `shape` per true entry of counts (None where not asked for) -- numpy
+    arrays with uint32 counts, or with device new torch tensors there with int32 counts -> (arrays, their pointers as the C ABI
+    takes them: null for an output not asked for and for an empty tensor)."""
+    if device is None:
+        outs = [np.zeros(shape + (4,), np.float32), np.zeros(shape + (4,), np.uint8) if rgba8 else None]
+        outs += [np.zeros(shape, np.uint32) if c else None for c in counts]
+        return outs, [a.ctypes.data if a is not None else None for a in outs]
+    import torch
+    outs = [torch.empty(shape + (4,), dtype=torch.float32, device=device),
+            torch.empty(shape + (4,), dtype=torch.uint8, device=device) if rgba8 else None]
+    outs += [torch.empty(shape, dtype=torch.int32, device=device) if c else None for c in counts]
+    return outs, [C.c_void_p(t.data_ptr() if t is not None and t.numel() else None) for t in outs]
+
+
+def _result(outs):
+    out = tuple(a for a in outs if a is not None)
+    return out if len(out) > 1 else out[0]
+
+
+def _sample_offsets(samples, complaint):
+    """samples: an int (a built-in pattern) or an [S, 2] array of offsets -> (pointer to the float32 offsets or None, S); the
+    pointer keeps its array alive"""
+    if isinstance(samples, (int, np.integer)):
+        return None, int(samples)
+    off = np.ascontiguousarray(samples, np.float32)
+    if off.ndim != 2 or off.shape[1] != 2:
+        raise ValueError(complaint)
+    return (off.ctypes.data_as(C.c_void_p) if off.shape[0] else None), off.shape[0]
+
+
 class Mesh:
     """Mesh.hpp:14-25.  verts: structured array of 32-byte Vertex; indices: uint32."""
 
@@ -511,23 +543,13 @@ class Renderer:
             if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
                 raise ValueError("shade_rays: need a contiguous [n, 12] int32 or float32 tensor")
             n = t.shape[0]
-            f32 = torch.empty((n, 4), dtype=torch.float32, device=t.device)
-            u8 = torch.empty((n, 4), dtype=torch.uint8, device=t.device) if rgba8 else None
-            cnt = torch.empty((n,), dtype=torch.int32, device=t.device) if ray_counts else None
-            self._ck(self._L.rr_shade_rays_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p),
-                                                  C.c_void_p(f32.data_ptr() if n else None),
-                                                  C.c_void_p(u8.data_ptr() if u8 is not None and n else None),
-                                                  C.c_void_p(cnt.data_ptr() if cnt is not None and n else None)), "rr_shade_rays_device")
+            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
+            self._ck(self._L.rr_shade_rays_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs), "rr_shade_rays_device")
         else:
             rays = np.ascontiguousarray(rays, RAY_DTYPE)
-            n = len(rays)
-            f32 = np.zeros((n, 4), np.float32)
-            u8 = np.zeros((n, 4), np.uint8) if rgba8 else None
-            cnt = np.zeros(n, np.uint32) if ray_counts else None
-            self._ck(self._L.rr_shade_rays(self._h, rays.ctypes.data, n, C.byref(p), f32.ctypes.data,
-                                           u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_shade_rays")
-        out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
-        return out if len(out) > 1 else f32
+            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
+            self._ck(self._L.rr_shade_rays(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays")
+        return _result(outs)
 
     def render_samples(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
         """Supersampled frame (rr_render_samples): every pixel of a width x height frame takes S primary rays through S sub-pixel
@@ -544,34 +566,15 @@ class Renderer:
         int32), computed on the renderer's stream without waiting for it (stream order as query_rays)."""
         p = params if params is not None else default_params()
         w, h = int(width), int(height)
-        if isinstance(samples, (int, np.integer)):
-            off, n = None, int(samples)
-        else:
-            off = np.ascontiguousarray(samples, np.float32)
-            if off.ndim != 2 or off.shape[1] != 2:
-                raise ValueError("render_samples: samples must be an int or an [S, 2] array")
-            n = off.shape[0]
+        offp, n = _sample_offsets(samples, "render_samples: samples must be an int or an [S, 2] array")
         if n < 0 or w < 0 or h < 0:
             raise ValueError("render_samples: negative size")
-        offp = off.ctypes.data if off is not None and n else None
-        shape = (max(h, 0), max(w, 0))
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
         if device:
-            import torch
-            dev = "cuda:%d" % self.device
-            f32 = torch.empty(shape + (4,), dtype=torch.float32, device=dev)
-            u8 = torch.empty(shape + (4,), dtype=torch.uint8, device=dev) if rgba8 else None
-            cnt = torch.empty(shape, dtype=torch.int32, device=dev) if ray_counts else None
-            self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, C.c_void_p(f32.data_ptr() if w * h else None),
-                                                      C.c_void_p(u8.data_ptr() if u8 is not None and w * h else None),
-                                                      C.c_void_p(cnt.data_ptr() if cnt is not None and w * h else None)), "rr_render_samples_device")
+            self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples_device")
         else:
-            f32 = np.zeros(shape + (4,), np.float32)
-            u8 = np.zeros(shape + (4,), np.uint8) if rgba8 else None
-            cnt = np.zeros(shape, np.uint32) if ray_counts else None
-            self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, f32.ctypes.data,
-                                               u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None), "rr_render_samples")
-        out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ())
-        return out if len(out) > 1 else f32
+            self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples")
+        return _result(outs)
 
     def render_adaptive(self, width, height, camera, samples=(4, 16), threshold=ADAPTIVE_THRESHOLD, params=None, rgba8=False, ray_counts=False,
                         sample_counts=False, device=False):
@@ -590,24 +593,12 @@ class Renderer:
         w, h = int(width), int(height)
         n_base, top = samples
         n_base = int(n_base)
-        if isinstance(top, (int, np.integer)):
-            off, n_max = None, int(top)
-        else:
-            off = np.ascontiguousarray(top, np.float32)
-            if off.ndim != 2 or off.shape[1] != 2:
-                raise ValueError("render_adaptive: samples must be (n_base, n_max) or (n_base, [S, 2] array)")
-            n_max = off.shape[0]
+        offp, n_max = _sample_offsets(top, "render_adaptive: samples must be (n_base, n_max) or (n_base, [S, 2] array)")
         if n_base < 0 or n_max < 0 or w < 0 or h < 0:
             raise ValueError("render_adaptive: negative size")
-        offp = off.ctypes.data if off is not None and n_max else None
-        shape = (h, w)
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts, sample_counts), "cuda:%d" % self.device if device else None)
         if device:
             import torch
-            dev = "cuda:%d" % self.device
-            f32 = torch.empty(shape + (4,), dtype=torch.float32, device=dev)
-            u8 = torch.empty(shape + (4,), dtype=torch.uint8, device=dev) if rgba8 else None
-            cnt = torch.empty(shape, dtype=torch.int32, device=dev) if ray_counts else None
-            taken = torch.empty(shape, dtype=torch.int32, device=dev) if sample_counts else None
             nbytes = int(self._L.rr_host_adaptive_workspace_bytes(w, h))
             # one workspace per stream the renderer has been put on, reused call after call: the calls on a stream are ordered,
             # calls on different streams are not and never share one.  Before a larger one replaces it that stream is waited
@@ -618,22 +609,14 @@ class Renderer:
             if ws is None or ws.numel() * 4 < nbytes:
                 if ws is not None:
                     self.wait()
-                ws = pool[key] = torch.empty((max(nbytes, 16) // 16, 4), dtype=torch.float32, device=dev)
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and w * h else None)
-            self._ck(self._L.rr_render_adaptive_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), ptr(f32),
-                                                       ptr(u8), ptr(cnt), ptr(taken), C.c_void_p(ws.data_ptr()), ws.numel() * 4),
-                     "rr_render_adaptive_device")
-            out = (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ()) + ((taken,) if sample_counts else ())
-            return out if len(out) > 1 else f32
-        f32 = np.zeros(shape + (4,), np.float32)
-        u8 = np.zeros(shape + (4,), np.uint8) if rgba8 else None
-        cnt = np.zeros(shape, np.uint32) if ray_counts else None
-        taken = np.zeros(shape, np.uint32) if sample_counts else None
+                ws = pool[key] = torch.empty((max(nbytes, 16) // 16, 4), dtype=torch.float32, device="cuda:%d" % self.device)
+            self._ck(self._L.rr_render_adaptive_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), *ptrs,
+                                                       C.c_void_p(ws.data_ptr()), ws.numel() * 4), "rr_render_adaptive_device")
+            return _result(outs)
         n_ref = C.c_uint64(0)
-        self._ck(self._L.rr_render_adaptive(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), f32.ctypes.data,
-                                            u8.ctypes.data if rgba8 else None, cnt.ctypes.data if ray_counts else None,
-                                            taken.ctypes.data if sample_counts else None, C.byref(n_ref)), "rr_render_adaptive")
-        return (f32,) + ((u8,) if rgba8 else ()) + ((cnt,) if ray_counts else ()) + ((taken,) if sample_counts else ()) + (int(n_ref.value),)
+        self._ck(self._L.rr_render_adaptive(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), *ptrs,
+                                            C.byref(n_ref)), "rr_render_adaptive")
+        return tuple(a for a in outs if a is not None) + (int(n_ref.value),)
 
     def env_lookup(self, dirs):
         """Miss (RayTracing.hlsl:127-137) on an [n,3] array of directions -> [n,3] texels."""

@@ -3,6 +3,8 @@
 //   pick <single need blas_tris pool_nodes pool_refs lds_fits> <depth n_tiles world compact mesh have_rect share refract reflect
 //        no_cull diag> <dbg_kernel dbg_stack tlas32>          -> kernel cls cand_a cand_b kernel-before-any-measurement
 //   fused <scene facts as pick> <depth reflect> <dbg_kernel dbg_stack tlas32>   -> stack pend stack16
+//   tree <single stack pend stack16>                         -> STACK PEND TLAS bits: the ray-tree kernels' instantiation
+//                                                               (for_tree_variant), bits = 16 or 32 per stack entry
 //   key <W H refract reflect depth>                          -> choice_key
 //   new                                                      -> (a fresh class) ok
 //   due <key share no_cull>        -> find + measure_due: due choice seen
@@ -64,6 +66,15 @@ int main()
             const DebugFacts d = read_debug(in);
             const FusedVariant v = fused_variant(s, depth, reflect, d);
             printf("%d %d %d\n", v.stack, v.pend, v.stack16 ? 1 : 0);
+        } else if (cmd == "tree") {
+            int single, stack16;
+            FusedVariant v;
+            in >> single >> v.stack >> v.pend >> stack16;
+            v.stack16 = stack16 != 0;
+            for_tree_variant(single != 0, v, [](auto t) {
+                using T = decltype(t);
+                return printf("%d %d %d %d\n", T::stack, T::pend, T::tlas ? 1 : 0, (int)(8 * sizeof(typename T::entry)));
+            });
         } else if (cmd == "key") {
             uint32_t w, h, depth;
             rr_dispatch_params p = {};

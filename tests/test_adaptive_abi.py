@@ -3,18 +3,16 @@ generation of its kernels."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 import refraction_raytracing_dxr_amd as rr
+from codeobj import HAVE_OBJDUMP, LAUNCHABLE, kernels, template_args
 from refraction_raytracing_dxr_amd import _capi
-from test_samples_abi import LAUNCHABLE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rrdxr.h")
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 RR_ERR_INVALID_ARGUMENT = 1
 _P = C.c_void_p
 _SC, _DP = C.POINTER(_capi.SceneConstants), C.POINTER(_capi.DispatchParams)
@@ -77,36 +75,12 @@ def test_workspace_bytes():
         assert ws(w, h) == 0, (w, h)
 
 
-def _kernels(tmp_path):
-    """{demangled kernel name: scratch_ instructions} of the gfx950 code objects of librrdxr.so"""
-    import refraction_raytracing_dxr_amd._build as B
-    so = tmp_path / "librrdxr.so"
-    shutil.copy(B.build(), so)
-    subprocess.run([OBJDUMP, "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    kernels = {}
-    for f in sorted(tmp_path.iterdir()):
-        if "gfx950" not in f.name:
-            continue
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "-C", str(f)], check=True, capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.split("\n"):
-            m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
-            if m:
-                cur = m.group(1)
-                kernels[cur] = 0
-                continue
-            if cur and line.strip().startswith("scratch_"):
-                kernels[cur] += 1
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
+@pytest.mark.skipif(not HAVE_OBJDUMP, reason="llvm-objdump of the ROCm toolchain not found")
 def test_adaptive_kernels_exist(tmp_path):
     """every rung of the ladder has its k_adaptive_base and k_adaptive_refine in the gfx950 code object, the three image passes
     are there, and k_render_samples / k_shade_rays still have every instantiation under its name.  The scratch_ instructions are
     printed next to those of k_render_samples (no assertion on the counts: DESIGN 5.7 records them)."""
-    k = _kernels(tmp_path)
-    b = {True: "true", False: "false"}
+    k = {n: v["scratch"] for n, v in kernels(tmp_path).items()}
     for name in ("k_adaptive_classify", "k_adaptive_scan", "k_adaptive_list"):
         got = [n for n in k if re.search(r"\b%s\(" % name, n)]
         assert len(got) == 1, (name, got)
@@ -115,8 +89,8 @@ def test_adaptive_kernels_exist(tmp_path):
         assert len([n for n in k if stage + "<" in n]) == len(LAUNCHABLE), stage
     for old in ("k_render_samples", "k_shade_rays"):
         assert len([n for n in k if old + "<" in n]) == len(LAUNCHABLE), old
-    for stack, pend, tlas, e in LAUNCHABLE:
-        args = "<%d, %d, %s, %s>" % (stack, pend, b[tlas], e)
+    for variant in LAUNCHABLE:
+        args = template_args(*variant)
         counts = []
         for kernel in ("k_adaptive_base", "k_adaptive_refine", "k_render_samples", "k_shade_rays"):
             got = [v for n, v in k.items() if kernel + args in n]

@@ -9,82 +9,13 @@ import pytest
 
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
-from test_gpu_samples import CELL16, ENV, SUB4, H, W, fold, view_constants
+from shading_helpers import ADAPTIVE_VIEWS as VIEWS
+from shading_helpers import CELL16, OFFP16, PERM16, THRESHOLD, H, W, adaptive_reference, display, fold, oracle_colours, view_constants
 
 F = np.float32
-# the 16 sub-pixels of a 4x4 cell, the built-in 4x pattern first: a pattern whose prefix of 4 is a pattern of its own
-PERM16 = list(SUB4) + [c for c in CELL16 if c not in SUB4]
-OFFP16 = np.array([[(2 * i + 1) / 8.0, (2 * j + 1) / 8.0] for i, j in PERM16], np.float32)
-# The views and the threshold of the GPU test.  The threshold is a tenth of a channel's displayed range: the oracle's frames below
-# then have both classes and both causes well above the floors the tests assert (the figures are printed).
-VIEWS = [(0.01, rr.FOV_Y), (1.3, 0.35)]
-THRESHOLD = 0.1
-
-
-def display(c, tonemap):
-    """step 2: what store_pixel shows of a channel value, in [0, 1] (np.fmax / np.fmin return the operand that is a number)"""
-    m = np.fmax(np.asarray(c, F), F(0))
-    if tonemap:
-        with np.errstate(invalid="ignore"):
-            m = m / (F(1) + m)                                  # inf / inf = NaN, which fmin turns into 1
-    v = np.fmin(m, F(1))
-    assert v.dtype == F
-    return v
-
-
-def adaptive_reference(colours, n_base, threshold, tonemap):
-    """colours [S, h, w, 3] float32, sample s of every pixel -> (mask [h, w] bool, resolved [h, w, 3], r_own [h, w], r_nb [h, w])"""
-    colours = np.asarray(colours)
-    assert colours.dtype == F and colours.ndim == 4 and colours.shape[3] == 3
-    S, h, w, _ = colours.shape
-    assert 1 <= n_base <= S
-    t = F(threshold)
-    with np.errstate(invalid="ignore", over="ignore"):
-        sum_b = colours[0].copy()                               # 1. the fold starts AT c_0
-        for s in range(1, n_base):
-            sum_b = sum_b + colours[s]
-        v = display(colours[:n_base], tonemap)                  # 3. own contrast
-        r_own = (np.fmax.reduce(v, axis=0) - np.fmin.reduce(v, axis=0)).max(axis=-1)
-        base = sum_b / F(n_base)
-        b = display(base, tonemap)                              # 4. neighbour contrast
-        r_nb = np.zeros((h, w), F)
-        dx = np.abs(b[:, 1:] - b[:, :-1]).max(axis=-1)
-        dy = np.abs(b[1:] - b[:-1]).max(axis=-1)
-        r_nb[:, 1:] = np.maximum(r_nb[:, 1:], dx)
-        r_nb[:, :-1] = np.maximum(r_nb[:, :-1], dx)
-        r_nb[1:] = np.maximum(r_nb[1:], dy)
-        r_nb[:-1] = np.maximum(r_nb[:-1], dy)
-        mask = (r_own > t) | (r_nb > t)                         # 5.
-        full = sum_b
-        for s in range(n_base, S):                              # 6. a refined pixel continues the same fold
-            full = full + colours[s]
-        out = np.where(mask[..., None], full / F(S), base)
-    assert out.dtype == F and r_own.dtype == F and r_nb.dtype == F
-    return mask, out, r_own, r_nb
 
 
 # ------------------------------------------------------------------------------------------------- the oracle's colours
-_cache = {}
-
-
-def oracle_colours(angle, fov, **kw):
-    """(colours [16, H, W, 3] in PERM16's order, counts [16, H, W]) of monkey.obj from the CPU oracle's 4W x 4H frame"""
-    key = (angle, fov, tuple(sorted(kw.items())))
-    if key not in _cache:
-        if "scene" not in _cache:
-            from conftest import procedural_env
-            m = rr.Mesh()
-            assert m.load(O.asset("monkey.obj"))
-            s = O.Scene()
-            s.add_mesh(m.verts, m.indices)
-            s.set_envmap(procedural_env(ENV["w"], ENV["h"], seed=ENV["seed"]))
-            _cache["scene"] = s
-        _, M, cam = view_constants(angle, fov)
-        ref = _cache["scene"].render(M, cam, 4 * W, 4 * H, O.default_params(use_bvh=1, accum_mode=1, use_libm=0, **kw), want_rays=True)
-        rgb = ref["rgb"].reshape(H, 4, W, 4, 3).transpose(1, 3, 0, 2, 4)
-        cnt = ref["rays"].astype(np.uint32).reshape(H, 4, W, 4).transpose(1, 3, 0, 2)
-        _cache[key] = (np.stack([rgb[j, i] for i, j in PERM16]), np.stack([cnt[j, i] for i, j in PERM16]))
-    return _cache[key]
 
 
 def scene_rect(angle, fov):

@@ -3,52 +3,14 @@ kernels this round put on a diet are checked for what the diet removed -- scalar
 (v_readlane / v_writelane: vector instructions that do no work), scratch in the hot kernels.  The compiler's choices here turned
 out to hinge on details as remote as the layout of an argument struct, so a change that brings the spills back
 should fail a test, not wait for a benchmark."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+from codeobj import HAVE_OBJDUMP, kernels
 
 
-def _kernels(tmp_path):
-    import refraction_raytracing_dxr_amd._build as B
-    lib = B.build()
-    work = tmp_path / "co"
-    work.mkdir()
-    so = work / "librrdxr.so"
-    shutil.copy(lib, so)
-    subprocess.run([OBJDUMP, "--offloading", str(so)], check=True, capture_output=True, cwd=work)
-    out = {}
-    for f in sorted(work.iterdir()):
-        if "gfx950" not in f.name:
-            continue
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "-C", str(f)], check=True, capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.split("\n"):
-            m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
-            if m:
-                cur = m.group(1)
-                out.setdefault(cur, {"lane": 0, "scratch": 0, "valu": 0})
-                continue
-            if cur is None:
-                continue
-            ins = line.strip().split(" ")[0] if line.strip() else ""
-            if ins.startswith(("v_readlane", "v_writelane")):
-                out[cur]["lane"] += 1
-            if ins.startswith("scratch_"):
-                out[cur]["scratch"] += 1
-            if ins.startswith("v_"):
-                out[cur]["valu"] += 1
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
+@pytest.mark.skipif(not HAVE_OBJDUMP, reason="llvm-objdump of the ROCm toolchain not found")
 def test_hot_kernels_do_not_spill_scalars_through_vector_lanes(tmp_path):
-    k = _kernels(tmp_path)
+    k = kernels(tmp_path)
 
     def find(sub):
         hits = [(n, v) for n, v in k.items() if sub in n]

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 import refraction_raytracing_dxr_amd as rr
-from test_adaptive_cpu import OFFP16, THRESHOLD, VIEWS, adaptive_reference, oracle_colours
-from test_gpu_samples import LIMITS, H, W, config4_scene, env_map, unorm8, view_constants
-from test_gpu_shade import STAT_FIELDS, gpu_scene, load
+from shading_helpers import ADAPTIVE_VIEWS as VIEWS
+from shading_helpers import (LIMITS, OFFP16, STAT_FIELDS, THRESHOLD, H, W, adaptive_reference, config4_scene, env_map, gpu_scene, load, oracle_colours,
+                             unorm8, view_constants)
 
 pytestmark = pytest.mark.gpu
 

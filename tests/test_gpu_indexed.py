@@ -19,11 +19,11 @@ import indexed_meshes as IM
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from test_gpu_kernels_oracle import (FUSED, KERNEL_ID, LDS, PATHS, STREAM, Scene, check_launch, counters, dispatch, load,  # noqa: F401
+from kernel_oracle_helpers import (FUSED, KERNEL_ID, LDS, PATHS, STREAM, Scene, check_launch, counters, dispatch, load,  # noqa: F401
                                      make_renderer, orbit, report, xf)
-from test_gpu_query import check_closest, oracle_scene as bare_oracle_scene, random_rays
-from test_gpu_refit import blas_bytes, deform
-from test_gpu_shade import camera_rays, check_against_oracle, view_constants
+from query_helpers import check_closest, oracle_scene as bare_oracle_scene, random_rays
+from refit_helpers import blas_bytes, deform
+from shading_helpers import camera_rays, check_against_oracle, view_constants
 
 pytestmark = pytest.mark.gpu
 

@@ -20,238 +20,21 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from test_gpu_parity import CULL_KINDS, CULL_SIZES, FRAME_CASES, adversarial_constants
+from kernel_oracle_helpers import (check_launch,  # noqa: F401  (make_renderer: a fixture)
+                                   check_slice, COUNTERS, counters, dispatch, FUSED, KERNEL_ID, load, make_renderer, oracle_frame,
+                                   orbit, PATHS, report, Scene, STREAM, xf)
+from parity_cases import adversarial_constants, CULL_KINDS, CULL_SIZES, FRAME_CASES
 
 pytestmark = pytest.mark.gpu
 
-FUSED, LDS, PATHS, STREAM = 0, 1, 2, 7
-KERNEL_ID = {"fused": FUSED, "lds": LDS, "paths": PATHS, "stream": STREAM}
-COUNTERS = ("rays", "hits", "misses", "terminal_hits", "tir")
-DEBUG_VARS = ("RR_DEBUG_KERNEL", "RR_DEBUG_SHAPE", "RR_DEBUG_TICKET", "RR_DEBUG_GROUP_TRACE", "RR_DEBUG_STACK", "RR_DEBUG_TLAS32",
-              "RR_DEBUG_TILE_ORDER", "RR_DEBUG_ASYNC", "RR_DEBUG_DIAG")
-TALLY = collections.Counter()           # oracle comparisons per asserted render_kernel, over the module (printed by each test)
-
-
-@pytest.fixture
-def make_renderer(monkeypatch):
-    """make(kernel, **env) -> a Renderer created with RR_DEBUG_KERNEL=kernel (and the given RR_DEBUG_* switches), closed at
-    teardown"""
-    made = []
-
-    def make(kernel, **env):
-        for k in DEBUG_VARS:
-            monkeypatch.delenv(k, raising=False)
-        monkeypatch.setenv("RR_DEBUG_KERNEL", kernel)
-        for k, v in env.items():
-            monkeypatch.setenv(k, str(v))
-        r = rr.Renderer(0)
-        made.append(r)
-        return r
-    yield make
-    for r in made:
-        r.close()
-
 
 # ------------------------------------------------------------------------------------------------------- scenes
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m.verts, m.indices
-
-
-def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
-    c, sn = np.cos(rot), np.sin(rot)
-    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
-    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
-
-
-class Scene:
-    """meshes [(verts, indices)], instances (blas = index into meshes; None: the reference's one identity instance), env"""
-
-    def __init__(self, key, meshes, env, instances=None):
-        self.key, self.meshes, self.env, self.instances = key, meshes, env, instances
-        self._oracle = None
-        self.single = instances is None
-        lo, hi = [], []
-        for k in range(1 if instances is None else len(instances)):
-            V, I = meshes[0 if instances is None else int(instances["blas"][k])]
-            P = V["position"][np.asarray(I, np.int64)].astype(np.float64)      # the referenced vertices: what the BLAS bounds
-            if instances is not None:
-                T = instances["transform"][k].reshape(3, 4).astype(np.float64)
-                P = P @ T[:, :3].T + T[:, 3]
-            lo.append(P.min(axis=0)); hi.append(P.max(axis=0))
-        self.bounds = (C.c_float * 6)(*[float(v) for v in np.min(lo, axis=0)], *[float(v) for v in np.max(hi, axis=0)])
-
-    def load_gpu(self, r):
-        ids = []
-        for v, i in self.meshes:
-            mid = r.upload_mesh(v, i)
-            r.build_blas(mid)
-            ids.append(mid)
-        if self.instances is None:
-            inst = rr.make_instances(meshes=[ids[0]])
-        else:
-            inst = self.instances.copy()
-            inst["blas"] = [ids[int(b)] for b in inst["blas"]]
-        r.build_tlas(inst)
-        r.upload_envmap(self.env)
-        r.set_tile_partition(0, 1)
-
-    def oracle(self):
-        if self._oracle is None:
-            s = O.Scene()
-            for v, i in self.meshes:
-                s.add_mesh(v, i)
-            if self.instances is not None:
-                inst = np.zeros(len(self.instances), O.INSTANCE_DTYPE)
-                inst["transform"] = self.instances["transform"]
-                inst["id_mask"] = self.instances["instance_id_mask"]
-                inst["hitgroup_flags"] = self.instances["hitgroup_flags"]
-                inst["blas"] = self.instances["blas"]
-                s.set_instances(inst)
-            s.set_envmap(self.env)
-            self._oracle = s
-        return self._oracle
-
-    def n_tris(self):
-        return len(self.meshes[0][1]) // 3
-
-
-_ORACLE_CACHE = {}
-
-
-def oracle_frame(scene, sc, W, H, kw, tonemap=0, region=None):
-    """the oracle's path-weight render of one slice, cached across kernels (same scene, constants, size and parameters)"""
-    M, cam = np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
-    key = (scene.key, M.tobytes(), cam.tobytes(), W, H, tuple(sorted(kw.items())), tonemap, region)
-    if key not in _ORACLE_CACHE:
-        if len(_ORACLE_CACHE) > 400:
-            _ORACLE_CACHE.clear()
-        _ORACLE_CACHE[key] = scene.oracle().render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, tonemap=tonemap, **kw),
-                                                   region=region)
-    return _ORACLE_CACHE[key]
-
-
-def orbit(angle, n, step=0.13, radius=1.0, height=None):
-    """n distinct orbit constants starting at `angle` (a batch's slices each get their own camera)"""
-    out = []
-    for f in range(n):
-        sc = rr.camera_orbit(angle + step * f)
-        sc.camera_loc[0] *= radius
-        sc.camera_loc[2] *= radius
-        if height is not None:
-            sc.camera_loc[1] = height
-        out.append(sc)
-    return out
 
 
 # ------------------------------------------------------------------------------------ which kernel can render a launch
-def _lds_shape_fits(node_bytes, stack_entries, min_shape):
-    """rr_render.hip lds_kernel_shape: 12x2, 16x2, 16x1 waves x workgroups per CU within 160 KiB of LDS per CU"""
-    for nw, wgs in ((12, 2), (16, 2), (16, 1))[min_shape:]:
-        if node_bytes + nw * stack_entries * 64 * 2 <= 160 * 1024 // wgs - 512:
-            return True
-        if min_shape <= 0:
-            return False
-    return False
-
-
-def screen_rect(scene, cams, W, H):
-    arr = (rr._capi.SceneConstants * len(cams))(*cams)
-    rect = (C.c_uint32 * 4)()
-    assert rr.lib().rr_host_screen_rect(scene.bounds, arr, len(cams), W, H, rect) == 0
-    return list(rect)
-
-
-def expected_kernel(kernel, scene, W, H, cams, kw, need, flags=0, shape=0, sharded=False):
-    """the kernel the forced switch must have rendered the launch with (rr_choice.cpp pick_kernel)"""
-    depth = len(cams)
-    refl = kw.get("max_reflect", 2)
-    if kernel == "lds":
-        n = scene.n_tris()
-        n_tiles = ((W + 31) // 32) * ((H + 31) // 32)
-        ok = (scene.single and n < 32768 and _lds_shape_fits(max(n - 1, 1) * 32, need + 1, shape) and n_tiles * depth * depth < 1 << 30
-              and not sharded)
-        return LDS if ok else FUSED
-    if kernel == "paths":
-        r = [0, 0, W, H] if flags & rr.DISPATCH_DEBUG_NO_CULL else screen_rect(scene, cams, W, H)
-        ok = not sharded and refl <= 2 and need <= 39 and r[2] > r[0] and r[3] > r[1] and depth <= 2
-        return PATHS if ok else FUSED
-    if kernel == "stream":
-        ok = not scene.single and refl <= 2 and kw.get("max_refract", 5) <= 62 and need <= 39
-        return STREAM if ok else FUSED
-    return FUSED
 
 
 # ------------------------------------------------------------------------------------------------- dispatch + compare
-def dispatch(r, W, H, cams, kw, flags):
-    p = rr.default_params(flags=flags | rr.DISPATCH_COLLECT_STATS, **kw)
-    if len(cams) == 1:
-        r.set_camera(cams[0])
-        r.dispatch_rays(W, H, p)
-    else:
-        r.dispatch_rays_batch(W, H, cams, p)
-    want_f = bool(flags & rr.DISPATCH_FLOAT_OUTPUT)
-    frames = []
-    for f in range(len(cams)):
-        got = r.read_frame(want_float=want_f, slice=f)
-        frames.append(got if want_f else (got, None))
-    st = r.stats()
-    assert st.traversal_overflow == 0 and st.stats_valid
-    return frames, st
-
-
-def counters(st):
-    return tuple(int(getattr(st, k)) for k in COUNTERS)
-
-
-def check_slice(rgba, f32, ref, tag):
-    assert np.all(rgba[..., 3] == 255), tag
-    if f32 is not None:
-        assert np.all(f32[..., 3] == 1.0), tag
-        d = np.argwhere(f32[..., :3].view(np.uint32) != ref["rgb"].view(np.uint32))
-        assert len(d) == 0, "%s: %d float channels differ, first at %s: %r / %r" % (tag, len(d), d[0], f32[tuple(d[0])], ref["rgb"][tuple(d[0])])
-    d = np.argwhere(rgba != ref["rgba8"])
-    assert len(d) == 0, "%s: %d RGBA8 bytes differ, first at %s: %r / %r" % (tag, len(d), d[0], rgba[tuple(d[0])], ref["rgba8"][tuple(d[0])])
-
-
-def check_launch(r, kernel, scene, W, H, cams, kw, flags, tally, shape=0, oracle_slices=None, tag=""):
-    """One launch of len(cams) slices on the forced kernel, asserted to have rendered it, against the oracle:
-    depth 1 -- the frame and the counters; depth > 1 -- every slice and the counter sum against single dispatches of the same
-    kernel, the oracle on oracle_slices (default: first, middle, last) with those singles' counters."""
-    depth = len(cams)
-    tm = 1 if flags & rr.DISPATCH_TONEMAP_REINHARD else 0
-    frames, st = dispatch(r, W, H, cams, kw, flags)
-    want = expected_kernel(kernel, scene, W, H, cams, kw, st.bvh_depth, flags, shape)
-    assert st.render_kernel == want, "%s: rendered by kernel %d, expected %d" % (tag, st.render_kernel, want)
-    if depth == 1:
-        ref = oracle_frame(scene, cams[0], W, H, kw, tm)
-        check_slice(frames[0][0], frames[0][1], ref, tag)
-        assert counters(st) == counters(ref["stats"]), (tag, counters(st), counters(ref["stats"]))
-        tally[st.render_kernel] += 1
-        return st.render_kernel
-    if oracle_slices is None:
-        oracle_slices = sorted({0, depth // 2, depth - 1})
-    total = np.zeros(len(COUNTERS), np.int64)
-    for f in range(depth):
-        one, s1 = dispatch(r, W, H, [cams[f]], kw, flags)
-        assert s1.render_kernel == expected_kernel(kernel, scene, W, H, [cams[f]], kw, s1.bvh_depth, flags, shape), (tag, f, s1.render_kernel)
-        assert np.array_equal(frames[f][0], one[0][0]), "%s: slice %d of the batch != its single dispatch" % (tag, f)
-        if frames[f][1] is not None:
-            assert np.array_equal(frames[f][1].view(np.uint32), one[0][1].view(np.uint32)), "%s: slice %d (float)" % (tag, f)
-        total += counters(s1)
-        if f in oracle_slices:
-            ref = oracle_frame(scene, cams[f], W, H, kw, tm)
-            check_slice(frames[f][0], frames[f][1], ref, "%s slice %d" % (tag, f))
-            assert counters(s1) == counters(ref["stats"]), (tag, f, counters(s1), counters(ref["stats"]))
-            tally[st.render_kernel] += 1
-    assert tuple(total) == counters(st), (tag, tuple(total), counters(st))
-    return st.render_kernel
-
-
-def report(name, tally):
-    TALLY.update(tally)
-    print("%s: oracle comparisons by render_kernel %s; module so far %s" % (name, dict(tally), dict(TALLY)))
 
 
 # --------------------------------------------------------------------------------- 1. single-mesh scenes (fused, lds, paths)
@@ -597,7 +380,7 @@ def test_background_culling_on_the_lds_and_stream_kernels(make_renderer, kernel)
 def test_refitted_two_instance_scene_on_stream_and_paths(make_renderer):
     """test_gpu_refit's two-instance scene, deformed: vertex update, BLAS update, TLAS update -- then stream (Depth 1, 3) and
     paths (Depth 1, 2) and fused render the deformed geometry as the oracle does"""
-    from test_gpu_refit import _two_instances, deform
+    from refit_helpers import _two_instances, deform
     verts, idx = load("monkey.obj")
     env = procedural_env(128, 64, seed=9)
     tally = collections.Counter()

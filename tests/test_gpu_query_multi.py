@@ -12,8 +12,7 @@ import pytest
 
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
-from test_gpu_query import (MASKED_INSTANCES, RAY_MASKS, _soup, bits, from_dev, gpu_scene, load, oracle_scene, random_rays, to_dev,
-                            xf)
+from query_helpers import bits, from_dev, gpu_scene, load, MASKED_INSTANCES, oracle_scene, random_rays, RAY_MASKS, _soup, to_dev, xf
 
 pytestmark = pytest.mark.gpu
 

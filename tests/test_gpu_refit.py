@@ -15,6 +15,7 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
+from refit_helpers import blas_bytes, deform, _two_instances
 
 pytestmark = pytest.mark.gpu
 
@@ -77,30 +78,6 @@ def procedural_mesh(n_side, seed=0):
     return verts, np.arange(tri.size, dtype=np.uint32)
 
 
-def deform(verts, kind, seed=0, amount=1.0):
-    """a copy of the vertex records with moved positions (and, for some kinds, moved normals)"""
-    v = verts.copy()
-    P = v["position"].astype(np.float64)
-    rng = np.random.default_rng(seed)
-    if kind == "wave":
-        P[:, 1] += 0.15 * amount * np.sin(4.0 * P[:, 0] + 0.7 * seed) * np.cos(3.0 * P[:, 2])
-        N = v["norm"].astype(np.float64)
-        N[:, 0] += 0.2 * amount * np.cos(4.0 * P[:, 0] + 0.7 * seed)
-        v["norm"] = (N / np.maximum(np.linalg.norm(N, axis=1, keepdims=True), 1e-12)).astype(np.float32)
-    elif kind == "scale":                          # x3 and translated: bounds and grid move
-        P = P * 3.0 + np.array([0.5, -0.25, 1.0])
-    elif kind == "jitter":
-        P += rng.normal(size=P.shape) * 0.02 * amount
-        N = v["norm"].astype(np.float64) + rng.normal(size=P.shape) * 0.1
-        v["norm"] = (N / np.maximum(np.linalg.norm(N, axis=1, keepdims=True), 1e-12)).astype(np.float32)
-    elif kind == "permute":                        # positions shuffled across vertices: the kept tree fits the new mesh badly
-        P = P[rng.permutation(len(P))]
-    else:
-        raise ValueError(kind)
-    v["position"] = P.astype(np.float32)
-    return v
-
-
 def random_rays(n, seed, radius=4.0, extent=1.2):
     rng = np.random.default_rng(seed)
     rays = np.zeros(n, rr.RAY_DTYPE)
@@ -158,12 +135,6 @@ def render_both(gpu, s, angle, W, H, **kw):
     lit = s.render(M, cam, W, H, O.default_params(use_bvh=1, **kw))
     pw = s.render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, **kw))
     return rgba, f32, st, lit, pw
-
-
-def blas_bytes(gpu, mid):
-    nodes, tris = gpu.download_blas(mid)
-    q, org, cell = gpu.download_qnodes(mid)
-    return nodes, tris, q, org, cell
 
 
 # ----------------------------------------------------------------------------------------- 1. identity refit
@@ -317,14 +288,6 @@ def test_refitted_frames_of_a_deep_batch_on_the_lds_kernel(gpu, tmp_path):
         pw = s.render(np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32), W, H,
                       O.default_params(use_bvh=1, accum_mode=1, max_refract=6))
         assert np.array_equal(out[k][..., :3].view(np.uint32), pw["rgb"].view(np.uint32)), "slice %d" % k
-
-
-def _two_instances(mid, shift):
-    t0 = np.eye(4, dtype=np.float32)[:3].copy()
-    t0[0, 3] = -0.9
-    t1 = np.array([[0.0, 0.0, 0.7, 0.9 + shift], [0.0, 0.7, 0.0, 0.2 * shift], [-0.7, 0.0, 0.0, 0.0]], np.float32)
-    return rr.make_instances(transforms=[t0, t1], meshes=[mid, mid], masks=[1, 1 if shift < 0.5 else 3],
-                             flags=[0, rr._capi.INSTANCE_FLAG_CULL_DISABLE if shift > 0 else 0])
 
 
 def test_two_instance_scene_after_blas_and_tlas_updates_matches_the_oracle(gpu):

@@ -13,19 +13,14 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from test_gpu_shade import STAT_FIELDS, gpu_scene, load, oracle_scene, xf
-from refraction_raytracing_dxr_amd import _capi
+from shading_helpers import (CELL16, LIMITS, STAT_FIELDS, SUB4, H, W, config4_scene, env_map, fold, gpu_scene, instanced_scene, load, oracle_scene,
+                             unorm8, view_constants)
 
 pytestmark = pytest.mark.gpu
 
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE, RR_ERR_UNSUPPORTED = 1, 5, 7
-W, H = 52, 37
 VIEWS = [(0.01, rr.FOV_Y), (1.3, 0.35), (3.7, 0.2)]
-LIMITS = [(5, 2, 1.2), (0, 0, 1.2), (8, 3, 1.2), (11, 3, 1.5)]          # max_reflect = 3: the PEND = 8 builds
-SUB4 = [(1, 0), (3, 1), (0, 2), (2, 3)]                                  # the built-in 4x pattern as sub-pixels of a 4x4 cell
-CELL16 = [(i, j) for j in range(4) for i in range(4)]                    # the whole cell, row-major
 OFF16 = np.array([[(2 * i + 1) / 8.0, (2 * j + 1) / 8.0] for i, j in CELL16], np.float32)
-ENV = dict(w=128, h=64, seed=3)
 
 
 @pytest.fixture(scope="module")
@@ -33,39 +28,6 @@ def gpu():
     r = rr.Renderer(0)
     yield r
     r.close()
-
-
-def env_map():
-    return procedural_env(ENV["w"], ENV["h"], seed=ENV["seed"])
-
-
-def view_constants(angle, fov, w=W, h=H):
-    sc = rr.camera_orbit(angle, fov_y=float(np.float32(fov)), aspect=float(np.float32(w / h)))
-    return sc, np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
-
-
-def unorm8(rgb, tonemap):
-    """the oracle library's rro_unorm8 of an [..., 3] float32 colour, after c / (1 + c) in float32 if tonemap; alpha 255"""
-    f = O.lib().rro_unorm8
-    f.restype, f.argtypes = C.c_uint8, [C.c_float]
-    c = np.ascontiguousarray(rgb, np.float32)
-    if tonemap:
-        c = c / (np.float32(1) + c)
-        assert c.dtype == np.float32
-    vals, inv = np.unique(c.view(np.uint32), return_inverse=True)
-    table = np.array([f(float(v)) for v in vals.view(np.float32)], np.uint8)
-    out = np.full(c.shape[:-1] + (4,), 255, np.uint8)
-    out[..., :3] = table[inv.reshape(c.shape)]
-    return out
-
-
-def fold(colours):
-    """the resolve rule over a list of [..., 3] float32 colours, in np.float32"""
-    s = colours[0].astype(np.float32, copy=True)
-    for c in colours[1:]:
-        s = s + c
-    assert s.dtype == np.float32
-    return s / np.float32(len(colours))
 
 
 def check(got, want_rgb, want_cnt, tonemap):
@@ -176,26 +138,6 @@ def test_oracle_parity(gpu, name, max_refract, max_reflect, ior):
 
 
 # ------------------------------------------------------------------------------------------------- 3. two-level
-# The two scenes below are copies: test_gpu_shade.py defines them inside its test bodies, where they cannot be imported from.
-# If those tests change their scenes, these do not follow by themselves.
-def instanced_scene():
-    """the scene of test_gpu_shade.py::test_oracle_parity_instanced_scene"""
-    inst = rr.make_instances(
-        transforms=[xf(0, 0, 0), xf(0, 0, -2.5, (0.5, 0.8, 0.5), 0.4), xf(0.3, 0.2, 2.4, (0.7, 0.7, 0.7), -1.0),
-                    xf(0, 1.9, 0, (0.4, 0.4, 0.4), 0.2), xf(0, -1.8, 0.5, (0.5, 0.5, 0.5)), xf(-2.2, 0.1, 0.3, (-0.6, 0.6, 0.6), 0.3)],
-        meshes=[1, 0, 1, 0, 0, 1], masks=[1, 1, 0xff, 1, 0, 1],
-        flags=[0, 0, 0, _capi.INSTANCE_FLAG_CULL_DISABLE, 0, _capi.INSTANCE_FLAG_FRONT_CCW])
-    return [load("cube.obj"), load("monkey.obj")], procedural_env(128, 64, seed=7), inst
-
-
-def config4_scene():
-    """the scene of test_gpu_shade.py::test_oracle_parity_config4_scene: three BLASes under one TLAS"""
-    def t(tx, ty, tz):
-        m = np.eye(4, dtype=np.float32)[:3].copy()
-        m[:, 3] = (tx, ty, tz)
-        return m
-    inst = rr.make_instances(transforms=[t(0, 0, 0), t(0, 0, -4.0), t(0, 0, 4.0)], meshes=[0, 1, 2])
-    return [load("shell.obj"), load("cube.obj"), load("ott.obj")], procedural_env(256, 128, seed=4), inst
 
 
 @pytest.mark.parametrize("angle", [0.6, 0.01])

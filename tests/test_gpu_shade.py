@@ -11,7 +11,8 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from refraction_raytracing_dxr_amd import _capi
+from shading_helpers import (STAT_FIELDS, camera_rays, check_against_oracle, config4_scene, gpu_scene, instanced_scene, load, oracle_scene,
+                             view_constants, xf)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,42 +32,6 @@ def gpu():
     r.close()
 
 
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m
-
-
-def camera_rays(M, cam, w, h, tmin=1e-4, tmax=100.0):
-    """rro_generate_camera_ray of every pixel, row-major, as ray records with the primary interval"""
-    o = np.zeros((h * w, 3), np.float32)
-    d = np.zeros((h * w, 3), np.float32)
-    for y in range(h):
-        for x in range(w):
-            o[y * w + x], d[y * w + x] = O.camera_ray(M, cam, x, y, w, h)
-    return rr.pack_rays(o, d, np.float32(tmin), np.float32(tmax))
-
-
-def view_constants(angle, fov, w=W, h=H):
-    sc = rr.camera_orbit(angle, fov_y=float(np.float32(fov)), aspect=float(np.float32(w / h)))
-    return sc, np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
-
-
-def check_against_oracle(gpu, s, M, cam, w, h, rays, **kw):
-    """shade_rays(rays) == rro_render of the camera the rays came from: float bits, RGBA8 with and without Reinhard, counts"""
-    ref = s.render(M, cam, w, h, O.default_params(use_bvh=1, accum_mode=1, use_libm=0, **kw), want_rays=True)
-    ref_tm = s.render(M, cam, w, h, O.default_params(use_bvh=1, accum_mode=1, use_libm=0, tonemap=1, **kw))
-    f32, u8, cnt = gpu.shade_rays(rays, rr.default_params(**kw), rgba8=True, ray_counts=True)
-    assert np.all(f32[:, 3] == 1.0) and np.all(u8[:, 3] == 255)
-    assert np.array_equal(f32[:, :3].view(np.uint32).reshape(h, w, 3), ref["rgb"].view(np.uint32))
-    assert np.array_equal(u8.reshape(h, w, 4), ref["rgba8"])
-    assert np.array_equal(cnt.reshape(h, w), ref["rays"].astype(np.uint32))
-    f32_tm, u8_tm = gpu.shade_rays(rays, rr.default_params(flags=rr.DISPATCH_TONEMAP_REINHARD, **kw), rgba8=True)
-    assert f32_tm.tobytes() == f32.tobytes()                    # the float colour is not tone-mapped
-    assert np.array_equal(u8_tm.reshape(h, w, 4), ref_tm["rgba8"])
-    return ref
-
-
 # ------------------------------------------------------------------------------------------------- 1. oracle parity, one BLAS
 _single = {}
 
@@ -82,7 +47,7 @@ def single_scene(gpu, name):
         s.set_envmap(env)
         views = []
         for angle, fov in VIEWS:
-            _, M, cam = view_constants(angle, fov)
+            _, M, cam = view_constants(angle, fov, W, H)
             views.append((M, cam, camera_rays(M, cam, W, H)))
         _single.clear()
         _single.update(name=name, s=s, views=views)
@@ -105,36 +70,6 @@ def test_oracle_parity_single_blas(gpu, name, max_refract, max_reflect, ior):
 
 
 # ------------------------------------------------------------------------------------------------- 2. oracle parity, two-level
-def oracle_scene(meshes, env, instances):
-    s = O.Scene()
-    for m in meshes:
-        s.add_mesh(m.verts, m.indices)
-    inst = np.zeros(len(instances), O.INSTANCE_DTYPE)
-    inst["transform"] = instances["transform"]
-    inst["id_mask"] = instances["instance_id_mask"]
-    inst["hitgroup_flags"] = instances["hitgroup_flags"]
-    inst["blas"] = instances["blas"]
-    s.set_instances(inst)
-    s.set_envmap(env)
-    return s
-
-
-def gpu_scene(gpu, meshes, env, instances):
-    ids = []
-    for m in meshes:
-        mid = gpu.upload_mesh(m.verts, m.indices)
-        gpu.build_blas(mid)
-        ids.append(mid)
-    instances = instances.copy()
-    instances["blas"] = [ids[int(b)] for b in instances["blas"]]
-    gpu.build_tlas(instances)
-    gpu.upload_envmap(env)
-
-
-def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
-    c, sn = np.cos(rot), np.sin(rot)
-    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
-    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
 
 
 def two_level_check(gpu, meshes, env, inst, angle, w, h, limits):
@@ -151,27 +86,14 @@ def two_level_check(gpu, meshes, env, inst, angle, w, h, limits):
 def test_oracle_parity_instanced_scene(gpu):
     """the scene of test_instanced_scene_parity (rotated, non-uniformly scaled instances, TRIANGLE_CULL_DISABLE, a zero-mask
     instance) plus a mirrored instance with TRIANGLE_FRONT_COUNTERCLOCKWISE"""
-    cube, monkey = load("cube.obj"), load("monkey.obj")
-    env = procedural_env(128, 64, seed=7)
-    inst = rr.make_instances(
-        transforms=[xf(0, 0, 0), xf(0, 0, -2.5, (0.5, 0.8, 0.5), 0.4), xf(0.3, 0.2, 2.4, (0.7, 0.7, 0.7), -1.0),
-                    xf(0, 1.9, 0, (0.4, 0.4, 0.4), 0.2), xf(0, -1.8, 0.5, (0.5, 0.5, 0.5)), xf(-2.2, 0.1, 0.3, (-0.6, 0.6, 0.6), 0.3)],
-        meshes=[1, 0, 1, 0, 0, 1], masks=[1, 1, 0xff, 1, 0, 1],
-        flags=[0, 0, 0, _capi.INSTANCE_FLAG_CULL_DISABLE, 0, _capi.INSTANCE_FLAG_FRONT_CCW])
-    ref = two_level_check(gpu, [cube, monkey], env, inst, 0.6, 200, 150, [(8, 2, 1.2), (0, 0, 1.2), (5, 3, 1.2), (11, 2, 1.5)])
+    meshes, env, inst = instanced_scene()
+    ref = two_level_check(gpu, meshes, env, inst, 0.6, 200, 150, [(8, 2, 1.2), (0, 0, 1.2), (5, 3, 1.2), (11, 2, 1.5)])
     assert (ref["rays"] > 1).mean() > 0.05
 
 
 def test_oracle_parity_config4_scene(gpu):
     """the scene of test_config4_multi_blas_scene: shell + cube + ott, three BLASes under one TLAS (trees deeper than 30 levels)"""
-    meshes = [load("shell.obj"), load("cube.obj"), load("ott.obj")]
-    env = procedural_env(256, 128, seed=4)
-
-    def t(tx, ty, tz):
-        m = np.eye(4, dtype=np.float32)[:3].copy()
-        m[:, 3] = (tx, ty, tz)
-        return m
-    inst = rr.make_instances(transforms=[t(0, 0, 0), t(0, 0, -4.0), t(0, 0, 4.0)], meshes=[0, 1, 2])
+    meshes, env, inst = config4_scene()
     ref = two_level_check(gpu, meshes, env, inst, 0.01, 240, 135, [(8, 2, 1.2), (5, 3, 1.2)])
     assert (ref["rays"] > 1).mean() > 0.02
 
@@ -200,7 +122,7 @@ def test_shade_rays_equals_a_dispatch(gpu, flags):
 # ------------------------------------------------------------------------------------------------- 4. order and neighbours
 def test_order_and_neighbours_do_not_matter(gpu):
     monkey_scene(gpu)
-    _, M, cam = view_constants(2.1, 0.3)
+    _, M, cam = view_constants(2.1, 0.3, W, H)
     rays = camera_rays(M, cam, W, H)
     p = rr.default_params(max_refract=8, max_reflect=3)
     f32, u8, cnt = gpu.shade_rays(rays, p, rgba8=True, ray_counts=True)
@@ -241,7 +163,7 @@ def to_dev(rays, gpu, dtype="int32"):
 def test_device_path_equals_host_path(gpu):
     import torch
     monkey_scene(gpu)
-    _, M, cam = view_constants(0.4, 0.3)
+    _, M, cam = view_constants(0.4, 0.3, W, H)
     rays = camera_rays(M, cam, W, H)
     p = rr.default_params(max_refract=8)
     f32, u8, cnt = gpu.shade_rays(rays, p, rgba8=True, ray_counts=True)
@@ -319,16 +241,58 @@ def test_device_path_refuses_bad_pointers_and_shapes(gpu):
             gpu.shade_rays(bad)
 
 
+
+def test_host_calls_share_one_staged_output_set(gpu):
+    """The host variants of shade_rays, render_samples and render_adaptive stage their outputs through one set of context buffers,
+    each sized by whichever call grew it last.  Calls of 100, 63, 144, 5, 9 and 300 elements -- growth, reuse at a smaller size,
+    growth again, for each of the three buffers -- must each equal, byte for byte, the same call's device variant into fresh torch
+    tensors, which does not touch the set."""
+    import torch
+    m = load("cube.obj")
+    gpu.load_scene(m.verts, m.indices, procedural_env(128, 64, seed=5))
+    p = rr.default_params(max_refract=8)
+    _, M, cam = view_constants(1.3, 0.35, 20, 15)
+    rays = camera_rays(M, cam, 20, 15)
+    rays = rays[np.random.default_rng(3).permutation(len(rays))]       # (every prefix holds rays that hit the cube)
+
+    def same(host, dev):
+        gpu.wait()
+        torch.cuda.synchronize()
+        assert len(host) == len(dev)
+        for a, t in zip(host, dev):
+            b = t.cpu().numpy()
+            assert a.shape == b.shape and a.tobytes() == b.tobytes()
+
+    def shade(n):
+        host = gpu.shade_rays(rays[:n], p, rgba8=True, ray_counts=True)
+        same(host, gpu.shade_rays(to_dev(rays[:n], gpu), p, rgba8=True, ray_counts=True))
+        return host
+
+    def samples(w, h, n):
+        sc, _, _ = view_constants(1.3, 0.35, w, h)
+        same(gpu.render_samples(w, h, sc, n, p, rgba8=True, ray_counts=True),
+             gpu.render_samples(w, h, sc, n, p, rgba8=True, ray_counts=True, device=True))
+
+    shade(100)
+    samples(9, 7, 4)
+    sc, _, _ = view_constants(1.3, 0.35, 16, 9)
+    kw = dict(samples=(1, 4), params=p, rgba8=True, ray_counts=True, sample_counts=True)
+    host = gpu.render_adaptive(16, 9, sc, **kw)
+    same(host[:4], gpu.render_adaptive(16, 9, sc, device=True, **kw))
+    assert set(np.unique(host[3])) <= {1, 4} and host[4] == int((host[3] == 4).sum())
+    shade(5)
+    samples(3, 3, 2)
+    _, _, cnt = shade(300)
+    assert (cnt > 1).any() and (cnt == 1).any()                 # hits and misses: the outputs are not constant
+
+
 # ------------------------------------------------------------------------------------------------- 6. leaves the context alone
-STAT_FIELDS = ("rays", "primary", "secondary", "hits", "misses", "terminal_hits", "tir", "node_visits", "tri_tests", "pixels",
-               "stats_valid", "traversal_overflow", "bvh_depth", "render_kernel", "node_trips", "leaf_trips", "shade_passes", "waves",
-               "background_waves", "render_kernel_name")
 
 
 def test_a_radiance_query_leaves_the_context_alone(gpu):
     import torch
     monkey_scene(gpu)
-    sc, M, cam = view_constants(0.3, 0.4)
+    sc, M, cam = view_constants(0.3, 0.4, W, H)
     gpu.set_tile_partition(0, 1)
     gpu.set_camera(sc)
     gpu.dispatch_rays(W, H, rr.default_params(flags=rr.DISPATCH_FLOAT_OUTPUT | rr.DISPATCH_COLLECT_STATS, max_refract=8))
@@ -336,7 +300,7 @@ def test_a_radiance_query_leaves_the_context_alone(gpu):
     st = gpu.stats()
     before = {k: getattr(st, k) for k in STAT_FIELDS}
     assert before["rays"] > W * H
-    _, M2, cam2 = view_constants(2.0, 0.2)
+    _, M2, cam2 = view_constants(2.0, 0.2, W, H)
     rays = camera_rays(M2, cam2, W, H)
     gpu.shade_rays(rays, rr.default_params(max_refract=3, max_reflect=3), rgba8=True, ray_counts=True)
     gpu.shade_rays(to_dev(rays, gpu), rr.default_params(flags=rr.DISPATCH_TONEMAP_REINHARD), rgba8=True, ray_counts=True)

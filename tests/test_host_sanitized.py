@@ -88,7 +88,7 @@ def test_interlaced_pngs_never_trip_the_sanitizers(driver, tmp_path):
     """The Adam7 de-interlace path parses untrusted files too: interlaced PNGs of every sample depth (1, 2, 4, 8, 16 bits;
     gray, gray+alpha, RGB, RGBA, palette), 1 x N and N x 1 images (most of the seven passes empty), truncations at every
     kind of offset and seeded bit-flips of all of them, through the ASan + UBSan build: decoded or refused, never a report."""
-    from test_host import _adam7_cases, _write_adam7_png
+    from host_goldens import _adam7_cases, _write_adam7_png
     rng = np.random.default_rng(12)
     cases = dict(_adam7_cases(rng))
     cases.update({

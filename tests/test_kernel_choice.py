@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from codeobj import LAUNCHABLE
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "refraction_raytracing_dxr_amd", "csrc")
 
@@ -166,6 +168,63 @@ def test_fused_variant(driver):
     got = [tuple(int(t) for t in line.split()) for line in run(driver, lines)]
     bad = [(kw, depth, reflect, want, g) for (_, kw, depth, reflect, want), g in zip(FUSED_VARIANTS, got) if g != want]
     assert not bad, bad
+
+
+def tree_rung(single, stack, pend, stack16):
+    """the ray-tree kernels' ladder as launch_shade_rays, launch_render_samples and launch_render_adaptive each spelt it before
+    for_tree_variant (csrc/rr_choice.h) replaced the three copies, rung for rung -> (STACK, PEND, TLAS, bits per stack entry)"""
+    if stack16 and not single and pend <= 2 and stack <= 30:
+        return (30, 2, 1, 16)
+    if stack16 and not single and pend <= 2 and stack <= 39:
+        return (39, 2, 1, 16)
+    if stack16 and single and stack <= 39:
+        return (39, 2 if pend <= 2 else 8, 0, 16)
+    tlas = 0 if single else 1
+    if stack <= 19 and pend <= 2:
+        return (19, 2, tlas, 32)
+    if stack <= 26 and pend <= 2:
+        return (26, 2, tlas, 32)
+    for rung in (31, 39):
+        if stack <= rung:
+            return (rung, 2 if pend <= 2 else 8, tlas, 32)
+    return (64, 2 if pend <= 2 else 8, tlas, 32)
+
+
+# (single, stack, pend, stack16) -> (STACK, PEND, TLAS, bits): both sides of every rung's boundary, written out
+TREE_VARIANTS = [
+    # the 16-bit rungs: two-level scenes up to 30 and up to 39 entries with two parked rays, a single BLAS up to 39 with two or eight
+    ((0, 30, 2, 1), (30, 2, 1, 16)), ((0, 31, 2, 1), (39, 2, 1, 16)), ((0, 39, 2, 1), (39, 2, 1, 16)), ((0, 40, 2, 1), (64, 2, 1, 32)),
+    ((0, 30, 3, 1), (31, 8, 1, 32)), ((0, 39, 3, 1), (39, 8, 1, 32)), ((0, 1, 0, 1), (30, 2, 1, 16)),
+    ((1, 19, 2, 1), (39, 2, 0, 16)), ((1, 39, 2, 1), (39, 2, 0, 16)), ((1, 39, 3, 1), (39, 8, 0, 16)), ((1, 39, 8, 1), (39, 8, 0, 16)),
+    ((1, 40, 2, 1), (64, 2, 0, 32)), ((1, 40, 3, 1), (64, 8, 0, 32)),
+    # 32-bit entries: 19 and 26 only with two parked rays
+    ((1, 19, 2, 0), (19, 2, 0, 32)), ((1, 20, 2, 0), (26, 2, 0, 32)), ((1, 26, 2, 0), (26, 2, 0, 32)), ((1, 27, 2, 0), (31, 2, 0, 32)),
+    ((1, 19, 3, 0), (31, 8, 0, 32)), ((1, 26, 3, 0), (31, 8, 0, 32)), ((1, 30, 2, 0), (31, 2, 0, 32)), ((1, 31, 2, 0), (31, 2, 0, 32)),
+    ((1, 31, 3, 0), (31, 8, 0, 32)), ((1, 32, 2, 0), (39, 2, 0, 32)), ((1, 32, 3, 0), (39, 8, 0, 32)), ((1, 39, 2, 0), (39, 2, 0, 32)),
+    ((1, 39, 3, 0), (39, 8, 0, 32)), ((1, 40, 2, 0), (64, 2, 0, 32)), ((1, 40, 3, 0), (64, 8, 0, 32)), ((1, 64, 2, 0), (64, 2, 0, 32)),
+    ((1, 64, 3, 0), (64, 8, 0, 32)), ((1, 64, 8, 0), (64, 8, 0, 32)),
+    ((0, 19, 2, 0), (19, 2, 1, 32)), ((0, 20, 2, 0), (26, 2, 1, 32)), ((0, 26, 2, 0), (26, 2, 1, 32)), ((0, 27, 2, 0), (31, 2, 1, 32)),
+    ((0, 19, 3, 0), (31, 8, 1, 32)), ((0, 30, 2, 0), (31, 2, 1, 32)), ((0, 31, 2, 0), (31, 2, 1, 32)), ((0, 31, 3, 0), (31, 8, 1, 32)),
+    ((0, 32, 2, 0), (39, 2, 1, 32)), ((0, 32, 3, 0), (39, 8, 1, 32)), ((0, 39, 2, 0), (39, 2, 1, 32)), ((0, 39, 3, 0), (39, 8, 1, 32)),
+    ((0, 40, 2, 0), (64, 2, 1, 32)), ((0, 40, 3, 0), (64, 8, 1, 32)), ((0, 64, 2, 0), (64, 2, 1, 32)), ((0, 64, 3, 0), (64, 8, 1, 32)),
+]
+TREE_BOUNDARIES = [(single, stack, pend, stack16) for single in (0, 1) for stack16 in (0, 1) for stack in (19, 20, 26, 27, 30, 31, 32, 39, 40, 64)
+                   for pend in (2, 3)]
+TREE_DOMAIN = [(single, stack, pend, stack16) for single in (0, 1) for stack16 in (0, 1) for stack in range(1, 65) for pend in range(0, 9)]
+
+
+def test_tree_variant_ladder(driver):
+    """for_tree_variant against the written-out table, against the ladder its three launchers carried (every boundary of every rung
+    and the whole domain), and its answers over the whole domain are exactly the launchable instantiations (4 with 16-bit stack entries, 10 with two
+    parked rays, 6 with eight)"""
+    assert [tree_rung(*q) for q, _ in TREE_VARIANTS] == [want for _, want in TREE_VARIANTS]
+    queries = [q for q, _ in TREE_VARIANTS] + TREE_BOUNDARIES + TREE_DOMAIN
+    got = [tuple(int(t) for t in line.split()) for line in run(driver, ["tree %d %d %d %d" % q for q in queries])]
+    bad = [(q, g, tree_rung(*q)) for q, g in zip(queries, got) if g != tree_rung(*q)]
+    assert not bad, bad[:10]
+    bits = {"unsigned short": 16, "unsigned int": 32}
+    launchable = {(s, p, int(t), bits[e]) for s, p, t, e in LAUNCHABLE}
+    assert len(launchable) == 20 and set(got[-len(TREE_DOMAIN):]) == launchable
 
 
 def key(driver, w, h, refract, reflect, depth):

@@ -6,27 +6,8 @@ import numpy as np
 import pytest
 
 import oracle as O
+from host_goldens import CAMERA_KATS, LOADER_GOLD, M_GOLD
 
-# produced by the reference's own Mesh::load body (g++ 11.4)
-LOADER_GOLD = {
-    "cube.obj": (12, "62afee94b8d6cb6a", (-1, -1, -1), (1, 1, 1)),
-    "sphere.obj": (768, "9b7d5bd5769fd643", (-1.732051,) * 3, (1.732051,) * 3),
-    "monkey.obj": (967, "a4734543877c2dd5", (-1.367188, -0.984375, -1.504792), (1.367188, 0.984375, 0.198333)),
-    "shell.obj": (1536, "7f2f52b6a1a28e63", (-1.732051,) * 3, (1.732051,) * 3),
-    "ott.obj": (12877, "46b040642a0ffe6f", (-0.927691, -1.211907, -1.236633), (0.931792, 1.282290, 0.559067)),
-}
-
-# SURVEY Appendix A.1 (float64 evaluation, compare at 1e-5), angle 0.01
-CAMERA_KATS = [
-    (1024, 768, 512, 384, (-0.999943191, -0.000640168, -0.010639805)),
-    (1024, 768, 0, 0, (-0.778907078, 0.379981610, 0.498916566)),
-    (1024, 768, 1023, 767, (-0.768773635, -0.379981610, -0.514393889)),
-    (1920, 1080, 960, 540, (-0.999946425, -0.000455231, -0.010341152)),
-    (1920, 1080, 0, 0, (-0.778775816, 0.380059543, 0.499062092)),
-    (1920, 1080, 1919, 1079, (-0.768639490, -0.380059543, -0.514536761)),
-]
-M_GOLD = np.array([[0.006501146, 0, 0, -0.9919504], [0, 0.487716015, 0, 0],
-                   [-0.650092915, 0, 0, -0.009919835], [-2.600371662, 0, 1, 1.059519008]])
 
 # SURVEY Appendix C, 256x192, angle 0.01, envmap.png, max_reflect 2: rays per depth level
 RAYCOUNT_GOLD = [

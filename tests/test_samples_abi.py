@@ -3,7 +3,6 @@ the sample rays against the CPU oracle, and the code generation of k_render_samp
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -11,11 +10,12 @@ import pytest
 
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
+from codeobj import HAVE_OBJDUMP, LAUNCHABLE, kernels, template_args
 from refraction_raytracing_dxr_amd import _capi
+from shading_helpers import H, W, view_constants
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rrdxr.h")
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 RR_ERR_INVALID_ARGUMENT = 1
 _P = C.c_void_p
 _SC, _DP = C.POINTER(_capi.SceneConstants), C.POINTER(_capi.DispatchParams)
@@ -25,11 +25,6 @@ NEW = {
     "rr_render_samples": (C.c_int, [_P, C.c_uint32, C.c_uint32, _SC, _DP, _P, C.c_uint32, _P, _P, _P]),
     "rr_render_samples_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _SC, _DP, _P, C.c_uint32, _P, _P, _P]),
 }
-# every (STACK, PEND, TLAS, E) launch_render_samples (rr_render_samples.hip) can launch: launch_shade_rays' ladder
-LAUNCHABLE = [(30, 2, True, "unsigned short"), (39, 2, True, "unsigned short"), (39, 2, False, "unsigned short"),
-              (39, 8, False, "unsigned short")] + \
-             [(s, 2, t, "unsigned int") for s in (19, 26, 31, 39, 64) for t in (False, True)] + \
-             [(s, 8, t, "unsigned int") for s in (31, 39, 64) for t in (False, True)]
 # D3D's standard multisample patterns in sixteenths of a pixel from the centre
 PATTERNS = {
     1: [(0, 0)],
@@ -40,7 +35,6 @@ PATTERNS = {
          (6, 7), (-7, -8)],
 }
 VIEWS = [(0.01, rr.FOV_Y), (1.3, 0.35), (3.7, 0.2)]
-W, H = 52, 37
 
 
 # ------------------------------------------------------------------------------------------------- 1. symbols and surface
@@ -106,9 +100,6 @@ def test_sample_patterns_are_the_d3d_tables():
 
 
 # ------------------------------------------------------------------------------------------------- 3. sample rays against the oracle
-def view_constants(angle, fov):
-    sc = rr.camera_orbit(angle, fov_y=float(np.float32(fov)), aspect=float(np.float32(W / H)))
-    return sc, np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
 
 
 def oracle_rays(M, cam, w, h, xs, ys):
@@ -172,40 +163,16 @@ def test_camera_rays_refuse_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------------- 4. codegen
-def _scratch_counts(tmp_path):
-    import refraction_raytracing_dxr_amd._build as B
-    so = tmp_path / "librrdxr.so"
-    shutil.copy(B.build(), so)
-    subprocess.run([OBJDUMP, "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    kernels = {}
-    for f in sorted(tmp_path.iterdir()):
-        if "gfx950" not in f.name:
-            continue
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "-C", str(f)], check=True, capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.split("\n"):
-            m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
-            if m:
-                cur = m.group(1) if ("k_shade_rays<" in m.group(1) or "k_render_samples<" in m.group(1)) else None
-                if cur:
-                    kernels[cur] = 0
-                continue
-            if cur and line.strip().startswith("scratch_"):
-                kernels[cur] += 1
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
+@pytest.mark.skipif(not HAVE_OBJDUMP, reason="llvm-objdump of the ROCm toolchain not found")
 def test_sample_kernels_exist(tmp_path):
     """every k_render_samples<STACK, PEND, TLAS, E> the host can launch is in the gfx950 code object; its scratch_ instructions
     are printed next to those of k_shade_rays, which runs the same tree without the three accumulators (no assertion on the
     counts: DESIGN 5.6 records them)"""
-    k = _scratch_counts(tmp_path)
-    b = {True: "true", False: "false"}
+    k = {n: v["scratch"] for n, v in kernels(tmp_path).items()}
     mine = {n: v for n, v in k.items() if "k_render_samples<" in n}
     assert len(mine) == len(LAUNCHABLE), sorted(mine)
-    for stack, pend, tlas, e in LAUNCHABLE:
-        args = "<%d, %d, %s, %s>" % (stack, pend, b[tlas], e)
+    for variant in LAUNCHABLE:
+        args = template_args(*variant)
         got = [v for n, v in mine.items() if "k_render_samples" + args in n]
         ref = [v for n, v in k.items() if "k_shade_rays" + args in n]
         assert len(got) == 1 and len(ref) == 1, (args, got, ref)

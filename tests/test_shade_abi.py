@@ -2,27 +2,21 @@
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 import refraction_raytracing_dxr_amd as rr
+from codeobj import HAVE_OBJDUMP, LAUNCHABLE, kernels, template_args
 from refraction_raytracing_dxr_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rrdxr.h")
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 _P = C.c_void_p
 NEW = {
     "rr_shade_rays": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_capi.DispatchParams), _P, _P, _P]),
     "rr_shade_rays_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_capi.DispatchParams), _P, _P, _P]),
 }
-# every (STACK, PEND, TLAS, E) launch_shade_rays (rr_shade_rays.hip) can launch: launch_render_fused's ladder without its 22-entry rung
-LAUNCHABLE = [(30, 2, True, "unsigned short"), (39, 2, True, "unsigned short"), (39, 2, False, "unsigned short"),
-              (39, 8, False, "unsigned short")] + \
-             [(s, 2, t, "unsigned int") for s in (19, 26, 31, 39, 64) for t in (False, True)] + \
-             [(s, 8, t, "unsigned int") for s in (31, 39, 64) for t in (False, True)]
 
 
 def test_shade_symbols_resolve_with_their_signatures():
@@ -57,40 +51,16 @@ def test_shade_entry_points_reject_a_null_context():
     assert L.rr_shade_rays_device(None, r, 1, None, f, None, None) == 1
 
 
-def _scratch_counts(tmp_path):
-    import refraction_raytracing_dxr_amd._build as B
-    so = tmp_path / "librrdxr.so"
-    shutil.copy(B.build(), so)
-    subprocess.run([OBJDUMP, "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
-    kernels = {}
-    for f in sorted(tmp_path.iterdir()):
-        if "gfx950" not in f.name:
-            continue
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "-C", str(f)], check=True, capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.split("\n"):
-            m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
-            if m:
-                cur = m.group(1) if ("k_shade_rays<" in m.group(1) or "k_render_fused<" in m.group(1)) else None
-                if cur:
-                    kernels[cur] = 0
-                continue
-            if cur and line.strip().startswith("scratch_"):
-                kernels[cur] += 1
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
+@pytest.mark.skipif(not HAVE_OBJDUMP, reason="llvm-objdump of the ROCm toolchain not found")
 def test_shade_kernels_exist_and_spill_no_more_than_the_render_kernels(tmp_path):
     """every k_shade_rays<STACK, PEND, TLAS, E> the host can launch is in the code objects, and holds no more scratch_
     instructions than k_render_fused<STACK, PEND, false, TLAS, false, E, *>, which parks the same rays"""
-    k = _scratch_counts(tmp_path)
-    b = {True: "true", False: "false"}
+    k = {n: v["scratch"] for n, v in kernels(tmp_path).items()}
     shade = {n: v for n, v in k.items() if "k_shade_rays<" in n}
     assert len(shade) == len(LAUNCHABLE), sorted(shade)
     for stack, pend, tlas, e in LAUNCHABLE:
-        mine = [v for n, v in shade.items() if "k_shade_rays<%d, %d, %s, %s>" % (stack, pend, b[tlas], e) in n]
-        ref = [v for n, v in k.items() if "k_render_fused<%d, %d, false, %s, false, %s, " % (stack, pend, b[tlas], e) in n]
+        mine = [v for n, v in shade.items() if "k_shade_rays" + template_args(stack, pend, tlas, e) in n]
+        ref = [v for n, v in k.items() if "k_render_fused<%d, %d, false, %s, false, %s, " % (stack, pend, "true" if tlas else "false", e) in n]
         assert len(mine) == 1 and len(ref) == 1, (stack, pend, tlas, e, mine, ref)
-        print("k_shade_rays<%d, %d, %s, %s>: %d scratch instructions, k_render_fused: %d" % (stack, pend, b[tlas], e, mine[0], ref[0]))
+        print("k_shade_rays%s: %d scratch instructions, k_render_fused: %d" % (template_args(stack, pend, tlas, e), mine[0], ref[0]))
         assert mine[0] <= ref[0], (stack, pend, tlas, e, mine[0], ref[0])

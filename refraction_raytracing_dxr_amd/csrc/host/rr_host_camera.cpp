@@ -149,7 +149,7 @@ extern "C" int rr_host_sample_pattern(uint32_t n_samples, float* offsets)
 }
 
 // GenerateCameraRay (RayTracing.hlsl:27-40) for every pixel of a frame, with the literal 0.5 replaced by (ox, oy): the
-// arithmetic of k_render_samples' sample ray (screen_coord and camera_ray_dir of rr_device.h), operation by operation
+// arithmetic of k_render_samples' sample ray (screen_coord of rr_frame.hip and camera_ray_dir of rr_device.h), operation by operation
 extern "C" int rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,
                                    rr_ray* rays)
 {

@@ -4,7 +4,7 @@
 // (Mesh.cpp:55-94), load_texture (:108-140), the two BuildRaytracingAccelerationStructure calls
 // (:277-356), the per-frame constant-buffer copy (:566), DispatchRays (:580-594), the UAV ->
 // backbuffer copy (:596-604) and the fence wait (:65-71).  Everything device-side is a kernel in
-// rr_bvh_build.hip / rr_render.hip; this file only owns memory, call order and error reporting.
+// rr_bvh_build.hip / rr_render_*.hip / rr_query*.hip / rr_frame.hip; this file only owns memory, call order and error reporting.
 // (Builds, dispatch, orbit loops, queries and RCCL are in the other rr_capi_*.cpp; what they share is in rr_context.h.)
 #include "rr_context.h"
 

@@ -405,7 +405,7 @@ int dispatch_impl(rr_context* ctx, const DispatchRequest& req)
         if (FILE* f = fopen(ctx->dbg_diag.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
     }
 
-    snprintf(ctx->last_kernel_name, sizeof ctx->last_kernel_name, "%s", kernel == K_STREAM ? last_stream_kernel_name() : last_render_kernel_name());
+    snprintf(ctx->last_kernel_name, sizeof ctx->last_kernel_name, "%s", last_render_kernel_name());
     ctx->last_kernel = (uint32_t)kernel;
     ctx->W = width; ctx->H = height; ctx->frame_world = ctx->tile_world; ctx->frame_depth = depth;
     ctx->have_f32 = o.want_f32; ctx->have_frame = ext_tiles == nullptr; ctx->have_assembled = false;

@@ -92,7 +92,7 @@ void record_timings(KernelChoice& ch, float ms_a, float ms_b, double rect_share)
 FusedVariant fused_variant(const SceneFacts& s, uint32_t depth, int max_reflect, const DebugFacts& d)
 {
     const uint32_t need = s.need;
-    int stack = need <= 19 ? 19 : need <= 22 ? 22 : need <= 26 ? 26 : need <= 31 ? 31 : need <= 39 ? 39 : 64;     // rr_render.hip: sizes that fill the LDS with 6 / 5 / 4 / 2 workgroups
+    int stack = need <= 19 ? 19 : need <= 22 ? 22 : need <= 26 ? 26 : need <= 31 ? 31 : need <= 39 ? 39 : 64;     // rr_render_fused.hip: sizes that fill the LDS with 6 / 5 / 4 / 2 workgroups
     if (d.stack >= (int)need) stack = d.stack;   // experiments only; never below the tree depth (the kernels do not check)
     // deep trees of small meshes: 16-bit stack entries keep eight waves per SIMD (LDS would otherwise allow 6/5/4)
     bool stack16 = s.single_identity && need > 19 && need <= 39 && d.stack == 0 && s.blas_tris < 32768u;

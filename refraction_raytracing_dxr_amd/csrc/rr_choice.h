@@ -68,7 +68,7 @@ template <int STACK, int PEND, class F> auto tree_variant32(bool single_identity
 // The one ladder of those kernels: f(TreeVariant) of the instantiation that runs a scene's FusedVariant (stack <= 64, pend <= 8: the
 // launchers check) -- launch_render_fused's ladder without its 22-entry rung (seven waves per SIMD against six: DESIGN 5.5).  20
 // instantiations in all; tests/test_kernel_choice.py walks every rung.  The other ladders stay where they are: launch_render_fused's
-// has that rung and branches on its diag and stats builds with waves per SIMD of its own per rung (rr_render.hip); the trace, query
+// has that rung and branches on its diag and stats builds with waves per SIMD of its own per rung (rr_render_fused.hip); the trace, query
 // and multi-hit kernels are <STACK, TLAS> builds of two stack sizes without parked rays, two lines each.
 template <class F> auto for_tree_variant(bool single_identity, FusedVariant v, F&& f)
 {

@@ -446,12 +446,6 @@ __device__ __forceinline__ void walk_blas(const QNode* __restrict__ nodes, const
             const NodeQ q = ns.load(nodes, node);
             if (STATS) { cnt.nodes++; if (first_active_lane()) cnt.node_trips++; }
             node = node_step(br, q, tmin, hit_bound(best), top, stk);
-#ifdef RR_EXP_EXTRA_VALU      // experiment: what do N more VALU instructions per visit cost?
-            { float dv = br.inv.x;
-#pragma unroll
-              for (int k = 0; k < RR_EXP_EXTRA_VALU; ++k) asm volatile("v_add_f32 %0, %0, %0" : "+v"(dv));
-              asm volatile("" :: "v"(dv)); }
-#endif
         }
         // leaf phase: every lane that holds a leaf tests its triangle and pops
         if (node < 0 && node != TRAV_DONE) {
@@ -717,14 +711,7 @@ __device__ __forceinline__ bool refract_ray(f3& R, f3 I, f3 N, float eta)
 }
 
 // ---- GenerateCameraRay: RayTracing.hlsl:27-40 ----------------------------------------------------
-// screen coordinate of a pixel centre (hlsl:29-33), the same operations for every pixel of a column / row: k_screen_tables
-// evaluates them once per column and row, the render kernels read the two tables
-__device__ __forceinline__ float screen_coord(uint32_t i, uint32_t n, bool flip)
-{
-    const float p = (float)i + 0.5f;
-    const float s = p / (float)n * 2.0f - 1.0f;
-    return flip ? -s : s;
-}
+// (the screen coordinates sx, sy of hlsl:29-33 come from k_screen_tables' two tables: screen_coord, rr_frame.hip)
 __device__ __forceinline__ f3 camera_ray_dir(const float* M, float sx, float sy)
 {
     f3 R;

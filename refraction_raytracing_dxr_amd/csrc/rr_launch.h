@@ -10,23 +10,26 @@ struct alignas(16) rr_ray_dev { float origin[3]; float tmin; float dir[3]; float
 struct rr_hit_dev { float t, u, v; uint32_t prim, inst, hit; };
 static_assert(sizeof(rr_ray_dev) == 48 && sizeof(rr_hit_dev) == 24, "ABI layout");
 
-// ---- rr_render.hip
+// ---- rr_render_fused.hip
 hipError_t launch_render_fused(const SceneDev& sc, const DispatchDev& a, int stack, int pend, bool stats, hipStream_t s,
                                bool stack16 = false);
+// the instantiation the calling thread's last launch_render_* call launched, e.g. "k_render_fused<19, 2, false, false, false, unsigned int, 0>"
+// (a launch without blocks launches nothing and leaves the name as it was); every render launcher sets it
+const char* last_render_kernel_name();
+void set_render_kernel_name(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// ---- rr_render_paths.hip
+// launches of one or two slices: four lanes per pixel inside the scene's screen rectangle (k_render_paths)
+hipError_t launch_render_paths(const SceneDev& sc, const DispatchDev& a, int stack, bool stats, hipStream_t s);
+// ---- rr_render_lds.hip
 // BLAS nodes in LDS, persistent workgroups (single identity instance whose node array fits: lds_kernel_shape() >= 0)
 // shapes (waves per workgroup x workgroups per CU): 0 = 12x2 (the product shape), 1 = 16x2, 2 = 16x1 (experiments:
 // RR_DEBUG_SHAPE = first shape to consider); -1: the node array does not fit
 int lds_kernel_shape(uint32_t node_bytes, uint32_t stack_entries, size_t* lds_bytes, int min_shape = 0);
 hipError_t launch_render_lds(const SceneDev& sc, const DispatchDev& a, LdsDispatch q, int n_cus, bool stats, hipStream_t s, int min_shape = 0);
-// launches of one or two slices: four lanes per pixel inside the scene's screen rectangle (k_render_paths)
-hipError_t launch_render_paths(const SceneDev& sc, const DispatchDev& a, int stack, bool stats, hipStream_t s);
-hipError_t launch_assemble_frames_mesh_rgb8(const uint8_t* gathered, const uint8_t* bg, uint32_t* frames, uint32_t W, uint32_t H, const MeshPartDev& mp,
-                                            size_t rank_stride_b, size_t frame_stride_b, size_t bg_stride_b, size_t out_stride, uint32_t n_frames, hipStream_t s);
 // ---- rr_render_stream.hip: one kernel per ray generation, rays in HBM queues, lanes refilled as their rays end (two-level scenes)
 hipError_t launch_render_stream(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, int stack, uint32_t n_wg, bool stats, hipStream_t st);
-const char* last_stream_kernel_name();
-// the instantiation the calling thread's last launch_render_* call launched, e.g. "k_render_fused<19, 2, false, false, false, unsigned int, 0>"
-const char* last_render_kernel_name();
+// ---- rr_query.hip: one stage on caller input
+hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_trace_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, rr_hit_dev* hits, uint32_t* err,
                              int stack, hipStream_t s);
 // the query kernels (rr_query_rays[_device]): instance masks and per-lane first-hit termination; inst0_mask: the InstanceMask of
@@ -78,8 +81,8 @@ struct AdaptiveWorkspace {
 hipError_t launch_render_adaptive(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_base,
                                   uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, float4* f32, uint32_t* rgba8, uint32_t* n_rays,
                                   uint32_t* n_taken, int stack, int pend, bool stack16, uint32_t refine_groups, hipStream_t s);
+// ---- rr_frame.hip: the screen-coordinate tables of a frame, and gathered tiles -> rasters
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
-hipError_t launch_env_lookup(const SceneDev& sc, const float* dirs, uint32_t n, float* rgb, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,
                                  uint32_t n_tiles, uint32_t world, uint32_t max_tiles, hipStream_t s);
 // batched: strides in 32-bit words
@@ -89,6 +92,8 @@ hipError_t launch_assemble_frames(const uint32_t* gathered, uint32_t* frames, ui
 hipError_t launch_assemble_frames_rgb8(const uint8_t* gathered, uint32_t* frames, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles,
                                        uint32_t world, size_t rank_stride_b, size_t frame_stride_b, size_t out_stride, uint32_t n_frames,
                                        hipStream_t s);
+hipError_t launch_assemble_frames_mesh_rgb8(const uint8_t* gathered, const uint8_t* bg, uint32_t* frames, uint32_t W, uint32_t H, const MeshPartDev& mp,
+                                            size_t rank_stride_b, size_t frame_stride_b, size_t bg_stride_b, size_t out_stride, uint32_t n_frames, hipStream_t s);
 
 // ---- rr_bvh_build.hip
 // Scratch + outputs of one LBVH build over n primitives (triangles of a mesh, or instances).

@@ -1,6 +1,6 @@
-// rr_render_common.h -- device code shared by the render kernels (rr_render.hip, rr_render_stream.hip, rr_shade_rays.hip,
-// rr_render_samples.hip): a pixel's ray tree as the lanes walk it (RayGen, ClosestHit / Miss, the parked
-// reflected rays), the frame store, the counters, and the numbering of a dispatch's 8x8 pixel blocks.
+// rr_render_common.h -- device code shared by the render kernels (rr_render_fused.hip, rr_render_paths.hip, rr_render_lds.hip,
+// rr_render_stream.hip, rr_shade_rays.hip, rr_render_samples.hip, rr_render_adaptive.hip): a pixel's ray tree as the
+// lanes walk it (RayGen, ClosestHit / Miss, the parked reflected rays), the frame store, the counters, and the numbering of a dispatch's 8x8 pixel blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -364,26 +364,5 @@ __device__ __forceinline__ BlockPos wave_block_pos(const DispatchDev& a, uint32_
     p.x0 = tx * TILE + p.px0; p.y0 = ty * TILE + p.py0;
     return p;
 }
-
-struct LdsPark {
-    uint32_t* base;         // this lane's column of the wave's slab in LDS: word f of slot k at base[(k * 8 + f) * 64]
-    __device__ __forceinline__ void put(int k, const PendRay& p)
-    {
-        uint32_t* q = base + k * (8 * 64);
-        q[0 * 64] = __float_as_uint(p.ox); q[1 * 64] = __float_as_uint(p.oy); q[2 * 64] = __float_as_uint(p.oz);
-        q[3 * 64] = __float_as_uint(p.dx); q[4 * 64] = __float_as_uint(p.dy); q[5 * 64] = __float_as_uint(p.dz);
-        q[6 * 64] = __float_as_uint(p.w);  q[7 * 64] = p.meta;
-    }
-    __device__ __forceinline__ PendRay get(int k) const
-    {
-        const uint32_t* q = base + k * (8 * 64);
-        PendRay p;
-        p.ox = __uint_as_float(q[0 * 64]); p.oy = __uint_as_float(q[1 * 64]); p.oz = __uint_as_float(q[2 * 64]);
-        p.dx = __uint_as_float(q[3 * 64]); p.dy = __uint_as_float(q[4 * 64]); p.dz = __uint_as_float(q[5 * 64]);
-        p.w = __uint_as_float(q[6 * 64]);  p.meta = q[7 * 64];
-        return p;
-    }
-};
-
 
 } // namespace rr

@@ -28,7 +28,6 @@
 // the next generation's waves take chunks w, w + W, w + 2W, ... of the reserved range and hand their rays out to lanes as those
 // fall idle.  No atomics on the consuming side, none on the image.
 #include <hip/hip_runtime.h>
-#include <cstdio>
 #include "rr_render_common.h"
 
 #ifndef RR_STREAM_WPS
@@ -506,9 +505,6 @@ __global__ __launch_bounds__(256) void k_stream_resolve(DispatchDev a, StreamDev
 }
 
 // ------------------------------------------------------------------------------------ launcher
-static thread_local char g_stream_name[96] = "";
-const char* last_stream_kernel_name() { return g_stream_name; }
-
 template <int STACK, bool STATS, int WPS>
 static hipError_t launch_stream_sw(const SceneDev& sc, const DispatchDev& a, const StreamDev& s, uint32_t n_wg, hipStream_t st)
 {
@@ -520,7 +516,7 @@ static hipError_t launch_stream_sw(const SceneDev& sc, const DispatchDev& a, con
     if (s.n_rect_wb < total_wb)
         hipLaunchKernelGGL((k_stream_background<STATS>), dim3((total_wb - s.n_rect_wb + 3u) / 4u), dim3(256), 0, st, sc, a, s);
     if (s.n_rect_wb == 0u) {        // (a rank without mesh tiles: the background kernel was the whole launch)
-        snprintf(g_stream_name, sizeof g_stream_name, "k_stream_background");
+        set_render_kernel_name("k_stream_background");
         return hipGetLastError();
     }
     hipLaunchKernelGGL((k_stream_primary<STACK, STATS, E, WPS>), dim3(n_wg), dim3(256), (size_t)4 * STACK * 64 * sizeof(E), st, sc, a, s);
@@ -534,7 +530,7 @@ static hipError_t launch_stream_sw(const SceneDev& sc, const DispatchDev& a, con
         ++launches;
     }
     hipLaunchKernelGGL(k_stream_resolve, dim3((s.n_rect_wb + 3u) / 4u), dim3(256), 0, st, a, s);
-    snprintf(g_stream_name, sizeof g_stream_name, "k_stream_primary + k_stream_rays<%d, %s, unsigned short, 1|2, %d> x %d", STACK, STATS ? "true" : "false", WPS, launches);
+    set_render_kernel_name("k_stream_primary + k_stream_rays<%d, %s, unsigned short, 1|2, %d> x %d", STACK, STATS ? "true" : "false", WPS, launches);
     return hipGetLastError();
 }
 

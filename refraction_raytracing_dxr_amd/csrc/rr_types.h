@@ -143,7 +143,7 @@ struct DispatchDev {
 
 // k_render_lds (persistent workgroups, BLAS nodes in LDS): the work queues of one launch.
 // Work is handed out in two phases, a ticket at a time; the wave that draws a ticket shares its blocks with its workgroup
-// through LDS (rr_render.hip).  Phase 1: the screen rectangle that bounds the mesh in every slice of the launch (the projection
+// through LDS (rr_render_lds.hip).  Phase 1: the screen rectangle that bounds the mesh in every slice of the launch (the projection
 // of the BLAS bounds, computed by the host from the slices' constants, widened to 32-pixel columns) in 32x8 strips of one slice
 // each -- these hold every secondary ray, i.e. every expensive block, and start first.  Phase 2: every 32x32 tile of every
 // slice in image order, minus the blocks phase 1 rendered: the background, a microsecond per block, sixteen blocks per ticket.

@@ -21,14 +21,18 @@ def template_args(stack, pend, tlas, e):
     return "<%d, %d, %s, %s>" % (stack, pend, "true" if tlas else "false", e)
 
 
-def kernels(tmp_path):
+def kernels(tmp_path, lib=None, lines=False):
     """{demangled symbol: {"lane": v_readlane / v_writelane, "scratch": scratch_*, "valu": v_* instructions}} of every symbol in
-    the gfx950 code objects of librrdxr.so (built first if it is stale); tmp_path receives the unbundled objects"""
-    import refraction_raytracing_dxr_amd._build as B
+    the gfx950 code objects of librrdxr.so (built first if it is stale); tmp_path receives the unbundled objects.
+    lib: another library or object file to walk instead; lines: every entry also gets "lines", its instruction lines as
+    disassembled, without address comments and without the zero padding behind the last instruction"""
     work = tmp_path / "co"
     work.mkdir()
     so = work / "librrdxr.so"
-    shutil.copy(B.build(), so)
+    if lib is None:
+        import refraction_raytracing_dxr_amd._build as B
+        lib = B.build()
+    shutil.copy(lib, so)
     subprocess.run([OBJDUMP, "--offloading", str(so)], check=True, capture_output=True, cwd=work)
     out = {}
     for f in sorted(work.iterdir()):
@@ -40,9 +44,15 @@ def kernels(tmp_path):
             m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
             if m:
                 cur = out.setdefault(m.group(1), {"lane": 0, "scratch": 0, "valu": 0})
+                if lines:
+                    cur.setdefault("lines", [])
                 continue
             if cur is None:
                 continue
+            if lines:
+                text = line.split("//")[0].strip()
+                if text and text != "...":
+                    cur["lines"].append(text)
             ins = line.strip().split(" ")[0] if line.strip() else ""
             if ins.startswith(("v_readlane", "v_writelane")):
                 cur["lane"] += 1

@@ -131,7 +131,7 @@ def orbit(angle, n, step=0.13, radius=1.0, height=None):
 
 
 def _lds_shape_fits(node_bytes, stack_entries, min_shape):
-    """rr_render.hip lds_kernel_shape: 12x2, 16x2, 16x1 waves x workgroups per CU within 160 KiB of LDS per CU"""
+    """rr_render_lds.hip lds_kernel_shape: 12x2, 16x2, 16x1 waves x workgroups per CU within 160 KiB of LDS per CU"""
     for nw, wgs in ((12, 2), (16, 2), (16, 1))[min_shape:]:
         if node_bytes + nw * stack_entries * 64 * 2 <= 160 * 1024 // wgs - 512:
             return True

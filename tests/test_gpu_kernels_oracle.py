@@ -410,3 +410,43 @@ def test_refitted_two_instance_scene_on_stream_and_paths(make_renderer):
         r.close()
     report("refit", tally)
     assert tally[STREAM] >= 8 and tally[PATHS] >= 8 and tally[FUSED] >= 8
+
+
+# ------------------------------------------------------------------------------------- 6. the name of the kernel that rendered
+# (scene, forced kernel, Depth) -> rr_stats.render_kernel_name without and with RR_DISPATCH_COLLECT_STATS.  The strings are a
+# record: what the library reported while the stream renderer's name and the other kernels' names still had a buffer each.
+RENDERED_BY = [
+    ("monkey", "fused", 3, "k_render_fused<19, 2, false, false, false, unsigned int, 0>",
+     "k_render_fused<19, 2, true, false, false, unsigned int, 0>"),
+    ("monkey", "lds", 3, "k_render_lds<12, 2, false, false>",
+     "k_render_lds<12, 2, true, false>"),
+    ("monkey", "paths", 1, "k_render_paths<19, false, false, false>",
+     "k_render_paths<19, true, false, false>"),
+    ("small", "fused", 3, "k_render_fused<30, 2, false, true, false, unsigned short, 7>",
+     "k_render_fused<30, 2, true, true, false, unsigned short, 7>"),
+    ("small", "stream", 3, "k_stream_primary + k_stream_rays<30, false, unsigned short, 1|2, 6> x 2",
+     "k_stream_primary + k_stream_rays<30, true, unsigned short, 1|2, 6> x 2"),
+]
+
+
+def test_every_renderer_reports_its_kernel_name(make_renderer):
+    """monkey.obj on fused, lds and paths, then the two-instance scene on fused and stream, 64x48, each without and with the
+    counters: after every launch rr_stats names the instantiation that rendered it -- one launcher after the other in one
+    thread, so every name passes through the launchers' one name slot right after another renderer's"""
+    scenes = {"monkey": Scene("monkey-names", [load("monkey.obj")], procedural_env(128, 64, seed=3)), "small": small_scene()}
+    for scene, kernel, depth, plain, counted in RENDERED_BY:
+        r = make_renderer(kernel)
+        scenes[scene].load_gpu(r)
+        for flags, want in ((0, plain), (rr.DISPATCH_COLLECT_STATS, counted)):
+            cams = orbit(0.3, depth)
+            if depth == 1:
+                r.set_camera(cams[0])
+                r.dispatch_rays(64, 48, rr.default_params(flags=flags))
+            else:
+                r.dispatch_rays_batch(64, 48, cams, rr.default_params(flags=flags))
+            r.wait()
+            st = r.stats()
+            print("%s %s depth %d flags %#x: kernel %d %r" % (scene, kernel, depth, flags, st.render_kernel, st.render_kernel_name.decode()))
+            assert st.render_kernel == KERNEL_ID[kernel], (scene, kernel, flags, st.render_kernel)
+            assert st.render_kernel_name.decode() == want, (scene, kernel, flags, st.render_kernel_name)
+        r.close()

@@ -2,8 +2,8 @@
 
     python3 tools/isa_cost.py [kernel-name-substring]     (default: the bench kernel, k_render_fused<19, 2, false, false, ...>)
 
-Compiles csrc/rr_render.hip to assembly with the product flags, takes the kernel whose mangled name contains the
-substring, and sorts every basic block by the loop it sits in (the compiler annotates each block with its innermost
+Compiles the source that holds the kernel (csrc/rr_render_fused.hip, rr_render_paths.hip, rr_render_lds.hip or rr_query.hip) to
+assembly with the product flags, takes the kernel whose mangled name contains the substring, and sorts every basic block by the loop it sits in (the compiler annotates each block with its innermost
 loop):  the innermost loop that holds the slab test (v_fma_mix_f32) is the INTERNAL-NODE trip; the rest of its parent loop
 is the LEAF trip (triangle test, pop); the rest of that one's parent is the per-ray PASS (box-test set-up, hit attributes,
 ClosestHit / Miss); everything outside is per-BLOCK work (RayGen, store).  Vector instructions are counted in three classes
@@ -16,7 +16,9 @@ per trip; bench.py scales them by the fraction of the static count the PMC count
 """
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "refraction_raytracing_dxr_amd", "csrc", "rr_render.hip")
+CSRC = os.path.join(ROOT, "refraction_raytracing_dxr_amd", "csrc")
+SOURCES = {"k_render_fused": "rr_render_fused.hip", "k_render_paths": "rr_render_paths.hip", "k_render_lds": "rr_render_lds.hip",
+           "k_trace_rays": "rr_query.hip", "k_query_rays": "rr_query.hip"}
 FULL = {"v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mac_f32"}
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
 
@@ -31,10 +33,13 @@ def klass(op):
 
 
 def main():
-    want = sys.argv[1] if len(sys.argv) > 1 else "k_render_fusedILi19ELi2ELb0ELb0ELb0EjLb0EE"
+    want = sys.argv[1] if len(sys.argv) > 1 else "k_render_fusedILi19ELi2ELb0ELb0ELb0EjLi0EE"
+    src = next((os.path.join(CSRC, f) for k, f in SOURCES.items() if k in want), None)
+    if src is None:
+        sys.exit("isa_cost: %r names none of %s" % (want, ", ".join(SOURCES)))
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "render.s")
-        subprocess.run(["hipcc", "-x", "hip", SRC, "--offload-arch=gfx950", "-fno-gpu-rdc", "-O3", "-std=c++17", "-ffp-contract=off",
+        subprocess.run(["hipcc", "-x", "hip", src, "--offload-arch=gfx950", "-fno-gpu-rdc", "-O3", "-std=c++17", "-ffp-contract=off",
                         "-fno-fast-math", "--cuda-device-only", "-S", "-o", out], check=True, stderr=subprocess.DEVNULL)
         text = open(out).read().split("\n")
     start = next(i for i, l in enumerate(text) if re.match(r"^_Z\w*%s\w*:" % re.escape(want), l))

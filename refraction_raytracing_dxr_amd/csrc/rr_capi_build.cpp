@@ -286,17 +286,26 @@ int rr_build_blas_ex(rr_context* ctx, uint32_t mesh_id, uint32_t flags)
         if (int r = alloc_refit_state(ctx, n, m.links, m.visit)) return r;
     }
     s.b.nodes = m.nodes.get();
-    RR_HIP(launch_tri_setup(m.d_verts.get(), m.d_idx.get(), n, s.b, ctx->stream));
-    if ((flags & RR_BUILD_PREFER_FAST_TRACE) && !(flags & RR_BUILD_PREFER_FAST_BUILD) && n > 1 && n <= PLOC_MAX_PRIMS)
-        RR_HIP(launch_ploc(s.b, ctx->stream));          // clustered hierarchy (fewer node visits)
-    else
-        RR_HIP(launch_lbvh(s.b, ctx->stream));          // Karras radix tree (fastest build, any size)
-    if (keep) RR_HIP(launch_keep_links(s.b, m.links.get(), ctx->stream));
-    RR_HIP(launch_pack_tris(m.d_verts.get(), m.d_idx.get(), s.b, m.tris.get(), m.nrms.get(), ctx->stream));
+    bool clustered = (flags & RR_BUILD_PREFER_FAST_TRACE) && !(flags & RR_BUILD_PREFER_FAST_BUILD) && n > 1 && n <= PLOC_MAX_PRIMS;
     uint32_t sb[6], depth = 0;
-    RR_HIP(hipMemcpyAsync(sb, s.b.scene_box, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RR_HIP(hipStreamSynchronize(ctx->stream));
+    for (;;) {
+        // (the setup again in front of a second pass: k_ploc used visit[] as scratch, k_refit needs it zero, and depth is a maximum)
+        RR_HIP(launch_tri_setup(m.d_verts.get(), m.d_idx.get(), n, s.b, ctx->stream));
+        if (clustered)
+            RR_HIP(launch_ploc(s.b, ctx->stream));          // clustered hierarchy (fewer node visits)
+        else
+            RR_HIP(launch_lbvh(s.b, ctx->stream));          // Karras radix tree (fastest build, any size)
+        if (keep) RR_HIP(launch_keep_links(s.b, m.links.get(), ctx->stream));
+        RR_HIP(launch_pack_tris(m.d_verts.get(), m.d_idx.get(), s.b, m.tris.get(), m.nrms.get(), ctx->stream));
+        RR_HIP(hipMemcpyAsync(sb, s.b.scene_box, sizeof sb, hipMemcpyDeviceToHost, ctx->stream));
+        RR_HIP(hipMemcpyAsync(&depth, s.b.depth, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RR_HIP(hipStreamSynchronize(ctx->stream));
+        // Where every merged-box area ties (coincident or same-box triangles) the clustered builder merges one pair a round
+        // and its tree is a chain as deep as the mesh is large: past the 64-entry stack the radix tree, whose depth the key
+        // length bounds, is built instead -- nodes, links and leaf records are all written again, so nothing of the chain stays
+        if (!clustered || depth <= 64) break;
+        clustered = false;
+    }
     set_bounds(m, sb);
     m.depth = depth;
     RR_HIP(launch_quantize_nodes(m.qnodes.get(), m.nodes.get(), m.n_nodes(), m.grid, 0, 0, ctx->stream));

@@ -1,0 +1,285 @@
+"""Meshes whose hierarchy has a chosen depth, a CPU model of the default builder, and the stack a traversal needs (test_depth_meshes_cpu.py,
+test_gpu_stack_rungs.py, test_gpu_builder_fallback.py).  No GPU code: numpy only, the package is imported for its record types.
+
+The traversal kernels carry no stack-overflow check: the host picks an instantiation by the built tree's depth (`need`).  A test of a
+rung therefore wants a tree of exactly that depth and a ray that fills the stack to its last entry.  The default builder (k_ploc:
+mutually nearest clusters by merged-box area, one forced pair when no pair is mutual) gives both on chain_mesh(n): triangle k is a
+little larger than triangle k - 1 and a little further along z, so every cluster's nearest neighbour is the one before it, only
+clusters 0 and 1 are ever mutual, one pair merges a round and the tree is a chain: node d holds the chain below it and triangle
+n - 1 - d.  A ray travelling towards +z enters the small end first, so at every node the near child is the chain and the far child,
+a leaf, is pushed: n - 1 entries when it reaches the bottom.  A ray travelling towards -z takes the leaf first and holds one entry.
+
+The margin: cluster [0, k) merged with triangle k has area 4 s_k^2 + 4 s_k k dz (s_k = 1 + 0.05 k); triangle k merged with k + 1
+has 4 s_k^2 + 0.4 s_k + 0.01 + ...: the chain holds while k dz < 0.1, so with dz = 0.0005 to n = 200 and with dz = 0.005 only to
+about 20 -- the areas differ in their second digit, nowhere near an fp32 rounding, and a power-of-two scale keeps every comparison.
+"""
+import itertools
+
+import numpy as np
+
+import refraction_raytracing_dxr_amd as rr
+
+F = np.float32
+PLOC_RADIUS = 16                          # rr_bvh_build.hip
+CHAIN_DEPTHS = (19, 20, 22, 23, 26, 27, 30, 31, 32, 39, 40, 64, 65)
+CHAIN_SCALE = 0.25                        # chain_mesh(65) spans +-1.05: inside the orbit camera's view from five units away
+
+
+def _mesh(P, normal=None):
+    """[n, 3, 3] corner positions -> (VERTEX_DTYPE [3n], uint32 [3n] indices in triangle order); normals: the geometric one"""
+    P = np.asarray(P, F)
+    n = len(P)
+    v = np.zeros(3 * n, rr.VERTEX_DTYPE)
+    v["position"] = P.reshape(-1, 3)
+    if normal is None:
+        g = np.cross((P[:, 1] - P[:, 0]).astype(np.float64), (P[:, 2] - P[:, 0]).astype(np.float64))
+        ln = np.linalg.norm(g, axis=1, keepdims=True)
+        g = np.where(ln > 0, g / np.where(ln > 0, ln, 1), np.array([0.0, 0.0, 1.0]))
+        normal = np.repeat(g, 3, axis=0)
+    v["norm"] = np.asarray(normal, F)
+    return v, np.arange(3 * n, dtype=np.uint32)
+
+
+def chain_mesh(n, front_to_plus_z=False, scale=CHAIN_SCALE, alternate=False):
+    """n triangles (-s, -s, z), (s, -s, z), (0, s, z) with s = 1 + 0.05 k, z = 0.0005 (k - (n - 1) / 2), times `scale` (a power
+    of two).  As listed the geometric normal is +z: the front face is what a ray travelling towards -z sees;
+    front_to_plus_z=True swaps two corners, so the rays that fill the stack (travelling towards +z) see front faces.
+    alternate=True gives every odd triangle the other winding: a stack of glass sheets, each entered through a front face and
+    left through a back face, so the rays of a ray tree cross the whole chain level after level.  The boxes, and so the tree,
+    are the same for every winding."""
+    m, e = np.frexp(scale)
+    assert m == 0.5, "scale must be a power of two"
+    k = np.arange(n, dtype=np.float64)
+    s = (1.0 + 0.05 * k).astype(F)
+    z = (0.0005 * (k - (n - 1) / 2.0)).astype(F)
+    P = np.zeros((n, 3, 3), F)
+    P[:, 0] = np.stack([-s, -s, z], -1)
+    P[:, 1] = np.stack([s, -s, z], -1)
+    P[:, 2] = np.stack([np.zeros(n, F), s, z], -1)
+    swap = np.full(n, bool(front_to_plus_z))
+    if alternate:
+        swap[1::2] = ~swap[1::2]
+    P[swap] = P[swap][:, [0, 2, 1]]
+    return _mesh(P * F(scale))
+
+
+def identical_mesh(n):
+    """n copies of one triangle: every merged-box area ties"""
+    return _mesh(np.tile(np.array([[[0, 0, 0], [1, 0, 0], [0, 1, 0]]], F), (n, 1, 1)))
+
+
+def one_point_mesh(n):
+    """n zero-size triangles at one point: every area is zero"""
+    return _mesh(np.tile(np.array([[[0.25, 0.5, -0.75]] * 3], F), (n, 1, 1)))
+
+
+def same_box_mesh(n):
+    """n triangles on three corners of the unit cube each, chosen so that the triangle's box is the cube: distinct triangles, one
+    box, every area ties"""
+    corners = list(itertools.product((0.0, 1.0), repeat=3))
+    triples = [t for t in itertools.combinations(corners, 3)
+               if all(min(c[a] for c in t) == 0.0 and max(c[a] for c in t) == 1.0 for a in range(3))]
+    assert len(triples) >= 8
+    return _mesh(np.array([triples[k % len(triples)] for k in range(n)], F))
+
+
+DEGENERATE = {"identical-65": lambda: identical_mesh(65), "identical-66": lambda: identical_mesh(66), "identical-200": lambda: identical_mesh(200),
+              "one-point-100": lambda: one_point_mesh(100), "same-box-100": lambda: same_box_mesh(100)}
+
+
+# ------------------------------------------------------------------------------------------- the default builder on the CPU
+def _expand_bits10(v):
+    v = v.astype(np.uint64)
+    v = (v * 0x00010001) & 0xFF0000FF
+    v = (v * 0x00000101) & 0x0F00F00F
+    v = (v * 0x00000011) & 0xC30C30C3
+    v = (v * 0x00000005) & 0x49249249
+    return v
+
+
+def morton_order(verts, idx):
+    """k_tri_boxes + k_morton_keys + the sort, in fp32 -> (sorted primitive indices, fp32 [n, 6] primitive boxes)"""
+    P = verts["position"][np.asarray(idx, np.int64)].reshape(-1, 3, 3).astype(F)
+    box = np.concatenate([P.min(1), P.max(1)], axis=1).astype(F)
+    slo, shi = box[:, :3].min(0), box[:, 3:].max(0)
+    c = F(0.5) * (box[:, :3] + box[:, 3:])
+    ext = shi - slo
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t = np.where(ext > 0, (c - slo) / np.where(ext > 0, ext, F(1)), F(0)).astype(F)
+    q = np.minimum(np.maximum(t * F(1024), F(0)), F(1023)).astype(np.uint32)
+    code = (_expand_bits10(q[:, 0]) << np.uint64(2)) | (_expand_bits10(q[:, 1]) << np.uint64(1)) | _expand_bits10(q[:, 2])
+    keys = (code << np.uint64(32)) | np.arange(len(box), dtype=np.uint64)
+    return np.argsort(keys, kind="stable"), box
+
+
+def ploc_model(verts, idx):
+    """k_ploc restated: the same fp32 areas, candidate order (positions i - 16 .. i + 16 ascending, the first stands unless a
+    smaller area turns up), mutual-pair rule, forced pair and id hand-out -> (NODE_DTYPE nodes as rr_download_blas gives them,
+    leaf position -> primitive, depth as k_depth counts it)"""
+    order, box = morton_order(verts, idx)
+    n = len(order)
+    assert n >= 2
+    node_box = np.zeros((2 * n - 1, 6), F)
+    node_box[n - 1:] = box[order]
+    child = np.zeros((n - 1, 2), np.int64)
+    parent = np.full(2 * n - 1, -1, np.int64)
+    A = list(range(n - 1, 2 * n - 1))
+    next_id, force = n - 2, False
+    while len(A) > 1:
+        m = len(A)
+        B = node_box[A]
+        d = (np.maximum(B[:, None, 3:], B[None, :, 3:]) - np.minimum(B[:, None, :3], B[None, :, :3])).astype(F)
+        with np.errstate(over="ignore", invalid="ignore"):
+            area = (d[..., 0] * d[..., 1] + d[..., 1] * d[..., 2]) + d[..., 2] * d[..., 0]
+        assert area.dtype == F
+        i = np.arange(m)
+        best, nn = np.full(m, np.inf, F), np.full(m, -1, np.int64)
+        for off in [o for o in range(-PLOC_RADIUS, PLOC_RADIUS + 1) if o]:
+            j = i + off
+            ok = (j >= 0) & (j < m)
+            a = area[i, np.clip(j, 0, m - 1)]
+            take = ok & ((nn < 0) | (a < best))
+            best[take], nn[take] = a[take], j[take]
+        if force:
+            nn[0], nn[1] = 1, 0
+        out, merges = [], 0
+        for p in range(m):
+            q = nn[p]
+            mutual = nn[q] == p
+            if mutual and p < q:
+                node = next_id - merges
+                ul, ur = A[p], A[q]
+                node_box[node, :3] = np.minimum(node_box[ul, :3], node_box[ur, :3])
+                node_box[node, 3:] = np.maximum(node_box[ul, 3:], node_box[ur, 3:])
+                child[node] = [~(u - (n - 1)) if u >= n - 1 else u for u in (ul, ur)]
+                parent[ul] = parent[ur] = node
+                out.append(node)
+                merges += 1
+            elif not mutual:
+                out.append(A[p])
+        next_id -= merges
+        force = merges == 0
+        A = out
+    nodes = np.zeros(n - 1, rr.NODE_DTYPE)
+    for k in (0, 1):
+        at = np.where(child[:, k] >= 0, child[:, k], (n - 1) + ~child[:, k])
+        for a, (lo, hi) in enumerate((("lox", "hix"), ("loy", "hiy"), ("loz", "hiz"))):
+            nodes[lo][:, k] = node_box[at, a]
+            nodes[hi][:, k] = node_box[at, 3 + a]
+        nodes["c"][:, k] = child[:, k]
+    depth = 0
+    for leaf in range(n):
+        dl, cur = 1, parent[n - 1 + leaf]
+        while cur >= 0:
+            dl, cur = dl + 1, parent[cur]
+        depth = max(depth, dl)
+    return nodes, order, depth
+
+
+def tree_depth(nodes):
+    """depth of a downloaded hierarchy as the builder counts it: nodes on the longest root-to-leaf path, the leaf included"""
+    if len(nodes) == 0:
+        return 1
+    best, todo = 0, [(0, 1)]
+    while todo:
+        node, d = todo.pop()
+        for c in nodes["c"][node]:
+            if c >= 0:
+                todo.append((int(c), d + 1))
+            else:
+                best = max(best, d + 1)
+    return best
+
+
+def is_chain(nodes):
+    """every internal node has a leaf for its second child and, but for the last, the rest of the chain for its first"""
+    c = nodes["c"]
+    return bool(np.all(c[:, 1] < 0) and np.sum(c[:, 0] < 0) == 1)
+
+
+# --------------------------------------------------------------------------------------------------- the stack a ray needs
+def stack_high_water(nodes, rays):
+    """The deepest stack occupancy of each ray in a near-child-first walk of a downloaded fp32 hierarchy (node_step's rule: both
+    children hit -> follow the one entered first, child 0 on a tie, push the other; a leaf or a node with no child hit pops), in
+    float64, over the whole of [tmin, tmax]: no hit ever shortens the ray, so this is the most a closest-hit walk can hold.
+    nodes: NODE_DTYPE; rays: RAY_DTYPE -> int [n_rays]"""
+    n_rays = len(rays)
+    high = np.zeros(n_rays, np.int64)
+    if len(nodes) == 0 or n_rays == 0:
+        return high
+    O, D = rays["origin"].astype(np.float64), rays["dir"].astype(np.float64)
+    tmin, tmax = rays["tmin"].astype(np.float64), rays["tmax"].astype(np.float64)
+    lo = np.stack([nodes["lox"], nodes["loy"], nodes["loz"]], -1).astype(np.float64)       # [node, child, axis]
+    hi = np.stack([nodes["hix"], nodes["hiy"], nodes["hiz"]], -1).astype(np.float64)
+    cref = nodes["c"].astype(np.int64)
+    DONE = np.iinfo(np.int64).min
+    stack = np.zeros((n_rays, len(nodes) + 1), np.int64)
+    sp = np.zeros(n_rays, np.int64)
+    node = np.zeros(n_rays, np.int64)
+
+    def pop(sel):
+        has = sp[sel] > 0
+        sp[sel[has]] -= 1
+        node[sel[has]] = stack[sel[has], sp[sel[has]]]
+        node[sel[~has]] = DONE
+
+    while True:
+        act = np.nonzero(node != DONE)[0]
+        if len(act) == 0:
+            return high
+        pop(act[node[act] < 0])                                    # a leaf: tested (nothing kept), then the next entry
+        act = act[node[act] >= 0]
+        if len(act) == 0:
+            continue
+        nd = node[act]
+        o, d = O[act][:, None, :], D[act][:, None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t0, t1 = (lo[nd] - o) / d, (hi[nd] - o) / d
+        par = d == 0                                               # parallel to the slab: inside it or not
+        inside = (lo[nd] <= o) & (o <= hi[nd])
+        tn = np.where(par, np.where(inside, -np.inf, np.inf), np.minimum(t0, t1))
+        tf = np.where(par, np.where(inside, np.inf, -np.inf), np.maximum(t0, t1))
+        tn = np.maximum(tn.max(-1), tmin[act][:, None])            # [ray, child]
+        tf = np.minimum(tf.min(-1), tmax[act][:, None])
+        hit = tn <= tf
+        both = hit[:, 0] & hit[:, 1]
+        swap = tn[:, 1] < tn[:, 0]
+        near = np.where(hit[:, 0] & ~(hit[:, 1] & swap), cref[nd, 0], cref[nd, 1])
+        far = np.where(swap, cref[nd, 0], cref[nd, 1])
+        none = ~(hit[:, 0] | hit[:, 1])
+        b = act[both]
+        stack[b, sp[b]] = far[both]
+        sp[b] += 1
+        high[b] = np.maximum(high[b], sp[b])
+        node[act[~none]] = near[~none]
+        pop(act[none])
+
+
+def to_object_space(rays, transform):
+    """rays under the inverse of a 3x4 object-to-world transform (float64 inverse; directions not renormalised, so t is kept)"""
+    T = np.asarray(transform, np.float64).reshape(3, 4)
+    Ri = np.linalg.inv(T[:, :3])
+    out = rays.copy()
+    out["origin"] = ((rays["origin"].astype(np.float64) - T[:, 3]) @ Ri.T).astype(F)
+    out["dir"] = (rays["dir"].astype(np.float64) @ Ri.T).astype(F)
+    return out
+
+
+def to_world_space(rays, transform):
+    """object-space rays under a 3x4 object-to-world transform, directions normalised again"""
+    T = np.asarray(transform, np.float64).reshape(3, 4)
+    out = rays.copy()
+    d = rays["dir"].astype(np.float64) @ T[:, :3].T
+    out["origin"] = (rays["origin"].astype(np.float64) @ T[:, :3].T + T[:, 3]).astype(F)
+    out["dir"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
+    return out
+
+
+def axis_rays(n_side=3, span=0.1, z=3.0):
+    """n_side^2 rays travelling towards +z and as many towards -z through the middle of a chain mesh, then obliques"""
+    g = np.linspace(-span, span, n_side)
+    xy = np.array([(x, y) for y in g for x in g], np.float64)
+    m = len(xy)
+    o = np.concatenate([np.c_[xy, np.full(m, -z)], np.c_[xy, np.full(m, z)]])
+    d = np.concatenate([np.tile([0.0, 0.0, 1.0], (m, 1)), np.tile([0.0, 0.0, -1.0], (m, 1))])
+    return rr.pack_rays(o, d, 1e-4, 100.0)

@@ -1,0 +1,140 @@
+"""GPU: rr_build_blas with default flags builds every mesh that fast_build=True builds.
+
+The default builder (k_ploc) merges mutually nearest clusters by merged-box area.  Where every area ties -- coincident triangles,
+zero-size triangles at one point, triangles that all span one box -- no pair is mutual, the forced pair (clusters 0 and 1) is the
+only merge of a round and the tree is a chain as deep as the mesh has triangles (test_depth_meshes_cpu.py shows it on the CPU
+model: 65, 66, 200, 100 and 100 levels for the five meshes below); past 64 levels rr_build_blas used to answer
+RR_ERR_UNSUPPORTED for a legal mesh.  It now builds the Karras tree instead.  Checked here: the build succeeds, the tree is a
+tree over every leaf with exact child boxes, at most 64 deep and byte for byte the fast_build one; trace_rays equals brute force;
+an ALLOW_UPDATE build of such a mesh refits (its links are the final tree's); and a chain that fits (64 levels) is still the
+clustered builder's, byte for byte what the CPU model says."""
+import numpy as np
+import pytest
+
+import refraction_raytracing_dxr_amd as rr
+from depth_meshes import chain_mesh, DEGENERATE, ploc_model, tree_depth
+from query_helpers import check_closest, oracle_scene
+
+pytestmark = pytest.mark.gpu
+
+MESHES = dict(DEGENERATE)
+MESHES["chain-65"] = lambda: chain_mesh(65)
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    r = rr.Renderer(0)
+    yield r
+    r.close()
+
+
+def check_structure(nodes, tris, verts, idx):
+    """test_lbvh_structure's checks: leaf records of every primitive once, every node and leaf referenced once from the root,
+    every child box the exact union of what is below it"""
+    T = len(idx) // 3
+    assert len(tris) == T and len(nodes) == T - 1
+    assert sorted(tris["prim"].tolist()) == list(range(T))
+    P = verts["position"][idx].reshape(T, 3, 3)
+    assert np.array_equal(tris["v0"], P[tris["prim"], 0])
+    assert np.array_equal(tris["e1"], P[tris["prim"], 1] - P[tris["prim"], 0])
+    assert np.array_equal(tris["e2"], P[tris["prim"], 2] - P[tris["prim"], 0])
+    seen_nodes, seen_leaves = np.zeros(T - 1, int), np.zeros(T, int)
+    seen_nodes[0] = 1
+    order, stack = [], [0]
+    while stack:
+        n = stack.pop()
+        order.append(n)
+        for c in nodes["c"][n]:
+            if c >= 0:
+                seen_nodes[c] += 1
+                stack.append(int(c))
+            else:
+                seen_leaves[~c] += 1
+    assert np.all(seen_nodes == 1) and np.all(seen_leaves == 1)
+    lo = np.full((T - 1, 3), np.inf, np.float32)
+    hi = np.full((T - 1, 3), -np.inf, np.float32)
+    for n in reversed(order):
+        for k in (0, 1):
+            c = nodes["c"][n][k]
+            l = np.array([nodes["lox"][n][k], nodes["loy"][n][k], nodes["loz"][n][k]], np.float32)
+            h = np.array([nodes["hix"][n][k], nodes["hiy"][n][k], nodes["hiz"][n][k]], np.float32)
+            tri = P[tris["prim"][~c]] if c < 0 else None
+            elo, ehi = (tri.min(0), tri.max(0)) if c < 0 else (lo[c], hi[c])
+            assert np.array_equal(l, elo) and np.array_equal(h, ehi), "node %d child %d" % (n, k)
+            lo[n], hi[n] = np.minimum(lo[n], l), np.maximum(hi[n], h)
+
+
+def rays_at(verts, n, seed):
+    """seeded rays from outside towards points of the mesh's box, no culling"""
+    P = verts["position"].astype(np.float64)
+    lo, hi = P.min(0), P.max(0)
+    ext = max(float((hi - lo).max()), 0.5)
+    rng = np.random.default_rng(seed)
+    o = rng.normal(size=(n, 3))
+    o = (lo + hi) / 2 + o / np.linalg.norm(o, axis=1, keepdims=True) * ext * 3
+    d = rng.uniform(lo - 0.05 * ext, hi + 0.05 * ext, (n, 3)) - o
+    return rr.pack_rays(o, d / np.linalg.norm(d, axis=1, keepdims=True), 1e-4, 100.0 * ext)
+
+
+def build(gpu, verts, idx, **kw):
+    mid = gpu.upload_mesh(verts, idx)
+    gpu.build_blas(mid, **kw)
+    gpu.build_tlas(rr.make_instances(meshes=[mid]))
+    return mid
+
+
+@pytest.mark.parametrize("name", list(MESHES))
+def test_default_flags_build_what_fast_build_builds(gpu, name):
+    verts, idx = MESHES[name]()
+    clustered = ploc_model(verts, idx)[2]
+    assert clustered > 64                                     # the clustered tree would not fit the stack
+    mid = build(gpu, verts, idx)
+    depth = gpu.stats().bvh_depth
+    nodes, tris = gpu.download_blas(mid)
+    print("%s: %d triangles, clustered depth %d, built depth %d" % (name, len(idx) // 3, clustered, depth))
+    assert depth <= 64 and tree_depth(nodes) == depth
+    check_structure(nodes, tris, verts, idx)
+    s = oracle_scene([(verts, idx)])
+    rays = rays_at(verts, 400, seed=len(name))
+    n_hit = check_closest(gpu.trace_rays(rays), s, rays)
+    assert n_hit >= (0 if name.startswith("one-point") else 100), n_hit
+    fast = build(gpu, verts, idx, fast_build=True)
+    fnodes, ftris = gpu.download_blas(fast)
+    assert gpu.stats().bvh_depth == depth and nodes.tobytes() == fnodes.tobytes() and tris.tobytes() == ftris.tobytes()
+
+
+def test_update_build_of_a_tied_mesh_refits(gpu):
+    """ALLOW_UPDATE on the 100 same-box triangles: the links kept are those of the tree that was kept, so a refit over moved
+    vertices gives exact boxes and brute-force hits again"""
+    verts, idx = MESHES["same-box-100"]()
+    mid = build(gpu, verts, idx, allow_update=True)
+    assert gpu.stats().bvh_depth <= 64
+    before, _ = gpu.download_blas(mid)
+    rng = np.random.default_rng(17)
+    moved = verts.copy()
+    c, s = np.cos(0.6), np.sin(0.6)
+    R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) * 1.5
+    moved["position"] = (verts["position"].astype(np.float64) @ R.T + rng.normal(size=(len(verts), 3)) * 0.2 + [0.3, -0.2, 0.1]).astype(np.float32)
+    gpu.update_mesh_vertices(mid, moved)
+    gpu.build_blas(mid, update=True)
+    gpu.build_tlas(rr.make_instances(meshes=[mid]))
+    nodes, tris = gpu.download_blas(mid)
+    assert np.array_equal(nodes["c"], before["c"]) and nodes.tobytes() != before.tobytes()
+    check_structure(nodes, tris, moved, idx)
+    rays = rays_at(moved, 400, seed=18)
+    assert check_closest(gpu.trace_rays(rays), oracle_scene([(moved, idx)]), rays) >= 100
+    # and back: the first build's boxes, bit for bit
+    gpu.update_mesh_vertices(mid, verts)
+    gpu.build_blas(mid, update=True)
+    assert gpu.download_blas(mid)[0].tobytes() == before.tobytes()
+
+
+def test_a_chain_that_fits_stays_clustered(gpu):
+    """64 levels fit: the default build is the clustered builder's chain, byte for byte the CPU model's, not the radix tree"""
+    verts, idx = chain_mesh(64)
+    mid = build(gpu, verts, idx)
+    assert gpu.stats().bvh_depth == 64
+    nodes, _ = gpu.download_blas(mid)
+    assert nodes.tobytes() == ploc_model(verts, idx)[0].tobytes()
+    fast = build(gpu, verts, idx, fast_build=True)
+    assert gpu.stats().bvh_depth < 64 and gpu.download_blas(fast)[0].tobytes() != nodes.tobytes()

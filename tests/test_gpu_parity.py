@@ -1462,12 +1462,20 @@ def test_stack_size_boundaries(gpu, levels, fast_build, depth):
             assert hits["prim"][k] == h.prim and np.float32(hits["t"][k]).view(np.uint32) == np.float32(h.t).view(np.uint32)
     # and a frame through the render kernel of that stack size: deterministic, every ray ends in a hit or a miss
     gpu.set_tile_partition(0, 1)
-    gpu.dispatch_rays(320, 180, rr.default_params(max_refract=8, flags=rr.DISPATCH_COLLECT_STATS))
-    a = gpu.read_frame().copy()
+    gpu.dispatch_rays(320, 180, rr.default_params(max_refract=8, flags=rr.DISPATCH_COLLECT_STATS | rr.DISPATCH_FLOAT_OUTPUT))
+    a, acc = (x.copy() for x in gpu.read_frame(want_float=True))
     st = gpu.stats()
     assert st.hits + st.misses == st.rays and st.traversal_overflow == 0
     gpu.dispatch_rays(320, 180, rr.default_params(max_refract=8))
     assert np.array_equal(gpu.read_frame(), a)
+    # and the oracle's frame (path-weight mode, the kernels' summation order): float bits, RGBA8 bytes, the recursion's counters
+    s.set_envmap(procedural_env(32, 16))
+    sc = rr.camera_orbit(0.4)
+    ref = s.render(np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32), 320, 180,
+                   O.default_params(use_bvh=1, max_refract=8, accum_mode=1))
+    assert np.array_equal(acc[..., :3].view(np.uint32), ref["rgb"].view(np.uint32)) and np.array_equal(a, ref["rgba8"])
+    rs = ref["stats"]
+    assert (st.rays, st.hits, st.misses, st.terminal_hits, st.tir) == (rs.rays, rs.hits, rs.misses, rs.terminal_hits, rs.tir)
 
 
 def test_subdivided_monkey_16k_frame_parity(gpu):

@@ -519,6 +519,14 @@ int  rr_download_blas(rr_context* ctx, uint32_t mesh_id, void* nodes, uint32_t* 
  * Every stored box contains its fp32 box. */
 int  rr_download_qnodes(rr_context* ctx, uint32_t mesh_id, void* qnodes, uint32_t* n_nodes, float grid_org_cell[6]);
 
+/* The top level of the scene, read only: nodes: n_nodes*64 B, the fp32 hierarchy over the instances' world boxes as
+ * rr_download_blas gives a BLAS (n_nodes = instances - 1, or 1 for one instance; a leaf ref is ~(triangles of the scene's
+ * distinct BLASes + instance index)); qnodes: n_nodes*32 B, the same nodes as the traversal kernels read them from the head
+ * of the scene's pool, on the scene grid returned in grid_org_cell (layout and meaning as rr_download_qnodes; internal refs
+ * are byte offsets into the pool).  Either pointer may be NULL.  Waits for the context's stream.  RR_ERR_STATE without a built
+ * TLAS (none yet, or invalidated by a BLAS build). */
+int  rr_download_tlas(rr_context* ctx, void* nodes, void* qnodes, uint32_t* n_nodes, float grid_org_cell[6]);
+
 /* ---- pure host helpers (no device, no context) --------------------------------------------- */
 void rr_default_dispatch_params(rr_dispatch_params* p);
 /* Where the box {lo[3], hi[3]} can be seen at all with any of the n constants (GenerateCameraRay, RayTracing.hlsl:27-40):

@@ -426,4 +426,17 @@ int rr_download_qnodes(rr_context* ctx, uint32_t mesh_id, void* qnodes, uint32_t
     if (qnodes) RR_HIP(hipMemcpy(qnodes, m.qnodes.get(), (size_t)nn * sizeof(QNode), hipMemcpyDeviceToHost));
     return RR_OK;
 }
+
+int rr_download_tlas(rr_context* ctx, void* nodes, void* qnodes, uint32_t* n_nodes, float grid_org_cell[6])
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_download_tlas: TLAS not built");
+    const uint32_t nn = ctx->n_insts > 1 ? ctx->n_insts - 1 : 1;
+    if (n_nodes) *n_nodes = nn;
+    if (grid_org_cell) { memcpy(grid_org_cell, ctx->scene_grid.org, 12); memcpy(grid_org_cell + 3, ctx->scene_grid.cell, 12); }
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    if (nodes) RR_HIP(hipMemcpy(nodes, ctx->d_pool_nodes.get(), (size_t)nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    if (qnodes) RR_HIP(hipMemcpy(qnodes, ctx->d_pool_qnodes.get(), (size_t)nn * sizeof(QNode), hipMemcpyDeviceToHost));
+    return RR_OK;
+}
 } // extern "C"

@@ -645,6 +645,19 @@ class Renderer:
         ga = np.array(list(g), np.float32)
         return q, ga[:3], ga[3:]
 
+    def download_tlas(self):
+        """-> (NODE_DTYPE array, QNODE_DTYPE array, grid origin float32[3], grid cell float32[3]): the top level in fp32 and as
+        traversal reads it on the scene grid; a leaf ref is ~(triangles of the scene's distinct meshes + instance)"""
+        from ._capi import QNODE_DTYPE
+        nn = C.c_uint32()
+        g = (C.c_float * 6)()
+        self._ck(self._L.rr_download_tlas(self._h, None, None, C.byref(nn), g), "rr_download_tlas")
+        nodes = np.zeros(nn.value, NODE_DTYPE)
+        q = np.zeros(nn.value, QNODE_DTYPE)
+        self._ck(self._L.rr_download_tlas(self._h, nodes.ctypes.data, q.ctypes.data, C.byref(nn), g), "rr_download_tlas")
+        ga = np.array(list(g), np.float32)
+        return nodes, q, ga[:3], ga[3:]
+
     # convenience: the reference's whole init sequence for one mesh + env map
     def load_scene(self, verts, indices, env_rgb, instances=None):
         mid = self.upload_mesh(verts, indices)

@@ -97,10 +97,14 @@ def _expand_bits10(v):
     return v
 
 
-def morton_order(verts, idx):
-    """k_tri_boxes + k_morton_keys + the sort, in fp32 -> (sorted primitive indices, fp32 [n, 6] primitive boxes)"""
+def tri_boxes(verts, idx):
+    """k_tri_boxes in fp32 -> [n, 6] primitive boxes"""
     P = verts["position"][np.asarray(idx, np.int64)].reshape(-1, 3, 3).astype(F)
-    box = np.concatenate([P.min(1), P.max(1)], axis=1).astype(F)
+    return np.concatenate([P.min(1), P.max(1)], axis=1).astype(F)
+
+
+def morton_keys(box):
+    """k_morton_keys + the sort over fp32 [n, 6] primitive boxes -> the sorted 64-bit keys (code << 32 | primitive), uint64 [n]"""
     slo, shi = box[:, :3].min(0), box[:, 3:].max(0)
     c = F(0.5) * (box[:, :3] + box[:, 3:])
     ext = shi - slo
@@ -108,14 +112,86 @@ def morton_order(verts, idx):
         t = np.where(ext > 0, (c - slo) / np.where(ext > 0, ext, F(1)), F(0)).astype(F)
     q = np.minimum(np.maximum(t * F(1024), F(0)), F(1023)).astype(np.uint32)
     code = (_expand_bits10(q[:, 0]) << np.uint64(2)) | (_expand_bits10(q[:, 1]) << np.uint64(1)) | _expand_bits10(q[:, 2])
-    keys = (code << np.uint64(32)) | np.arange(len(box), dtype=np.uint64)
-    return np.argsort(keys, kind="stable"), box
+    return np.sort((code << np.uint64(32)) | np.arange(len(box), dtype=np.uint64))
+
+
+def morton_order(verts, idx):
+    """k_tri_boxes + k_morton_keys + the sort, in fp32 -> (sorted primitive indices, fp32 [n, 6] primitive boxes)"""
+    box = tri_boxes(verts, idx)
+    return (morton_keys(box) & np.uint64(0xffffffff)).astype(np.int64), box
+
+
+def pack_nodes(n, child, node_box):
+    """k_pack_nodes: child refs [n - 1, 2] and boxes [2n - 1, 6] (internal nodes, then leaves by position) -> NODE_DTYPE [n - 1]"""
+    nodes = np.zeros(n - 1, rr.NODE_DTYPE)
+    for k in (0, 1):
+        at = np.where(child[:, k] >= 0, child[:, k], (n - 1) + ~child[:, k])
+        for a, (lo, hi) in enumerate((("lox", "hix"), ("loy", "hiy"), ("loz", "hiz"))):
+            nodes[lo][:, k] = node_box[at, a]
+            nodes[hi][:, k] = node_box[at, 3 + a]
+        nodes["c"][:, k] = child[:, k]
+    return nodes
+
+
+def _merged_area(a, c):
+    """merged_area of k_ploc on rows of fp32 boxes"""
+    d = (np.maximum(a[:, 3:], c[:, 3:]) - np.minimum(a[:, :3], c[:, :3])).astype(F)
+    with np.errstate(over="ignore", invalid="ignore"):
+        area = (d[:, 0] * d[:, 1] + d[:, 1] * d[:, 2]) + d[:, 2] * d[:, 0]
+    assert area.dtype == F
+    return area
 
 
 def ploc_model(verts, idx):
     """k_ploc restated: the same fp32 areas, candidate order (positions i - 16 .. i + 16 ascending, the first stands unless a
     smaller area turns up), mutual-pair rule, forced pair and id hand-out -> (NODE_DTYPE nodes as rr_download_blas gives them,
-    leaf position -> primitive, depth as k_depth counts it)"""
+    leaf position -> primitive, depth as k_depth counts it).  Areas are computed inside the band only, one vector per offset (the
+    area of a pair is symmetric, so offset +o serves -o too): a round costs 16 vectors of at most m areas, whatever m is."""
+    order, box = morton_order(verts, idx)
+    n = len(order)
+    assert n >= 2
+    node_box = np.zeros((2 * n - 1, 6), F)
+    node_box[n - 1:] = box[order]
+    child = np.zeros((n - 1, 2), np.int64)
+    A = np.arange(n - 1, 2 * n - 1, dtype=np.int64)
+    next_id, force = n - 2, False
+    while len(A) > 1:
+        m = len(A)
+        B = node_box[A]
+        band = {o: _merged_area(B[:m - o], B[o:]) for o in range(1, min(PLOC_RADIUS, m - 1) + 1)}   # band[o][p]: clusters p and p + o
+        best, nn = np.full(m, np.inf, F), np.full(m, -1, np.int64)
+        for off in [o for o in range(-PLOC_RADIUS, PLOC_RADIUS + 1) if o and abs(o) < m]:
+            o = abs(off)
+            i = np.arange(o, m) if off < 0 else np.arange(0, m - o)          # the positions that have a candidate at i + off
+            a = band[o]                                                       # indexed by min(i, i + off), which ascends with i
+            take = (nn[i] < 0) | (a < best[i])
+            best[i[take]], nn[i[take]] = a[take], i[take] + off
+        if force:
+            nn[0], nn[1] = 1, 0
+        i = np.arange(m)
+        mutual = nn[nn] == i
+        merge = mutual & (i < nn)
+        ids = next_id - (np.cumsum(merge) - 1)[merge]                         # handed out downwards in position order
+        ul, ur = A[merge], A[nn[merge]]
+        node_box[ids, :3] = np.minimum(node_box[ul, :3], node_box[ur, :3])
+        node_box[ids, 3:] = np.maximum(node_box[ul, 3:], node_box[ur, 3:])
+        child[ids, 0] = np.where(ul >= n - 1, ~(ul - (n - 1)), ul)
+        child[ids, 1] = np.where(ur >= n - 1, ~(ur - (n - 1)), ur)
+        out = A.copy()
+        out[merge] = ids
+        A = out[~mutual | merge]
+        next_id -= len(ids)
+        force = len(ids) == 0
+    level = np.zeros(2 * n - 1, np.int64)                                     # a parent's id is below its children's
+    level[0] = 1
+    for node, (l, r) in enumerate(child.tolist()):
+        level[l if l >= 0 else (n - 1) + ~l] = level[r if r >= 0 else (n - 1) + ~r] = level[node] + 1
+    return pack_nodes(n, child, node_box), order, int(level[n - 1:].max())
+
+
+def ploc_model_dense(verts, idx):
+    """ploc_model with every pair's area in one [m, m] table a round, O(m^2) memory: the first statement of k_ploc, kept to check
+    the banded one against on small meshes (test_builder_models_cpu.py)"""
     order, box = morton_order(verts, idx)
     n = len(order)
     assert n >= 2
@@ -198,22 +274,21 @@ def is_chain(nodes):
 
 
 # --------------------------------------------------------------------------------------------------- the stack a ray needs
-def stack_high_water(nodes, rays):
-    """The deepest stack occupancy of each ray in a near-child-first walk of a downloaded fp32 hierarchy (node_step's rule: both
-    children hit -> follow the one entered first, child 0 on a tie, push the other; a leaf or a node with no child hit pops), in
-    float64, over the whole of [tmin, tmax]: no hit ever shortens the ray, so this is the most a closest-hit walk can hold.
-    nodes: NODE_DTYPE; rays: RAY_DTYPE -> int [n_rays]"""
+def _near_first_walk(nodes, rays):
+    """The walk stack_high_water and pushed_refs share -> (deepest occupancy per ray, largest internal index pushed by any ray,
+    largest leaf index pushed by any ray; -1 where nothing of the kind was pushed)"""
     n_rays = len(rays)
     high = np.zeros(n_rays, np.int64)
+    top = [-1, -1]                                                 # largest internal index, largest leaf index pushed
     if len(nodes) == 0 or n_rays == 0:
-        return high
+        return high, -1, -1
     O, D = rays["origin"].astype(np.float64), rays["dir"].astype(np.float64)
     tmin, tmax = rays["tmin"].astype(np.float64), rays["tmax"].astype(np.float64)
     lo = np.stack([nodes["lox"], nodes["loy"], nodes["loz"]], -1).astype(np.float64)       # [node, child, axis]
     hi = np.stack([nodes["hix"], nodes["hiy"], nodes["hiz"]], -1).astype(np.float64)
     cref = nodes["c"].astype(np.int64)
     DONE = np.iinfo(np.int64).min
-    stack = np.zeros((n_rays, len(nodes) + 1), np.int64)
+    stack = np.zeros((n_rays, tree_depth(nodes) + 1), np.int64)
     sp = np.zeros(n_rays, np.int64)
     node = np.zeros(n_rays, np.int64)
 
@@ -226,7 +301,7 @@ def stack_high_water(nodes, rays):
     while True:
         act = np.nonzero(node != DONE)[0]
         if len(act) == 0:
-            return high
+            return high, top[0], top[1]
         pop(act[node[act] < 0])                                    # a leaf: tested (nothing kept), then the next entry
         act = act[node[act] >= 0]
         if len(act) == 0:
@@ -249,10 +324,29 @@ def stack_high_water(nodes, rays):
         none = ~(hit[:, 0] | hit[:, 1])
         b = act[both]
         stack[b, sp[b]] = far[both]
+        pushed = far[both]
+        top[0] = max(top[0], int(pushed[pushed >= 0].max(initial=-1)))
+        top[1] = max(top[1], int((~pushed[pushed < 0]).max(initial=-1)))
         sp[b] += 1
         high[b] = np.maximum(high[b], sp[b])
         node[act[~none]] = near[~none]
         pop(act[none])
+
+
+def stack_high_water(nodes, rays):
+    """The deepest stack occupancy of each ray in a near-child-first walk of a downloaded fp32 hierarchy (node_step's rule: both
+    children hit -> follow the one entered first, child 0 on a tie, push the other; a leaf or a node with no child hit pops), in
+    float64, over the whole of [tmin, tmax]: no hit ever shortens the ray, so this is the most a closest-hit walk can hold.
+    nodes: NODE_DTYPE; rays: RAY_DTYPE -> int [n_rays]"""
+    return _near_first_walk(nodes, rays)[0]
+
+
+def pushed_refs(nodes, rays):
+    """The same walk -> (deepest occupancy per ray, the largest internal node index and the largest leaf index (~ref) that any of
+    the rays puts on its stack; -1 for a kind that is never pushed).  A walk that is never shortened by a hit pushes a superset
+    of what a closest-hit traversal pushes in the same child order; a ref counted here is one the far side of a node both of
+    whose boxes the ray enters."""
+    return _near_first_walk(nodes, rays)
 
 
 def to_object_space(rays, transform):

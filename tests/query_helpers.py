@@ -61,16 +61,17 @@ def random_rays(n, seed, radius=4.0, extent=1.2, masks=(0xff,), any_frac=0.0):
     return rr.pack_rays(o, d, tmin, tmax, flags=flags, instance_mask=rng.choice(list(masks), n))
 
 
-def oracle_trace(s, rays, k):
+def oracle_trace(s, rays, k, use_bvh=0):
     return s.trace(rays["origin"][k], rays["dir"][k], float(rays["tmin"][k]), float(rays["tmax"][k]), int(rays["flags"][k]) & 0x30,
-                   use_bvh=0)
+                   use_bvh=use_bvh)
 
 
-def check_closest(hits, s, rays, sel=None, inst_map=None):
-    """hits[k] == the oracle's brute-force closest hit for every k in sel; inst_map: oracle instance -> GPU instance"""
+def check_closest(hits, s, rays, sel=None, inst_map=None, use_bvh=0):
+    """hits[k] == the oracle's brute-force closest hit for every k in sel (use_bvh=1: through the oracle's own hierarchy, for
+    meshes of tens of thousands of triangles); inst_map: oracle instance -> GPU instance"""
     n_hit = 0
     for k in (range(len(rays)) if sel is None else sel):
-        h = oracle_trace(s, rays, k)
+        h = oracle_trace(s, rays, k, use_bvh)
         g = hits[k]
         assert bool(g["hit"]) == bool(h.hit), "ray %d" % k
         if h.hit:

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import refraction_raytracing_dxr_amd as rr
+from builder_models import check_structure
 from depth_meshes import chain_mesh, DEGENERATE, ploc_model, tree_depth
 from query_helpers import check_closest, oracle_scene
 
@@ -26,42 +27,6 @@ def gpu():
     r = rr.Renderer(0)
     yield r
     r.close()
-
-
-def check_structure(nodes, tris, verts, idx):
-    """test_lbvh_structure's checks: leaf records of every primitive once, every node and leaf referenced once from the root,
-    every child box the exact union of what is below it"""
-    T = len(idx) // 3
-    assert len(tris) == T and len(nodes) == T - 1
-    assert sorted(tris["prim"].tolist()) == list(range(T))
-    P = verts["position"][idx].reshape(T, 3, 3)
-    assert np.array_equal(tris["v0"], P[tris["prim"], 0])
-    assert np.array_equal(tris["e1"], P[tris["prim"], 1] - P[tris["prim"], 0])
-    assert np.array_equal(tris["e2"], P[tris["prim"], 2] - P[tris["prim"], 0])
-    seen_nodes, seen_leaves = np.zeros(T - 1, int), np.zeros(T, int)
-    seen_nodes[0] = 1
-    order, stack = [], [0]
-    while stack:
-        n = stack.pop()
-        order.append(n)
-        for c in nodes["c"][n]:
-            if c >= 0:
-                seen_nodes[c] += 1
-                stack.append(int(c))
-            else:
-                seen_leaves[~c] += 1
-    assert np.all(seen_nodes == 1) and np.all(seen_leaves == 1)
-    lo = np.full((T - 1, 3), np.inf, np.float32)
-    hi = np.full((T - 1, 3), -np.inf, np.float32)
-    for n in reversed(order):
-        for k in (0, 1):
-            c = nodes["c"][n][k]
-            l = np.array([nodes["lox"][n][k], nodes["loy"][n][k], nodes["loz"][n][k]], np.float32)
-            h = np.array([nodes["hix"][n][k], nodes["hiy"][n][k], nodes["hiz"][n][k]], np.float32)
-            tri = P[tris["prim"][~c]] if c < 0 else None
-            elo, ehi = (tri.min(0), tri.max(0)) if c < 0 else (lo[c], hi[c])
-            assert np.array_equal(l, elo) and np.array_equal(h, ehi), "node %d child %d" % (n, k)
-            lo[n], hi[n] = np.minimum(lo[n], l), np.maximum(hi[n], h)
 
 
 def rays_at(verts, n, seed):

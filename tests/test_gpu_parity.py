@@ -16,6 +16,7 @@ import pytest
 
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
+from builder_models import check_quantised
 from conftest import procedural_env
 from parity_cases import adversarial_constants, CULL_KINDS, CULL_SIZES, FRAME_CASES
 
@@ -532,22 +533,8 @@ def test_quantised_nodes_contain_the_fp32_boxes(gpu, name):
     gpu.build_blas(mid)
     nodes, _ = gpu.download_blas(mid)
     q, org, cell = gpu.download_qnodes(mid)
-    assert len(q) == len(nodes) and np.all(cell > 0)
-    org, cell = org.astype(np.float64), cell.astype(np.float64)
-    for ax, (lo, hi) in enumerate((("lox", "hix"), ("loy", "hiy"), ("loz", "hiz"))):
-        qlo = org[ax] + q[lo].astype(np.float64) * cell[ax]
-        qhi = org[ax] + q[hi].astype(np.float64) * cell[ax]
-        flo, fhi = nodes[lo].astype(np.float64), nodes[hi].astype(np.float64)
-        real = flo <= fhi                                      # (a one-triangle mesh has an empty second child)
-        assert np.all(np.abs(q[lo][real].astype(np.float64)) <= 32768) and np.all(np.abs(q[hi][real].astype(np.float64)) <= 32768)
-        assert np.all(qlo[real] <= flo[real]) and np.all(qhi[real] >= fhi[real])
-        assert np.all(flo[real] - qlo[real] <= 18 * cell[ax]) and np.all(qhi[real] - fhi[real] <= 18 * cell[ax])
-    c, qc = nodes["c"], q["c"]
-    assert np.array_equal(qc[c < 0], c[c < 0]) and np.array_equal(qc[c >= 0], c[c >= 0] * 32)
-    # the grid spans the mesh bounds, origin at their centre
     P = m.verts["position"][m.indices].astype(np.float64)
-    assert np.all(org - 32768 * cell <= P.min(0)) and np.all(org + 32768 * cell >= P.max(0))
-    assert np.all(np.abs(org - (P.min(0) + P.max(0)) / 2) <= 8 * cell + 1e-6 * np.abs(org))
+    check_quantised(q, org, cell, nodes, P.min(0), P.max(0))
 
 
 def test_fast_build_and_fast_trace_hierarchies_render_the_same_frame(gpu):

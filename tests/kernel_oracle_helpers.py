@@ -1,6 +1,6 @@
-"""What the tests that force each render kernel in turn share (test_gpu_kernels_oracle.py, test_gpu_indexed.py): the renderer
-fixture with its debug switches, scenes with their oracle twins, and a launch checked against the oracle with the kernel that
-rendered it asserted."""
+"""What the tests that force each render kernel in turn share (test_gpu_kernels_oracle.py, test_gpu_indexed.py,
+test_gpu_stack_rungs.py, test_gpu_capacity_edges.py): the renderer fixture with its debug switches, the cached oracle frame of a
+scenes.Scene, orbit cameras, and a launch checked against the oracle with the kernel that rendered it asserted."""
 import collections
 import ctypes as C
 
@@ -36,70 +36,6 @@ def make_renderer(monkeypatch):
     yield make
     for r in made:
         r.close()
-
-
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m.verts, m.indices
-
-
-def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
-    c, sn = np.cos(rot), np.sin(rot)
-    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
-    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
-
-
-class Scene:
-    """meshes [(verts, indices)], instances (blas = index into meshes; None: the reference's one identity instance), env"""
-
-    def __init__(self, key, meshes, env, instances=None):
-        self.key, self.meshes, self.env, self.instances = key, meshes, env, instances
-        self._oracle = None
-        self.single = instances is None
-        lo, hi = [], []
-        for k in range(1 if instances is None else len(instances)):
-            V, I = meshes[0 if instances is None else int(instances["blas"][k])]
-            P = V["position"][np.asarray(I, np.int64)].astype(np.float64)      # the referenced vertices: what the BLAS bounds
-            if instances is not None:
-                T = instances["transform"][k].reshape(3, 4).astype(np.float64)
-                P = P @ T[:, :3].T + T[:, 3]
-            lo.append(P.min(axis=0)); hi.append(P.max(axis=0))
-        self.bounds = (C.c_float * 6)(*[float(v) for v in np.min(lo, axis=0)], *[float(v) for v in np.max(hi, axis=0)])
-
-    def load_gpu(self, r):
-        ids = []
-        for v, i in self.meshes:
-            mid = r.upload_mesh(v, i)
-            r.build_blas(mid)
-            ids.append(mid)
-        if self.instances is None:
-            inst = rr.make_instances(meshes=[ids[0]])
-        else:
-            inst = self.instances.copy()
-            inst["blas"] = [ids[int(b)] for b in inst["blas"]]
-        r.build_tlas(inst)
-        r.upload_envmap(self.env)
-        r.set_tile_partition(0, 1)
-
-    def oracle(self):
-        if self._oracle is None:
-            s = O.Scene()
-            for v, i in self.meshes:
-                s.add_mesh(v, i)
-            if self.instances is not None:
-                inst = np.zeros(len(self.instances), O.INSTANCE_DTYPE)
-                inst["transform"] = self.instances["transform"]
-                inst["id_mask"] = self.instances["instance_id_mask"]
-                inst["hitgroup_flags"] = self.instances["hitgroup_flags"]
-                inst["blas"] = self.instances["blas"]
-                s.set_instances(inst)
-            s.set_envmap(self.env)
-            self._oracle = s
-        return self._oracle
-
-    def n_tris(self):
-        return len(self.meshes[0][1]) // 3
 
 
 _ORACLE_CACHE = {}

@@ -1,6 +1,8 @@
-"""What the tests of the ray-tree queries share (radiance queries, supersampled and adaptive frames: test_gpu_shade.py,
-test_gpu_samples.py, test_gpu_adaptive.py, test_adaptive_cpu.py, test_samples_abi.py, and test_gpu_indexed.py's use of them): views,
-scenes, the oracle-side references and the small frame the sample tests render.  Module-scoped fixtures stay in the test modules."""
+"""The ray-tree and supersampling references (radiance queries, supersampled and adaptive frames: test_gpu_shade.py,
+test_gpu_samples.py, test_gpu_adaptive.py, test_adaptive_cpu.py, test_samples_abi.py, and the use test_gpu_indexed.py,
+test_gpu_stack_rungs.py and test_gpu_capacity_edges.py make of them): views, camera rays, shade_rays against the oracle, two scenes
+of test_gpu_parity.py, the resolve and refinement rules and the small frame the sample tests render.  Meshes and scenes on both
+sides come from scenes.py; module-scoped fixtures stay in the test modules."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +11,7 @@ import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
 from refraction_raytracing_dxr_amd import _capi
+from scenes import load, oracle_scene, xf
 
 F = np.float32
 # the frame of the sample tests: small, since the oracle renders it 4 times as large per axis
@@ -27,12 +30,6 @@ THRESHOLD = 0.1
 STAT_FIELDS = ("rays", "primary", "secondary", "hits", "misses", "terminal_hits", "tir", "node_visits", "tri_tests", "pixels",
                "stats_valid", "traversal_overflow", "bvh_depth", "render_kernel", "node_trips", "leaf_trips", "shade_passes", "waves",
                "background_waves", "render_kernel_name")
-
-
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m
 
 
 def env_map():
@@ -67,38 +64,6 @@ def check_against_oracle(gpu, s, M, cam, w, h, rays, **kw):
     assert f32_tm.tobytes() == f32.tobytes()                    # the float colour is not tone-mapped
     assert np.array_equal(u8_tm.reshape(h, w, 4), ref_tm["rgba8"])
     return ref
-
-
-def oracle_scene(meshes, env, instances):
-    s = O.Scene()
-    for m in meshes:
-        s.add_mesh(m.verts, m.indices)
-    inst = np.zeros(len(instances), O.INSTANCE_DTYPE)
-    inst["transform"] = instances["transform"]
-    inst["id_mask"] = instances["instance_id_mask"]
-    inst["hitgroup_flags"] = instances["hitgroup_flags"]
-    inst["blas"] = instances["blas"]
-    s.set_instances(inst)
-    s.set_envmap(env)
-    return s
-
-
-def gpu_scene(gpu, meshes, env, instances):
-    ids = []
-    for m in meshes:
-        mid = gpu.upload_mesh(m.verts, m.indices)
-        gpu.build_blas(mid)
-        ids.append(mid)
-    instances = instances.copy()
-    instances["blas"] = [ids[int(b)] for b in instances["blas"]]
-    gpu.build_tlas(instances)
-    gpu.upload_envmap(env)
-
-
-def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
-    c, sn = np.cos(rot), np.sin(rot)
-    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
-    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
 
 
 def instanced_scene():
@@ -197,11 +162,7 @@ def oracle_colours(angle, fov, **kw):
     key = (angle, fov, tuple(sorted(kw.items())))
     if key not in _cache:
         if "scene" not in _cache:
-            m = load("monkey.obj")
-            s = O.Scene()
-            s.add_mesh(m.verts, m.indices)
-            s.set_envmap(env_map())
-            _cache["scene"] = s
+            _cache["scene"] = oracle_scene([load("monkey.obj")], env_map())
         _, M, cam = view_constants(angle, fov)
         ref = _cache["scene"].render(M, cam, 4 * W, 4 * H, O.default_params(use_bvh=1, accum_mode=1, use_libm=0, **kw), want_rays=True)
         rgb = ref["rgb"].reshape(H, 4, W, 4, 3).transpose(1, 3, 0, 2, 4)

@@ -12,20 +12,14 @@ import pytest
 
 import refraction_raytracing_dxr_amd as rr
 from shading_helpers import ADAPTIVE_VIEWS as VIEWS
-from shading_helpers import (LIMITS, OFFP16, STAT_FIELDS, THRESHOLD, H, W, adaptive_reference, config4_scene, env_map, gpu_scene, load, oracle_colours,
-                             unorm8, view_constants)
+from scenes import gpu, gpu_scene, load  # noqa: F401  (gpu: a fixture)
+from shading_helpers import (LIMITS, OFFP16, STAT_FIELDS, THRESHOLD, H, W, adaptive_reference, config4_scene, env_map, oracle_colours, unorm8,
+                             view_constants)
 
 pytestmark = pytest.mark.gpu
 
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE, RR_ERR_UNSUPPORTED = 1, 5, 7
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 _scene = {}
@@ -35,7 +29,7 @@ def monkey_scene(gpu):
     """monkey.obj under test_gpu_samples' environment map (built once per renderer)"""
     if _scene.get("monkey") is not gpu:
         m = load("monkey.obj")
-        gpu.load_scene(m.verts, m.indices, env_map())
+        gpu.load_scene(*m, env_map())
         _scene.clear()
         _scene["monkey"] = gpu
 
@@ -263,7 +257,7 @@ def test_refine_pass_as_a_loop_over_the_list(gpu, monkeypatch):
         monkeypatch.delenv("RR_DEBUG_REFINE_GROUPS")
         try:
             m = load("monkey.obj")
-            looped.load_scene(m.verts, m.indices, env_map())
+            looped.load_scene(*m, env_map())
             got = looped.render_adaptive(w, h, sc, (4, OFFP16), 0.0, p, rgba8=True, ray_counts=True, sample_counts=True)
         finally:
             looped.close()

@@ -14,19 +14,12 @@ import pytest
 import refraction_raytracing_dxr_amd as rr
 from builder_models import check_structure
 from depth_meshes import chain_mesh, DEGENERATE, ploc_model, tree_depth
-from query_helpers import check_closest, oracle_scene
+from scenes import build, check_closest, gpu, oracle_scene  # noqa: F401  (gpu: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 MESHES = dict(DEGENERATE)
 MESHES["chain-65"] = lambda: chain_mesh(65)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 def rays_at(verts, n, seed):
@@ -39,13 +32,6 @@ def rays_at(verts, n, seed):
     o = (lo + hi) / 2 + o / np.linalg.norm(o, axis=1, keepdims=True) * ext * 3
     d = rng.uniform(lo - 0.05 * ext, hi + 0.05 * ext, (n, 3)) - o
     return rr.pack_rays(o, d / np.linalg.norm(d, axis=1, keepdims=True), 1e-4, 100.0 * ext)
-
-
-def build(gpu, verts, idx, **kw):
-    mid = gpu.upload_mesh(verts, idx)
-    gpu.build_blas(mid, **kw)
-    gpu.build_tlas(rr.make_instances(meshes=[mid]))
-    return mid
 
 
 @pytest.mark.parametrize("name", list(MESHES))

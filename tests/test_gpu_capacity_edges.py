@@ -23,9 +23,8 @@ from builder_models import (FAMILIES, aimed_rays, check_quantised, check_structu
                             karras_model, karras_tlas_model, same_tree)
 from conftest import procedural_env
 from depth_meshes import ploc_model, pushed_refs, to_object_space, tree_depth
-from kernel_oracle_helpers import (check_slice, counters, dispatch, FUSED, make_renderer, oracle_frame, Scene,  # noqa: F401  (make_renderer: a fixture)
-                                   STREAM)
-from query_helpers import check_closest, load, oracle_scene, xf
+from kernel_oracle_helpers import check_slice, counters, dispatch, FUSED, make_renderer, oracle_frame, STREAM  # noqa: F401  (make_renderer: a fixture)
+from scenes import build, check_closest, gpu, load, oracle_scene, Scene, xf  # noqa: F401  (gpu: a fixture)
 from shading_helpers import check_against_oracle as check_shade
 from test_gpu_query_multi import check_slots
 from test_gpu_query_multi import expected as multi_expected
@@ -40,13 +39,6 @@ KW = dict(max_refract=5)
 FW, FH = 64, 36
 ENV = procedural_env(128, 64, seed=3)
 _meshes = {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 def mesh(family, T):
@@ -66,13 +58,6 @@ def expected_tree(verts, idx, fast_build):
             return m + ("clustered",)
         return karras_model(verts, idx) + ("radix, the clustered tree being %d deep" % m[2],)
     return karras_model(verts, idx) + ("radix",)
-
-
-def build(gpu, verts, idx, **kw):
-    mid = gpu.upload_mesh(verts, idx)
-    gpu.build_blas(mid, **kw)
-    gpu.build_tlas(rr.make_instances(meshes=[mid]))
-    return mid
 
 
 # ------------------------------------------------------------------------------------------------------- A. builder sizes, BLAS
@@ -148,7 +133,7 @@ def check_masked(gpu, cube, inst, rays):
         sel = np.flatnonzero(rays["instance_mask"] == rm)
         keep = np.flatnonzero(inst_masks & rm & 0xff)
         assert len(sel) and len(keep)
-        hits = check_closest(q, oracle_scene([cube], inst[keep]), rays, sel=sel, inst_map=keep)
+        hits = check_closest(q, oracle_scene([cube], instances=inst[keep]), rays, sel=sel, inst_map=keep)
         assert hits > 0, hex(rm)
         n_hit += hits
     return n_hit, q

@@ -19,10 +19,10 @@ import indexed_meshes as IM
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from kernel_oracle_helpers import (FUSED, KERNEL_ID, LDS, PATHS, STREAM, Scene, check_launch, counters, dispatch, load,  # noqa: F401
-                                     make_renderer, orbit, report, xf)
-from query_helpers import check_closest, oracle_scene as bare_oracle_scene, random_rays
+from kernel_oracle_helpers import (FUSED, KERNEL_ID, LDS, PATHS, STREAM, check_launch, counters, dispatch,  # noqa: F401  (make_renderer: a fixture)
+                                   make_renderer, orbit, report)
 from refit_helpers import blas_bytes, deform
+from scenes import Scene, build, check_closest, gpu, load, oracle_scene, random_rays, xf  # noqa: F401  (gpu: a fixture)
 from shading_helpers import camera_rays, check_against_oracle, view_constants
 
 pytestmark = pytest.mark.gpu
@@ -34,13 +34,6 @@ CASES = [(n, v) for n in ASSET_NAMES for v in IM.VARIANTS] + [("grid%d" % n, "na
 SMALL_CASES = [c for c in CASES if c[0] != "grid181"]                 # what the consumers run on (the 65 522-triangle grid: builds only)
 CASE_IDS = ["%s-%s" % (n.replace(".obj", ""), v) for n, v in CASES]
 SMALL_IDS = ["%s-%s" % (n.replace(".obj", ""), v) for n, v in SMALL_CASES]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,12 +53,6 @@ def degenerate_ids(name):
 
 def same(a, b):
     return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
-def build(gpu, V, I, **kw):
-    mid = gpu.upload_mesh(V, I)
-    gpu.build_blas(mid, **kw)
-    return mid
 
 
 def show(gpu, mid):
@@ -126,17 +113,17 @@ def test_indexed_mesh_builds_the_blas_of_its_flat_twin(gpu, name, var, fast_buil
     """nodes, triangle records, traversal nodes, grid and depth of (V, I) == those of (V[I], arange), both builders: a wrong
     gather in k_tri_boxes or k_pack_tris, or bounds / a grid widened by unreferenced vertices, changes a byte"""
     V, I = mesh(name, var)
-    a = blas_state(gpu, build(gpu, V, I, fast_build=fast_build))
-    b = blas_state(gpu, build(gpu, *IM.flat(V, I), fast_build=fast_build))
+    a = blas_state(gpu, build(gpu, V, I, fast_build=fast_build, tlas=False))
+    b = blas_state(gpu, build(gpu, *IM.flat(V, I), fast_build=fast_build, tlas=False))
     for k, what in enumerate(("nodes", "triangle records", "qnodes", "grid origin", "grid cell", "depth")):
         assert a[k] == b[k], what
-    nodes, tris = gpu.download_blas(build(gpu, V, I, fast_build=fast_build))
+    nodes, tris = gpu.download_blas(build(gpu, V, I, fast_build=fast_build, tlas=False))
     T = len(I) // 3
     assert len(tris) == T and np.array_equal(np.sort(tris["prim"]), np.arange(T))
     P = V["position"][I].reshape(T, 3, 3)[tris["prim"]]
     assert same(tris["v0"], P[:, 0]) and same(tris["e1"], P[:, 1] - P[:, 0]) and same(tris["e2"], P[:, 2] - P[:, 0])
     # the grid spans the referenced vertices' bounds (holes / padded: the far ones do not show)
-    _, org, cell = gpu.download_qnodes(build(gpu, V, I, fast_build=fast_build))
+    _, org, cell = gpu.download_qnodes(build(gpu, V, I, fast_build=fast_build, tlas=False))
     ref = V["position"][I].astype(np.float64)
     org, cell = org.astype(np.float64), cell.astype(np.float64)
     assert np.all(org - 32768.0 * cell <= ref.min(0)) and np.all(org + 32768.0 * cell >= ref.max(0))
@@ -150,12 +137,12 @@ def test_closest_hit_queries_on_an_indexed_mesh(gpu, name, var):
     """trace_rays and query_rays: hit, prim, t, u, v == the oracle's brute force over (V, I), and == the flat twin's bytes"""
     V, I = mesh(name, var)
     rays = query_set(name, var, 600 if name == "ott.obj" else 1500)
-    show(gpu, build(gpu, V, I))
+    show(gpu, build(gpu, V, I, tlas=False))
     t, q = gpu.trace_rays(rays), gpu.query_rays(rays)
-    show(gpu, build(gpu, *IM.flat(V, I)))
+    show(gpu, build(gpu, *IM.flat(V, I), tlas=False))
     assert same(t, gpu.trace_rays(rays)) and same(q, gpu.query_rays(rays))
     assert same(t, q)
-    n_hit = check_closest(q, bare_oracle_scene([(V, I)]), rays)
+    n_hit = check_closest(q, oracle_scene([(V, I)]), rays)
     assert n_hit > (len(rays) // 40 if name != "tri" else 5), n_hit
     if var == "degenerate":
         p, deg, dup = degenerate_ids(name)
@@ -173,10 +160,10 @@ def test_multi_hit_queries_on_an_indexed_mesh(gpu, name, var):
     `degenerate`: the duplicate triangle is reported next to its original, an index-degenerate triangle never"""
     V, I = mesh(name, var)
     rays = query_set(name, var, 1500)
-    show(gpu, build(gpu, V, I))
+    show(gpu, build(gpu, V, I, tlas=False))
     hits, counts = gpu.query_rays_multi(rays, 16, counts=True)
     q = gpu.query_rays(rays)
-    show(gpu, build(gpu, *IM.flat(V, I)))
+    show(gpu, build(gpu, *IM.flat(V, I), tlas=False))
     fh, fc = gpu.query_rays_multi(rays, 16, counts=True)
     assert same(hits, fh) and same(counts, fc)
     assert np.array_equal(counts > 0, q["hit"] != 0)
@@ -212,15 +199,15 @@ def test_radiance_queries_on_an_indexed_mesh(gpu, name, var):
     w, h = 96, 72
     env = procedural_env(64, 32, seed=3)
     gpu.upload_envmap(env)
-    s = bare_oracle_scene([(V, I)])
+    s = oracle_scene([(V, I)])
     s.set_envmap(env)
     _, M, cam = view_constants(0.7, 0.45 if name != "ott.obj" else rr.FOV_Y, w, h)
     rays = camera_rays(M, cam, w, h)
-    show(gpu, build(gpu, V, I))
+    show(gpu, build(gpu, V, I, tlas=False))
     ref = check_against_oracle(gpu, s, M, cam, w, h, rays, max_refract=6)
     assert ref["stats"].hits > 100
     a = gpu.shade_rays(rays, rr.default_params(max_refract=6), rgba8=True, ray_counts=True)
-    show(gpu, build(gpu, *IM.flat(V, I)))
+    show(gpu, build(gpu, *IM.flat(V, I), tlas=False))
     b = gpu.shade_rays(rays, rr.default_params(max_refract=6), rgba8=True, ray_counts=True)
     assert all(same(x, y) for x, y in zip(a, b))
 
@@ -312,7 +299,7 @@ def test_unreferenced_vertices_do_not_move_the_mesh_partition(gpu):
         V, I = mesh(name, var)
         parts = []
         for verts, idx in ((V, I), IM.flat(V, I)):
-            mid = build(gpu, verts, idx)
+            mid = build(gpu, verts, idx, tlas=False)
             gpu.build_tlas(rr.make_instances(transforms=[xf(0.1, 0.05, 0, (0.2, 0.2, 0.2), 0.5)], meshes=[mid]))
             gpu.set_tile_partition(1, world)
             parts.append(gpu.mesh_partition_for_orbit(W, H, F, angle=0.3))
@@ -352,7 +339,7 @@ def frame_of(gpu, mid, angle=0.9, W=128, H=96, instances=None):
 
 def check_frame_against_oracle(frame, V, I, env, W=128, H=96, instances=None):
     rgba, f32, cnt, sc = frame
-    s = bare_oracle_scene([(V, I)], instances)
+    s = oracle_scene([(V, I)], instances=instances)
     s.set_envmap(env)
     ref = s.render(np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32), W, H,
                    O.default_params(use_bvh=1, accum_mode=1, max_refract=6))
@@ -375,15 +362,15 @@ def test_vertex_updates_and_refits_with_fewer_vertices_than_indices(gpu, name, v
     assert len(V) != len(I)
     env = procedural_env(64, 32, seed=5)
     gpu.upload_envmap(env)
-    mid = build(gpu, V, I, fast_build=fast_build, allow_update=True)
+    mid = build(gpu, V, I, fast_build=fast_build, allow_update=True, tlas=False)
     built = blas_state(gpu, mid)
-    assert built == blas_state(gpu, build(gpu, V, I, fast_build=fast_build))
+    assert built == blas_state(gpu, build(gpu, V, I, fast_build=fast_build, tlas=False))
     for src in (V, to_device(gpu, V)):
         gpu.update_mesh_vertices(mid, src)
         gpu.build_blas(mid, update=True)
         assert blas_state(gpu, mid) == built
-    twin = build(gpu, *IM.flat(V, I), fast_build=fast_build, allow_update=True)
-    dev = build(gpu, V, I, fast_build=fast_build, allow_update=True)
+    twin = build(gpu, *IM.flat(V, I), fast_build=fast_build, allow_update=True, tlas=False)
+    dev = build(gpu, V, I, fast_build=fast_build, allow_update=True, tlas=False)
     for step, kind in enumerate(("wave", "scale", "jitter")):
         dv = moved(V, kind, seed=step + len(name))
         gpu.update_mesh_vertices(mid, dv)
@@ -402,10 +389,10 @@ def test_vertex_updates_and_refits_with_fewer_vertices_than_indices(gpu, name, v
         rays["origin"] += c.astype(np.float32)
         show(gpu, mid)
         hits = gpu.query_rays(rays)
-        fresh = build(gpu, dv, I, fast_build=fast_build)
+        fresh = build(gpu, dv, I, fast_build=fast_build, tlas=False)
         show(gpu, fresh)
         assert same(hits, gpu.query_rays(rays)), kind
-        assert check_closest(hits, bare_oracle_scene([(dv, I)]), rays) > 0, kind
+        assert check_closest(hits, oracle_scene([(dv, I)]), rays) > 0, kind
         fr = frame_of(gpu, mid)
         ff = frame_of(gpu, fresh)
         assert same(fr[0], ff[0]) and same(fr[1], ff[1]) and fr[2] == ff[2], kind
@@ -419,7 +406,7 @@ def test_moving_only_unreferenced_vertices_changes_nothing(gpu):
     V, I = mesh("monkey.obj", "holes")
     env = procedural_env(64, 32, seed=6)
     gpu.upload_envmap(env)
-    mid = build(gpu, V, I, allow_update=True)
+    mid = build(gpu, V, I, allow_update=True, tlas=False)
     built = blas_state(gpu, mid)
     frame = frame_of(gpu, mid)
     check_frame_against_oracle(frame, V, I, env)
@@ -443,7 +430,7 @@ def test_two_instance_scene_of_an_indexed_mesh_through_blas_and_tlas_updates(gpu
     V, I = mesh("monkey.obj", "shuffled")
     env = procedural_env(128, 64, seed=9)
     gpu.upload_envmap(env)
-    mid = build(gpu, V, I, allow_update=True)
+    mid = build(gpu, V, I, allow_update=True, tlas=False)
 
     def inst_of(m, shift):
         return rr.make_instances(transforms=_pair(shift), meshes=[m, m], masks=[1, 1], flags=[0, rr._capi.INSTANCE_FLAG_CULL_DISABLE])
@@ -462,7 +449,7 @@ def test_two_instance_scene_of_an_indexed_mesh_through_blas_and_tlas_updates(gpu
         st = gpu.stats()
         assert st.traversal_overflow == 0
         check_frame_against_oracle((rgba, f32, counters(st), sc), dv, I, env, 200, 120, inst_of(0, 0.3 * (step + 1)))
-        fresh = build(gpu, dv, I)
+        fresh = build(gpu, dv, I, tlas=False)
         gpu.build_tlas(inst_of(fresh, 0.3 * (step + 1)))
         gpu.dispatch_rays(200, 120, p)
         r2, f2 = gpu.read_frame(want_float=True)
@@ -480,7 +467,7 @@ def test_refusals_leave_an_indexed_mesh_as_it_was():
         nv, ni = len(V), len(I)
         assert nv < ni
         gpu.upload_envmap(procedural_env(64, 32, seed=4))
-        mid = build(gpu, V, I, allow_update=True)
+        mid = build(gpu, V, I, allow_update=True, tlas=False)
         before_blas = blas_state(gpu, mid)
         before = frame_of(gpu, mid)
 

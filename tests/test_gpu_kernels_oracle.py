@@ -21,9 +21,10 @@ import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
 from kernel_oracle_helpers import (check_launch,  # noqa: F401  (make_renderer: a fixture)
-                                   check_slice, COUNTERS, counters, dispatch, FUSED, KERNEL_ID, load, make_renderer, oracle_frame,
-                                   orbit, PATHS, report, Scene, STREAM, xf)
+                                   check_slice, COUNTERS, counters, dispatch, FUSED, KERNEL_ID, make_renderer, oracle_frame, orbit, PATHS,
+                                   report, STREAM)
 from parity_cases import adversarial_constants, CULL_KINDS, CULL_SIZES, FRAME_CASES
+from scenes import load, Scene, xf
 
 pytestmark = pytest.mark.gpu
 

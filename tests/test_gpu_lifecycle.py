@@ -12,9 +12,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
+from kernel_oracle_helpers import orbit
+from scenes import load
 
 pytestmark = pytest.mark.gpu
 
@@ -22,21 +23,11 @@ LEAK_LIMIT = 64 << 20
 LDS = 1             # rr_stats.render_kernel of k_render_lds
 
 
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m.verts, m.indices
-
-
 def free_bytes():
     import torch
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return torch.cuda.mem_get_info(0)[0]
-
-
-def orbit_cams(n, angle=0.3):
-    return [rr.camera_orbit(angle + 0.01 * k) for k in range(n)]
 
 
 def checked_stats(r):
@@ -71,7 +62,7 @@ def two_level_work(r, torch, a, b, verts_a, verts_b):
     rgba, f32 = r.read_frame(want_float=True)
     assert rgba.shape == (H, W, 4) and f32.shape == (H, W, 4)
     checked_stats(r)
-    r.dispatch_rays_batch(1920, 1080, orbit_cams(16))                      # a 1080p Depth 16 frame buffer
+    r.dispatch_rays_batch(1920, 1080, orbit(0.3, 16, step=0.01))         # a 1080p Depth 16 frame buffer
     checked_stats(r)
 
     r.set_frames_in_flight(2)
@@ -133,7 +124,7 @@ def lds_work(r, a):
     k_render_fused"""
     r.build_tlas(rr.make_instances(meshes=[a]))
     W, H = 640, 360
-    cams = orbit_cams(24)
+    cams = orbit(0.3, 24, step=0.01)
     r.dispatch_rays_batch(W, H, cams)
     assert checked_stats(r).render_kernel == LDS
     for _ in range(2):

@@ -19,104 +19,15 @@ import refraction_raytracing_dxr_amd as rr
 from builder_models import check_quantised
 from conftest import procedural_env
 from parity_cases import adversarial_constants, CULL_KINDS, CULL_SIZES, FRAME_CASES
+from scenes import (FLOAT_TOL, check_frame, gpu, gpu_scene, load, oracle_scene, procedural_mesh, random_rays, render_both, soup,  # noqa: F401  (gpu: a fixture)
+                    xf)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLOAT_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
-
-
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m
-
-
-def oracle_scene(meshes, env, instances=None):
-    s = O.Scene()
-    for m in meshes:
-        s.add_mesh(m.verts, m.indices)
-    if instances is not None:
-        inst = np.zeros(len(instances), O.INSTANCE_DTYPE)
-        inst["transform"] = instances["transform"]
-        inst["id_mask"] = instances["instance_id_mask"]
-        inst["hitgroup_flags"] = instances["hitgroup_flags"]
-        inst["blas"] = instances["blas"]
-        s.set_instances(inst)
-    s.set_envmap(env)
-    return s
-
-
-def gpu_scene(gpu, meshes, env, instances=None):
-    ids = []
-    for m in meshes:
-        mid = gpu.upload_mesh(m.verts, m.indices)
-        gpu.build_blas(mid)
-        ids.append(mid)
-    if instances is None:
-        instances = rr.make_instances(meshes=[ids[0]])
-    else:
-        instances = instances.copy()
-        instances["blas"] = [ids[int(b)] for b in instances["blas"]]
-    gpu.build_tlas(instances)
-    gpu.upload_envmap(env)
-    return ids
-
-
-def render_both(gpu, s, angle, W, H, stats=True, **kw):
-    sc = rr.camera_orbit(angle)
-    M, cam = np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
-    flags = rr.DISPATCH_FLOAT_OUTPUT | (rr.DISPATCH_COLLECT_STATS if stats else 0)
-    gpu.set_tile_partition(0, 1)
-    gpu.set_camera(sc)
-    gpu.dispatch_rays(W, H, rr.default_params(flags=flags, **kw))
-    rgba, f32 = gpu.read_frame(want_float=True)
-    st = gpu.stats()
-    lit = s.render(M, cam, W, H, O.default_params(use_bvh=1, **kw))
-    pw = s.render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, **kw))
-    return rgba, f32, st, lit, pw
-
-
-def check_frame(rgba, f32, st, lit, pw):
-    assert st.traversal_overflow == 0
-    o = lit["stats"]
-    assert st.rays == o.rays and st.primary == o.primary and st.secondary == o.secondary
-    if st.stats_valid:
-        assert (st.hits, st.misses, st.terminal_hits, st.tir) == (o.hits, o.misses, o.terminal_hits, o.tir)
-    assert np.all(f32[..., 3] == 1.0) and np.all(rgba[..., 3] == 255)
-    # literal recursive oracle: stated tolerance on every pixel
-    d = np.abs(f32[..., :3] - lit["rgb"])
-    assert d.max() <= FLOAT_TOL, "max |d| %.3g at %s" % (d.max(), np.unravel_index(d.argmax(), d.shape))
-    assert np.abs(rgba.astype(int) - lit["rgba8"].astype(int)).max() <= 1
-    # path-weight oracle (same summation order as the kernel): bit-exact
-    assert np.array_equal(f32[..., :3].view(np.uint32), pw["rgb"].view(np.uint32))
-    assert np.array_equal(rgba, pw["rgba8"])
 
 
 # ------------------------------------------------------------------------------- TraceRay
-def random_rays(n, seed, radius=4.0):
-    rng = np.random.default_rng(seed)
-    rays = np.zeros(n, rr.RAY_DTYPE)
-    o = rng.normal(size=(n, 3))
-    o = o / np.linalg.norm(o, axis=1, keepdims=True) * rng.uniform(0.0, radius, (n, 1))
-    tgt = rng.uniform(-1.2, 1.2, (n, 3))
-    d = tgt - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays["origin"] = o.astype(np.float32)
-    rays["dir"] = d.astype(np.float32)
-    rays["tmin"] = np.where(rng.random(n) < 0.5, 1e-4, 1e-3).astype(np.float32)
-    rays["tmax"] = rng.choice([100.0, 1000.0, 3.0], n).astype(np.float32)
-    rays["flags"] = rng.choice([rr.RAY_FLAG_CULL_BACK, rr.RAY_FLAG_CULL_FRONT, 0], n, p=[0.45, 0.45, 0.1])
-    return rays
-
-
 @pytest.mark.parametrize("name,n", [("cube.obj", 4000), ("sphere.obj", 6000), ("monkey.obj", 6000),
                                     ("shell.obj", 6000), ("ott.obj", 3000)])
 def test_trace_rays_bit_exact_vs_brute_force(gpu, name, n):
@@ -145,34 +56,13 @@ def test_trace_rays_bit_exact_vs_brute_force(gpu, name, n):
     assert n_hit > n // 20
 
 
-def _soup(kind, n, seed):
-    """awkward geometry for the builder and the quantised boxes (vertex records, identity indices)"""
-    rng = np.random.default_rng(seed)
-    if kind == "flat":                     # every triangle in the plane z = 0.25: zero extent on one axis
-        P = rng.uniform(-2, 2, (n, 3, 3)); P[..., 2] = 0.25
-    elif kind == "far":                    # small mesh far from the origin: coordinates ~1e3, extent ~1
-        P = rng.uniform(-0.5, 0.5, (n, 3, 3)) * 0.2 + rng.uniform(-0.5, 0.5, (n, 1, 3)) + np.array([1000.0, -2000.0, 500.0])
-    elif kind == "mixed":                  # huge and tiny triangles, slivers, a few degenerate ones
-        c = rng.uniform(-3, 3, (n, 1, 3))
-        P = c + rng.normal(size=(n, 3, 3)) * rng.choice([1e-4, 1e-2, 0.3, 2.0], (n, 1, 1))
-        P[::17, 1] = P[::17, 0]            # zero-area: two equal vertices
-        P[5::29, 2] = (P[5::29, 0] + P[5::29, 1]) / 2          # zero-area: collinear
-    else:                                  # "line": all centroids on one line (Morton codes collide massively)
-        t = rng.uniform(-2, 2, (n, 1, 1))
-        P = t * np.array([1.0, 1.0, 1.0]) + rng.normal(size=(n, 3, 3)) * 0.01
-    v = np.zeros(n * 3, rr.VERTEX_DTYPE)
-    v["position"] = P.reshape(-1, 3).astype(np.float32)
-    v["norm"] = (0, 0, 1)
-    return v, np.arange(n * 3, dtype=np.uint32)
-
-
 @pytest.mark.parametrize("kind,n", [("flat", 300), ("far", 400), ("mixed", 700), ("line", 500), ("mixed", 1), ("far", 2), ("flat", 3),
                                     ("line", 5), ("mixed", 9), ("far", 33), ("flat", 64), ("mixed", 65)])
 @pytest.mark.parametrize("fast_build", [False, True])
 def test_trace_rays_awkward_geometry_vs_brute_force(gpu, kind, n, fast_build):
     """flat, far-away, wildly mixed-size / degenerate and collinear triangle soups: closest hit through the GPU
     hierarchy (both builders, fp16 boxes on the grid of the bounds) == the oracle's brute force, bit for bit"""
-    verts, idx = _soup(kind, n, seed=n + len(kind))
+    verts, idx = soup(kind, n, seed=n + len(kind))
     mid = gpu.upload_mesh(verts, idx)
     gpu.build_blas(mid, fast_build=fast_build)
     gpu.build_tlas(rr.make_instances(meshes=[mid]))
@@ -372,13 +262,10 @@ def test_stream_renderer_renders_the_same_frames(tmp_path):
     import sys
     code = (
         "import os, sys, numpy as np\n"
-        "sys.path.insert(0, %r)\n"
+        "sys.path[:0] = %r\n"
         "import refraction_raytracing_dxr_amd as rr\n"
         "from refraction_raytracing_dxr_amd.synth import asset, procedural_env\n"
-        "def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):\n"
-        "    c, sn = np.cos(rot), np.sin(rot)\n"
-        "    R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)\n"
-        "    return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)\n"
+        "from scenes import xf\n"
         "r = rr.Renderer(0); out = []; cnt = []\n"
         "ids = []\n"
         "for name in ('cube.obj', 'monkey.obj', 'sphere.obj'):\n"
@@ -457,7 +344,7 @@ def test_stream_renderer_renders_the_same_frames(tmp_path):
         "        r.render_orbit(Wm, Hm, 1, angle=float(aa), params=rr.default_params(max_refract=7), frames_per_dispatch=1); aa = np.float32(aa + np.float32(0.01))\n"
         "        assert np.array_equal(fl[k], r.read_frame().view(np.uint32)[..., 0]), ('in flight', si, k)\n"
         "    out += [fl[6].astype(np.float64)]\n"
-        "np.save(sys.argv[1], np.stack(out)); print(' '.join(str(c) for c in cnt))\n") % ROOT
+        "np.save(sys.argv[1], np.stack(out)); print(' '.join(str(c) for c in cnt))\n") % [ROOT, os.path.dirname(os.path.abspath(__file__))]
     res = {}
     for k in ("fused", "stream"):
         env = dict(os.environ, RR_DEBUG_KERNEL=k)
@@ -514,7 +401,7 @@ def test_builds_are_deterministic(gpu):
     got = []
     for _ in range(2):
         for fast_build in (False, True):
-            mid = gpu.upload_mesh(m.verts, m.indices)
+            mid = gpu.upload_mesh(*m)
             gpu.build_blas(mid, fast_build=fast_build)
             nodes, tris = gpu.download_blas(mid)
             q, org, cell = gpu.download_qnodes(mid)
@@ -528,12 +415,12 @@ def test_quantised_nodes_contain_the_fp32_boxes(gpu, name):
     only has to be conservative: every stored child box must contain its fp32 box (evaluated in float64 from the same
     float32 grid the kernels use), by no more than the fp16 spacing there (<= 16 cells at the faces of the bounds) plus
     the guard cell; child refs are the same tree with internal refs as byte offsets."""
-    m = load(name)
-    mid = gpu.upload_mesh(m.verts, m.indices)
+    verts, idx = load(name)
+    mid = gpu.upload_mesh(verts, idx)
     gpu.build_blas(mid)
     nodes, _ = gpu.download_blas(mid)
     q, org, cell = gpu.download_qnodes(mid)
-    P = m.verts["position"][m.indices].astype(np.float64)
+    P = verts["position"][idx].astype(np.float64)
     check_quantised(q, org, cell, nodes, P.min(0), P.max(0))
 
 
@@ -545,7 +432,7 @@ def test_fast_build_and_fast_trace_hierarchies_render_the_same_frame(gpu):
     gpu.set_camera(rr.camera_orbit(0.9))
     frames, visits = [], []
     for fast_build in (False, True):
-        mid = gpu.upload_mesh(m.verts, m.indices)
+        mid = gpu.upload_mesh(*m)
         gpu.build_blas(mid, fast_build=fast_build)
         gpu.build_tlas(rr.make_instances(meshes=[mid]))
         gpu.dispatch_rays(320, 180, rr.default_params(max_refract=8, flags=rr.DISPATCH_FLOAT_OUTPUT | rr.DISPATCH_COLLECT_STATS))
@@ -580,15 +467,15 @@ def test_trace_rays_empty_and_single_triangle(gpu):
 @pytest.mark.parametrize("name", ["cube.obj", "monkey.obj", "ott.obj"])
 def test_lbvh_structure(gpu, name, fast_build):
     """both builders (PREFER_FAST_TRACE = clustered PLOC tree, PREFER_FAST_BUILD = Karras radix tree)"""
-    m = load(name)
-    mid = gpu.upload_mesh(m.verts, m.indices)
+    verts, idx = load(name)
+    mid = gpu.upload_mesh(verts, idx)
     gpu.build_blas(mid, fast_build=fast_build)
     nodes, tris = gpu.download_blas(mid)
-    T = len(m.indices) // 3
+    T = len(idx) // 3
     assert len(tris) == T and len(nodes) == T - 1
     # leaves are a permutation of the primitives, records hold v0, v1-v0, v2-v0
     assert sorted(tris["prim"].tolist()) == list(range(T))
-    P = m.verts["position"][m.indices].reshape(T, 3, 3)
+    P = verts["position"][idx].reshape(T, 3, 3)
     assert np.array_equal(tris["v0"], P[tris["prim"], 0])
     assert np.array_equal(tris["e1"], P[tris["prim"], 1] - P[tris["prim"], 0])
     assert np.array_equal(tris["e2"], P[tris["prim"], 2] - P[tris["prim"], 0])
@@ -708,11 +595,6 @@ def test_instanced_scene_parity(gpu):
     cube, monkey = load("cube.obj"), load("monkey.obj")
     env = procedural_env(128, 64, seed=7)
 
-    def xf(tx, ty, tz, s=(1, 1, 1), rot=0.0):
-        c, sn = np.cos(rot), np.sin(rot)
-        R = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]], np.float32) * np.array(s, np.float32)
-        return np.concatenate([R, np.array([[tx], [ty], [tz]], np.float32)], axis=1)
-
     inst = rr.make_instances(
         transforms=[xf(0, 0, 0), xf(0, 0, -2.5, (0.5, 0.8, 0.5), 0.4), xf(0.3, 0.2, 2.4, (0.7, 0.7, 0.7), -1.0),
                     xf(0, 1.9, 0, (0.4, 0.4, 0.4), 0.2), xf(0, -1.8, 0.5, (0.5, 0.5, 0.5))],
@@ -721,7 +603,7 @@ def test_instanced_scene_parity(gpu):
     gpu_scene(gpu, [cube, monkey], env, inst)
     s = oracle_scene([cube, monkey], env, inst)
     # TraceRay first: bit-exact incl. instance index
-    rays = random_rays(4000, seed=11, radius=5.0)
+    rays = random_rays(4000, seed=11, radius=5.0, cull_p=(0.45, 0.45, 0.1))
     hits = gpu.trace_rays(rays)
     seen = set()
     for k in range(len(rays)):
@@ -751,19 +633,18 @@ def test_background_culling_equals_tracing_every_primary_ray(gpu, scene):
     if scene == "monkey":
         meshes = [load("monkey.obj")]
     elif scene == "sphere_small":
-        m = load("sphere.obj")
-        v = m.verts.copy(); v["position"] = v["position"] * np.float32(0.15) + np.array([0.4, -0.2, 0.1], np.float32)
-        m.verts = v
-        meshes = [m]
+        v, i = load("sphere.obj")
+        v = v.copy(); v["position"] = v["position"] * np.float32(0.15) + np.array([0.4, -0.2, 0.1], np.float32)
+        meshes = [(v, i)]
     else:
-        def xf(tx, ty, tz, s):
+        def scaled(tx, ty, tz, s):
             return np.concatenate([np.eye(3, dtype=np.float32) * np.float32(s), np.array([[tx], [ty], [tz]], np.float32)], axis=1)
         meshes = [load("cube.obj"), load("monkey.obj")]
-        inst = rr.make_instances(transforms=[xf(0, 0, 0, 0.6), xf(1.2, 0.3, -0.8, 0.3), xf(-0.9, -0.4, 0.7, 0.4)], meshes=[1, 0, 1])
+        inst = rr.make_instances(transforms=[scaled(0, 0, 0, 0.6), scaled(1.2, 0.3, -0.8, 0.3), scaled(-0.9, -0.4, 0.7, 0.4)], meshes=[1, 0, 1])
     gpu_scene(gpu, meshes, env, inst)
     s = oracle_scene(meshes, env, inst)
-    lo = np.min([m.verts["position"].min(axis=0) for m in meshes], axis=0).astype(np.float64)
-    hi = np.max([m.verts["position"].max(axis=0) for m in meshes], axis=0).astype(np.float64)
+    lo = np.min([v["position"].min(axis=0) for v, _ in meshes], axis=0).astype(np.float64)
+    hi = np.max([v["position"].max(axis=0) for v, _ in meshes], axis=0).astype(np.float64)
     if inst is not None:
         lo, hi = np.array([-1.5, -1.0, -1.2]), np.array([1.6, 1.0, 1.2])
     rng = np.random.default_rng({"monkey": 1, "sphere_small": 2, "tlas": 3}[scene])
@@ -908,7 +789,7 @@ def test_error_behaviour():
     with pytest.raises(rr.RRError):
         rr.Renderer(99)
     m = load("cube.obj")
-    r.load_scene(m.verts, m.indices, procedural_env(16, 8))
+    r.load_scene(*m, procedural_env(16, 8))
     with pytest.raises(rr.RRError):
         r.dispatch_rays(64, 64)                                  # camera not set
     r.set_camera(rr.camera_orbit(0.01))
@@ -955,8 +836,7 @@ def test_batched_dispatch_equals_single_dispatches(gpu, name):
     31 levels; the subdivided monkey, 24) -- all three must agree with the oracle-checked single dispatches."""
     if name == "sub2":
         from refraction_raytracing_dxr_amd.synth import subdivide
-        m = rr.Mesh()
-        m.verts, m.indices = subdivide(load("monkey.obj").verts, 2)
+        m = subdivide(load("monkey.obj")[0], 2)
     else:
         m = load(name)
     env = procedural_env(128, 64, seed=13)
@@ -1057,7 +937,7 @@ def _sharded_worker(rank, world, port, backend, out, rgb8=True, W=250, mesh=Fals
     env = procedural_env(128, 64, seed=21)
     r = rr.Renderer(0)
     r.set_stream(torch.cuda.current_stream().cuda_stream)
-    r.load_scene(m.verts, m.indices, env)
+    r.load_scene(*m, env)
     H, K, F = 130, 13, 2                           # 7 batches: every buffer set and both lanes are reused
     # world 1 under nccl: still issue the RCCL gather (async_op, views of the ring buffers), as the N > 1 ranks do
     sf = rr.dist.ShardedFrames(r, W, H, rank, world, torch.device("cuda", 0), frames_per_gather=F, rgb8=rgb8,
@@ -1125,7 +1005,7 @@ def _rotating_worker(rank, world, port, out_dir):
     m = load("monkey.obj")
     r = rr.Renderer(0)
     r.set_stream(torch.cuda.current_stream().cuda_stream)
-    r.load_scene(m.verts, m.indices, procedural_env(128, 64, seed=21))
+    r.load_scene(*m, procedural_env(128, 64, seed=21))
     W, H, K, F = 256, 130, 11, 2                   # batches 0..5: even ones end on rank 0, odd ones on rank 1
     sf = rr.dist.ShardedFrames(r, W, H, rank, world, torch.device("cuda", 0), frames_per_gather=F, rotate_root=True)
     seen = []
@@ -1351,22 +1231,6 @@ def test_native_rccl_gather_entry_points(gpu):
 
 
 # ------------------------------------------------------------------------------- large mesh (builder at scale)
-def procedural_mesh(n_side, seed=0):
-    """bumpy unit-ish sphere patch grid: 2*n_side*n_side triangles with smooth normals"""
-    rng = np.random.default_rng(seed)
-    u, v = np.meshgrid(np.linspace(0.02, np.pi - 0.02, n_side + 1), np.linspace(0, 2 * np.pi, n_side + 1), indexing="ij")
-    rad = 1.0 + 0.08 * np.sin(7 * u) * np.cos(5 * v) + 0.01 * rng.standard_normal(u.shape)
-    P = np.stack([rad * np.sin(u) * np.cos(v), rad * np.cos(u), rad * np.sin(u) * np.sin(v)], -1).astype(np.float32)
-    N = P / np.linalg.norm(P, axis=-1, keepdims=True)
-    idx = np.arange((n_side + 1) * (n_side + 1)).reshape(n_side + 1, n_side + 1)
-    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
-    tri = np.concatenate([np.stack([a, c, b], 1), np.stack([a, d, c], 1)]).astype(np.int64)    # outward winding
-    verts = np.zeros(tri.size, rr.VERTEX_DTYPE)
-    verts["position"] = P.reshape(-1, 3)[tri.ravel()]
-    verts["norm"] = N.reshape(-1, 3)[tri.ravel()].astype(np.float32)
-    return verts, np.arange(tri.size, dtype=np.uint32)
-
-
 def test_large_mesh_build_and_trace(gpu):
     """131 072 triangles: multi-block bitonic sort stages, Karras tree and the fenced bottom-up refit at a
     size where thousands of workgroups on all XCDs take part; structure checked vectorised, TraceRay
@@ -1396,7 +1260,7 @@ def test_large_mesh_build_and_trace(gpu):
         assert np.array_equal(lo[:, k], exp_lo) and np.array_equal(hi[:, k], exp_hi)
     s = O.Scene()
     s.add_mesh(verts, idx)
-    rays = random_rays(3000, seed=99, radius=3.0)
+    rays = random_rays(3000, seed=99, radius=3.0, cull_p=(0.45, 0.45, 0.1))
     hits = gpu.trace_rays(rays)
     nh = 0
     for k in range(len(rays)):
@@ -1430,7 +1294,7 @@ def test_stack_size_boundaries(gpu, levels, fast_build, depth):
     monkey fills the 26-entry stack to the last entry) must still trace like brute force."""
     from refraction_raytracing_dxr_amd.synth import subdivide
     m = load("monkey.obj")
-    v, i = subdivide(m.verts, levels)
+    v, i = subdivide(m[0], levels)
     mid = gpu.upload_mesh(v, i)
     gpu.build_blas(mid, fast_build=fast_build)
     gpu.build_tlas(rr.make_instances(meshes=[mid]))
@@ -1440,7 +1304,7 @@ def test_stack_size_boundaries(gpu, levels, fast_build, depth):
     assert gpu.stats().bvh_depth == depth
     s = O.Scene()
     s.add_mesh(v, i)
-    rays = random_rays(1200, seed=levels * 7 + depth)
+    rays = random_rays(1200, seed=levels * 7 + depth, cull_p=(0.45, 0.45, 0.1))
     hits = gpu.trace_rays(rays)
     for k in range(len(rays)):
         h = s.trace(rays["origin"][k], rays["dir"][k], float(rays["tmin"][k]), float(rays["tmax"][k]), int(rays["flags"][k]), use_bvh=1)
@@ -1471,7 +1335,7 @@ def test_subdivided_monkey_16k_frame_parity(gpu):
     subdivision moves no surface point, the image stays close to the 967-triangle one."""
     from refraction_raytracing_dxr_amd.synth import subdivide
     m = load("monkey.obj")
-    v16, i16 = subdivide(m.verts, 2)
+    v16, i16 = subdivide(m[0], 2)
     assert len(i16) == 3 * 15472
     env = procedural_env(128, 64, seed=5)
     W, H = 256, 144
@@ -1492,7 +1356,7 @@ def test_subdivided_monkey_16k_frame_parity(gpu):
     assert np.array_equal(acc[..., :3].view(np.uint32), ref["rgb"].view(np.uint32))
     assert np.array_equal(rgba, ref["rgba8"])
     # the coarse mesh renders nearly the same picture (shading normals differ slightly: normalised midpoints)
-    gpu.load_scene(m.verts, m.indices, env)
+    gpu.load_scene(*m, env)
     gpu.set_camera(sc)
     gpu.dispatch_rays(W, H, rr.default_params(max_refract=8))
     coarse = gpu.read_frame().astype(int)

@@ -13,19 +13,13 @@ import pytest
 
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from query_helpers import (ANY, bits, check_closest, CULLS, from_dev, gpu_scene, load, MASKED_INSTANCES, oracle_scene, oracle_trace, random_rays,
-                           RAY_MASKS, _soup, to_dev, xf)
+from query_helpers import ANY, CULLS, MASKED_INSTANCES, RAY_MASKS
+from scenes import (bits, check_closest, from_dev, gpu, gpu_scene, load, oracle_scene, oracle_trace, random_rays, soup, to_dev,  # noqa: F401  (gpu: a fixture)
+                    xf)
 
 pytestmark = pytest.mark.gpu
 
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE = 1, 5
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 def check_first_hits(first, closest, rays, meshes, instances=None, sample=300, seed=0):
@@ -49,7 +43,7 @@ def check_first_hits(first, closest, rays, meshes, instances=None, sample=300, s
             inst["blas"] = 0
             inst["instance_id_mask"] = 1 << 24
         tri = np.ascontiguousarray(verts[idx[3 * int(g["prim"]):3 * int(g["prim"]) + 3]])
-        s = oracle_scene([(tri, np.arange(3, dtype=np.uint32))], inst)
+        s = oracle_scene([(tri, np.arange(3, dtype=np.uint32))], instances=inst)
         h = oracle_trace(s, rays, k)
         assert h.hit, "ray %d" % k
         assert bits(g["t"]) == bits(h.t) and bits(g["u"]) == bits(h.u) and bits(g["v"]) == bits(h.v), "ray %d" % k
@@ -59,7 +53,7 @@ def check_first_hits(first, closest, rays, meshes, instances=None, sample=300, s
 def masked_scene(gpu):
     meshes = [load("cube.obj"), load("monkey.obj")]
     inst = rr.make_instances(**MASKED_INSTANCES)
-    gpu_scene(gpu, meshes, inst)
+    gpu_scene(gpu, meshes, instances=inst)
     return meshes, inst
 
 
@@ -77,7 +71,7 @@ def test_closest_query_equals_trace_rays_and_brute_force(gpu, name, n):
 
 @pytest.mark.parametrize("kind,n", [("flat", 300), ("mixed", 700), ("line", 500), ("mixed", 9)])
 def test_closest_query_on_awkward_soups(gpu, kind, n):
-    verts, idx = _soup(kind, n, seed=n + len(kind))
+    verts, idx = soup(kind, n, seed=n + len(kind), collinear=False)
     gpu_scene(gpu, [(verts, idx)])
     P = verts["position"].astype(np.float64)
     ctr, ext = (P.min(0) + P.max(0)) / 2, max(float((P.max(0) - P.min(0)).max()), 1e-3)
@@ -104,7 +98,7 @@ def test_instance_masks_select_instances_like_dxr(gpu):
         if len(keep) == 0:
             assert not q["hit"][sel].any(), hex(rm)
             continue
-        s = oracle_scene(meshes, inst[keep])
+        s = oracle_scene(meshes, instances=inst[keep])
         n_hit = check_closest(q, s, rays, sel=sel, inst_map=keep)
         assert n_hit > 0, hex(rm)
         seen |= set(int(i) for i in q["inst"][sel][q["hit"][sel] != 0])
@@ -304,7 +298,7 @@ def test_queries_after_refit_equal_a_fresh_build(gpu):
     first_rays = rays.copy()
     first_rays["flags"] |= ANY
     refit_closest, refit_first = gpu.query_rays(rays), gpu.query_rays(first_rays)
-    gpu_scene(gpu, [(dv, idx)], inst)
+    gpu_scene(gpu, [(dv, idx)], instances=inst)
     fresh_closest, fresh_first = gpu.query_rays(rays), gpu.query_rays(first_rays)
     assert refit_closest.tobytes() == fresh_closest.tobytes()
     assert refit_closest["hit"].sum() > 600

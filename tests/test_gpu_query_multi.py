@@ -12,20 +12,14 @@ import pytest
 
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
-from query_helpers import bits, from_dev, gpu_scene, load, MASKED_INSTANCES, oracle_scene, random_rays, RAY_MASKS, _soup, to_dev, xf
+from query_helpers import MASKED_INSTANCES, RAY_MASKS
+from scenes import bits, from_dev, gpu, gpu_scene, load, oracle_scene, random_rays, soup, to_dev, xf  # noqa: F401  (gpu: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE = 1, 5
 ANY = rr.RAY_FLAG_ACCEPT_FIRST_HIT
 FRONT, BACK = rr.HIT_KIND_FRONT_FACE, rr.HIT_KIND_BACK_FACE
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 def tri_scenes(meshes, instances=None, clear_cull_disable=False):
@@ -46,7 +40,7 @@ def tri_scenes(meshes, instances=None, clear_cull_disable=False):
             one["hitgroup_flags"] &= ~np.uint32(1 << 24)
         for p in range(len(idx) // 3):
             tri = np.ascontiguousarray(verts[idx[3 * p:3 * p + 3]])
-            out.append((i, p, int(instances["instance_id_mask"][i]) >> 24, oracle_scene([(tri, np.arange(3, dtype=np.uint32))], one)))
+            out.append((i, p, int(instances["instance_id_mask"][i]) >> 24, oracle_scene([(tri, np.arange(3, dtype=np.uint32))], instances=one)))
     return out
 
 
@@ -101,7 +95,7 @@ def instanced_scene(gpu, name):
         meshes = [load("cube.obj")]
         inst = rr.make_instances(transforms=[xf(3.0 * i - 34.5, 0, 0, (0.6, 0.6, 0.6), 0.1 * i) for i in range(24)], meshes=[0] * 24,
                                  masks=[1] * 24)
-    gpu_scene(gpu, meshes, inst)
+    gpu_scene(gpu, meshes, instances=inst)
     return meshes, inst
 
 
@@ -131,7 +125,7 @@ def test_slots_and_counts_are_the_oracles_sorted_set(gpu, name):
         gpu_scene(gpu, meshes)
         rays = random_rays(300, seed=len(name))
     elif name.startswith("soup"):
-        m = _soup(name[5:], 150, seed=7)
+        m = soup(name[5:], 150, seed=7, collinear=False)
         meshes, inst = [m], None
         gpu_scene(gpu, meshes)
         rays = soup_rays(m[0], 300, seed=8)
@@ -195,7 +189,7 @@ def test_coincident_surfaces_return_both_twins_in_order(gpu):
     n_tri = len(idx) // 3
     rays = random_rays(3000, seed=12, masks=(0xff,))
     # two instances of monkey with the same transform
-    gpu_scene(gpu, [(verts, idx)], rr.make_instances(transforms=[xf(0, 0, 0, (1, 1, 1), 0.3)] * 2, meshes=[0, 0], masks=[1, 1]))
+    gpu_scene(gpu, [(verts, idx)], instances=rr.make_instances(transforms=[xf(0, 0, 0, (1, 1, 1), 0.3)] * 2, meshes=[0, 0], masks=[1, 1]))
     for twin_of in ("inst", "prim"):
         if twin_of == "prim":          # one mesh whose every triangle appears twice (prim p and p + n_tri)
             gpu_scene(gpu, [(verts, np.concatenate([idx, idx]))])
@@ -390,7 +384,7 @@ def test_multi_after_refit_equals_a_fresh_build(gpu):
     gpu.build_tlas(ii, update=True)
     rays = random_rays(6000, seed=51, radius=5.0, extent=2.0, masks=(0xff, 1, 2, 3, 0))
     refit = [gpu.query_rays_multi(rays, 16, counts=True), gpu.query_rays_multi(rays, 3)]
-    gpu_scene(gpu, [(dv, idx)], inst)
+    gpu_scene(gpu, [(dv, idx)], instances=inst)
     fresh = [gpu.query_rays_multi(rays, 16, counts=True), gpu.query_rays_multi(rays, 3)]
     assert refit[0][0].tobytes() == fresh[0][0].tobytes() and np.array_equal(refit[0][1], fresh[0][1])
     assert refit[1].tobytes() == fresh[1].tobytes()

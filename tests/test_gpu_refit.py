@@ -16,40 +16,12 @@ import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
 from refit_helpers import blas_bytes, deform, _two_instances
+from scenes import check_closest, check_frame, gpu, load, oracle_scene, procedural_mesh, random_rays, render_both  # noqa: F401  (gpu: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLOAT_TOL = 1e-4
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE = 1, 5
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
-
-
-def load(name):
-    m = rr.Mesh()
-    assert m.load(O.asset(name))
-    return m.verts, m.indices
-
-
-def oracle_scene(meshes, env, instances=None):
-    s = O.Scene()
-    for verts, idx in meshes:
-        s.add_mesh(verts, idx)
-    if instances is not None:
-        inst = np.zeros(len(instances), O.INSTANCE_DTYPE)
-        inst["transform"] = instances["transform"]
-        inst["id_mask"] = instances["instance_id_mask"]
-        inst["hitgroup_flags"] = instances["hitgroup_flags"]
-        inst["blas"] = instances["blas"]
-        s.set_instances(inst)
-    s.set_envmap(env)
-    return s
 
 
 def gpu_refit_scene(gpu, verts, idx, deformed, fast_build=False):
@@ -60,81 +32,6 @@ def gpu_refit_scene(gpu, verts, idx, deformed, fast_build=False):
     gpu.build_blas(mid, update=True)
     gpu.build_tlas(rr.make_instances(meshes=[mid]))
     return mid
-
-
-def procedural_mesh(n_side, seed=0):
-    """bumpy sphere patch grid of 2*n_side*n_side triangles with smooth normals (the large mesh of the parity suite)"""
-    rng = np.random.default_rng(seed)
-    u, v = np.meshgrid(np.linspace(0.02, np.pi - 0.02, n_side + 1), np.linspace(0, 2 * np.pi, n_side + 1), indexing="ij")
-    rad = 1.0 + 0.08 * np.sin(7 * u) * np.cos(5 * v) + 0.01 * rng.standard_normal(u.shape)
-    P = np.stack([rad * np.sin(u) * np.cos(v), rad * np.cos(u), rad * np.sin(u) * np.sin(v)], -1).astype(np.float32)
-    N = P / np.linalg.norm(P, axis=-1, keepdims=True)
-    idx = np.arange((n_side + 1) * (n_side + 1)).reshape(n_side + 1, n_side + 1)
-    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
-    tri = np.concatenate([np.stack([a, c, b], 1), np.stack([a, d, c], 1)]).astype(np.int64)
-    verts = np.zeros(tri.size, rr.VERTEX_DTYPE)
-    verts["position"] = P.reshape(-1, 3)[tri.ravel()]
-    verts["norm"] = N.reshape(-1, 3)[tri.ravel()].astype(np.float32)
-    return verts, np.arange(tri.size, dtype=np.uint32)
-
-
-def random_rays(n, seed, radius=4.0, extent=1.2):
-    rng = np.random.default_rng(seed)
-    rays = np.zeros(n, rr.RAY_DTYPE)
-    o = rng.normal(size=(n, 3))
-    o = o / np.linalg.norm(o, axis=1, keepdims=True) * rng.uniform(0.0, radius, (n, 1))
-    tgt = rng.uniform(-extent, extent, (n, 3))
-    d = tgt - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays["origin"] = o.astype(np.float32)
-    rays["dir"] = d.astype(np.float32)
-    rays["tmin"] = np.where(rng.random(n) < 0.5, 1e-4, 1e-3).astype(np.float32)
-    rays["tmax"] = rng.choice([100.0, 1000.0, 3.0], n).astype(np.float32)
-    rays["flags"] = rng.choice([rr.RAY_FLAG_CULL_BACK, rr.RAY_FLAG_CULL_FRONT, 0], n, p=[0.45, 0.45, 0.1])
-    return rays
-
-
-def check_trace(gpu, s, rays, use_bvh=0):
-    hits = gpu.trace_rays(rays)
-    n_hit = 0
-    for k in range(len(rays)):
-        h = s.trace(rays["origin"][k], rays["dir"][k], float(rays["tmin"][k]), float(rays["tmax"][k]), int(rays["flags"][k]),
-                    use_bvh=use_bvh)
-        g = hits[k]
-        assert bool(g["hit"]) == bool(h.hit), "ray %d" % k
-        if h.hit:
-            n_hit += 1
-            assert g["prim"] == h.prim, "ray %d" % k
-            assert np.float32(g["t"]).view(np.uint32) == np.float32(h.t).view(np.uint32), "ray %d" % k
-            assert np.float32(g["u"]).view(np.uint32) == np.float32(h.u).view(np.uint32), "ray %d" % k
-            assert np.float32(g["v"]).view(np.uint32) == np.float32(h.v).view(np.uint32), "ray %d" % k
-    return n_hit
-
-
-def check_frame(rgba, f32, st, lit, pw):
-    assert st.traversal_overflow == 0
-    o = lit["stats"]
-    assert st.rays == o.rays and st.primary == o.primary and st.secondary == o.secondary
-    if st.stats_valid:
-        assert (st.hits, st.misses, st.terminal_hits, st.tir) == (o.hits, o.misses, o.terminal_hits, o.tir)
-    d = np.abs(f32[..., :3] - lit["rgb"])
-    assert d.max() <= FLOAT_TOL, "max |d| %.3g at %s" % (d.max(), np.unravel_index(d.argmax(), d.shape))
-    assert np.abs(rgba.astype(int) - lit["rgba8"].astype(int)).max() <= 1
-    assert np.array_equal(f32[..., :3].view(np.uint32), pw["rgb"].view(np.uint32))
-    assert np.array_equal(rgba, pw["rgba8"])
-
-
-def render_both(gpu, s, angle, W, H, **kw):
-    sc = rr.camera_orbit(angle)
-    M, cam = np.array(sc.proj_inv, np.float32), np.array(sc.camera_loc, np.float32)
-    gpu.set_tile_partition(0, 1)
-    gpu.set_camera(sc)
-    gpu.dispatch_rays(W, H, rr.default_params(flags=rr.DISPATCH_FLOAT_OUTPUT | rr.DISPATCH_COLLECT_STATS, **kw))
-    rgba, f32 = gpu.read_frame(want_float=True)
-    st = gpu.stats()
-    lit = s.render(M, cam, W, H, O.default_params(use_bvh=1, **kw))
-    pw = s.render(M, cam, W, H, O.default_params(use_bvh=1, accum_mode=1, **kw))
-    return rgba, f32, st, lit, pw
 
 
 # ----------------------------------------------------------------------------------------- 1. identity refit
@@ -165,9 +62,10 @@ def test_refitted_mesh_traces_bit_exact_vs_brute_force(gpu, name, kind):
     s = oracle_scene([(dv, idx)], procedural_env(32, 16))
     P = dv["position"].astype(np.float64)
     c, r = (P.min(0) + P.max(0)) / 2, np.abs(P.max(0) - P.min(0)).max() / 2
-    rays = random_rays(3000 if name == "monkey.obj" else 1500, seed=len(name) + len(kind), radius=4.0 * r, extent=1.2 * r)
+    rays = random_rays(3000 if name == "monkey.obj" else 1500, seed=len(name) + len(kind), radius=4.0 * r, extent=1.2 * r,
+                       cull_p=(0.45, 0.45, 0.1))
     rays["origin"] += c.astype(np.float32)
-    assert check_trace(gpu, s, rays) > len(rays) // 20
+    assert check_closest(gpu.trace_rays(rays), s, rays) > len(rays) // 20
 
 
 def test_refitted_large_mesh_traces_bit_exact(gpu):
@@ -177,7 +75,8 @@ def test_refitted_large_mesh_traces_bit_exact(gpu):
     dv = deform(verts, "wave", seed=5)
     mid = gpu_refit_scene(gpu, verts, idx, dv, fast_build=True)
     s = oracle_scene([(dv, idx)], procedural_env(32, 16))
-    assert check_trace(gpu, s, random_rays(400, seed=41, radius=3.0)) > 40
+    rays = random_rays(400, seed=41, radius=3.0, cull_p=(0.45, 0.45, 0.1))
+    assert check_closest(gpu.trace_rays(rays), s, rays) > 40
     # the same refit equals a fresh build of the deformed vertices wherever the hierarchy does not show: triangle records
     # per primitive, bounds
     fresh = gpu.upload_mesh(dv, idx)

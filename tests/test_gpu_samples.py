@@ -13,21 +13,14 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from shading_helpers import (CELL16, LIMITS, STAT_FIELDS, SUB4, H, W, config4_scene, env_map, fold, gpu_scene, instanced_scene, load, oracle_scene,
-                             unorm8, view_constants)
+from scenes import gpu, gpu_scene, load, oracle_scene  # noqa: F401  (gpu: a fixture)
+from shading_helpers import CELL16, LIMITS, STAT_FIELDS, SUB4, H, W, config4_scene, env_map, fold, instanced_scene, unorm8, view_constants
 
 pytestmark = pytest.mark.gpu
 
 RR_ERR_INVALID_ARGUMENT, RR_ERR_STATE, RR_ERR_UNSUPPORTED = 1, 5, 7
 VIEWS = [(0.01, rr.FOV_Y), (1.3, 0.35), (3.7, 0.2)]
 OFF16 = np.array([[(2 * i + 1) / 8.0, (2 * j + 1) / 8.0] for i, j in CELL16], np.float32)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
 
 
 def check(got, want_rgb, want_cnt, tonemap):
@@ -52,7 +45,7 @@ def shade_fold(gpu, sc, w, h, offsets, p):
 
 def monkey_scene(gpu):
     m = load("monkey.obj")
-    gpu.load_scene(m.verts, m.indices, env_map())
+    gpu.load_scene(*m, env_map())
 
 
 # ------------------------------------------------------------------------------------------------- 1. one centre sample is a dispatch
@@ -86,10 +79,8 @@ def single_scene(gpu, name):
     if _single.get("name") != name:
         m = load(name)
         env = env_map()
-        gpu.load_scene(m.verts, m.indices, env)
-        s = O.Scene()
-        s.add_mesh(m.verts, m.indices)
-        s.set_envmap(env)
+        gpu.load_scene(*m, env)
+        s = oracle_scene([m], env)
         _single.clear()
         _single.update(name=name, s=s)
     return _single["s"]
@@ -328,13 +319,13 @@ def test_supersampled_frames_need_a_built_scene(gpu):
                 assert e.value.status == RR_ERR_STATE
         refused()                                                               # nothing built
         m = load("cube.obj")
-        mid = fresh.upload_mesh(m.verts, m.indices)
+        mid = fresh.upload_mesh(*m)
         fresh.build_blas(mid, allow_update=True)
         refused()                                                               # BLAS built, no TLAS yet
         fresh.build_tlas(rr.make_instances(meshes=[mid]), allow_update=True)
         fresh.upload_envmap(procedural_env(64, 32, seed=1))
         a = fresh.render_samples(8, 8, sc, 4)
-        fresh.update_mesh_vertices(mid, m.verts)
+        fresh.update_mesh_vertices(mid, m[0])
         fresh.build_blas(mid, update=True)
         refused()                                                               # BLAS updated, TLAS not
         fresh.build_tlas(rr.make_instances(meshes=[mid]), update=True)

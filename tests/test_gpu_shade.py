@@ -11,8 +11,8 @@ import pytest
 import oracle as O
 import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
-from shading_helpers import (STAT_FIELDS, camera_rays, check_against_oracle, config4_scene, gpu_scene, instanced_scene, load, oracle_scene,
-                             view_constants, xf)
+from scenes import gpu, gpu_scene, load, oracle_scene, to_dev, xf  # noqa: F401  (gpu: a fixture)
+from shading_helpers import STAT_FIELDS, camera_rays, check_against_oracle, config4_scene, instanced_scene, view_constants
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +25,6 @@ VIEWS = [(0.01, rr.FOV_Y), (1.3, 0.35), (3.7, 0.2)]
 LIMITS = [(mr, ml, 1.2) for mr in (0, 1, 5, 11) for ml in (0, 2, 3)] + [(5, 2, 1.5), (11, 3, 1.05)]     # ml = 3: the PEND = 8 builds
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    r = rr.Renderer(0)
-    yield r
-    r.close()
-
-
 # ------------------------------------------------------------------------------------------------- 1. oracle parity, one BLAS
 _single = {}
 
@@ -41,10 +34,8 @@ def single_scene(gpu, name):
     if _single.get("name") != name:
         m = load(name)
         env = procedural_env(128, 64, seed=3)
-        gpu.load_scene(m.verts, m.indices, env)
-        s = O.Scene()
-        s.add_mesh(m.verts, m.indices)
-        s.set_envmap(env)
+        gpu.load_scene(*m, env)
+        s = oracle_scene([m], env)
         views = []
         for angle, fov in VIEWS:
             _, M, cam = view_constants(angle, fov, W, H)
@@ -101,7 +92,7 @@ def test_oracle_parity_config4_scene(gpu):
 # ------------------------------------------------------------------------------------------------- 3. equals a dispatch
 def monkey_scene(gpu):
     m = load("monkey.obj")
-    gpu.load_scene(m.verts, m.indices, procedural_env(128, 64, seed=5))
+    gpu.load_scene(*m, procedural_env(128, 64, seed=5))
 
 
 @pytest.mark.parametrize("flags", [0, rr.DISPATCH_TONEMAP_REINHARD])
@@ -153,13 +144,6 @@ def test_order_and_neighbours_do_not_matter(gpu):
 
 
 # ------------------------------------------------------------------------------------------------- 5. device path
-def to_dev(rays, gpu, dtype="int32"):
-    import torch
-    a = np.ascontiguousarray(rays).view(np.int32).reshape(-1, 12)
-    t = torch.from_numpy(a.copy()).to("cuda:%d" % gpu.device)
-    return t.view(torch.float32) if dtype == "float32" else t
-
-
 def test_device_path_equals_host_path(gpu):
     import torch
     monkey_scene(gpu)
@@ -249,7 +233,7 @@ def test_host_calls_share_one_staged_output_set(gpu):
     tensors, which does not touch the set."""
     import torch
     m = load("cube.obj")
-    gpu.load_scene(m.verts, m.indices, procedural_env(128, 64, seed=5))
+    gpu.load_scene(*m, procedural_env(128, 64, seed=5))
     p = rr.default_params(max_refract=8)
     _, M, cam = view_constants(1.3, 0.35, 20, 15)
     rays = camera_rays(M, cam, 20, 15)
@@ -323,7 +307,7 @@ def test_radiance_queries_need_a_built_scene(gpu):
                 fresh.shade_rays(r)                                             # nothing built
             assert e.value.status == RR_ERR_STATE
         m = load("cube.obj")
-        mid = fresh.upload_mesh(m.verts, m.indices)
+        mid = fresh.upload_mesh(*m)
         fresh.build_blas(mid, allow_update=True)
         for r in (rays, t):
             with pytest.raises(rr.RRError) as e:
@@ -332,7 +316,7 @@ def test_radiance_queries_need_a_built_scene(gpu):
         fresh.build_tlas(rr.make_instances(meshes=[mid]), allow_update=True)
         fresh.upload_envmap(procedural_env(64, 32, seed=1))
         a = fresh.shade_rays(rays)
-        fresh.update_mesh_vertices(mid, m.verts)
+        fresh.update_mesh_vertices(mid, m[0])
         fresh.build_blas(mid, update=True)
         for r in (rays, t):
             with pytest.raises(rr.RRError) as e:

@@ -30,8 +30,9 @@ import refraction_raytracing_dxr_amd as rr
 from conftest import procedural_env
 from depth_meshes import axis_rays, chain_mesh, stack_high_water, to_object_space, to_world_space, tree_depth
 from kernel_oracle_helpers import (check_launch,  # noqa: F401  (make_renderer: a fixture)
-                                   dispatch, expected_kernel, FUSED, LDS, load, make_renderer, PATHS, report, Scene, STREAM, xf)
-from query_helpers import check_closest, CULLS
+                                   dispatch, expected_kernel, FUSED, LDS, make_renderer, PATHS, report, STREAM)
+from query_helpers import CULLS
+from scenes import check_closest, load, Scene, xf
 from shading_helpers import OFFP16, PERM16, THRESHOLD, fold
 from shading_helpers import check_against_oracle as check_shade
 from test_gpu_adaptive import follows_the_rule

@@ -11,18 +11,11 @@ import pytest
 import indexed_meshes as IM
 import oracle as O
 from refraction_raytracing_dxr_amd.synth import procedural_env
+from scenes import load, oracle_scene
 
 ASSETS = ["cube.obj", "sphere.obj", "monkey.obj", "shell.obj", "ott.obj"]
 # vertices of the shipped meshes welded on whole 32-byte records / on positions alone
 WELDED = {"cube.obj": 24, "sphere.obj": 441, "monkey.obj": 556, "shell.obj": 882, "ott.obj": 8255}
-
-
-def load(name):
-    m = O.mesh_load(O.asset(name))
-    assert m is not None
-    verts, idx = m
-    assert np.array_equal(idx, np.arange(len(verts), dtype=np.uint32))       # the loader's meshes are un-indexed
-    return verts, idx
 
 
 def same_bytes(a, b):
@@ -111,13 +104,6 @@ def stat_tuple(st):
     return tuple(tuple(getattr(st, f)) if f == "rays_per_level" else int(getattr(st, f)) for f in STAT_FIELDS)
 
 
-def oracle_scene(V, I, env):
-    s = O.Scene()
-    s.add_mesh(V, I)
-    s.set_envmap(env)
-    return s
-
-
 def trace_rays(n, seed, centre, radius):
     rng = np.random.default_rng(seed)
     o = rng.normal(size=(n, 3))
@@ -131,7 +117,7 @@ def assert_oracle_equal(V, I, W=96, H=72, angle=0.4, n_rays=200, seed=0, tag="")
     """the oracle on (V, I) == the oracle on the flat twin: path-weight frame (float bits, RGBA8, per-pixel ray counts, every
     Stats counter), and brute-force and BVH traces of random rays"""
     env = procedural_env(64, 32, seed=7)
-    a, b = oracle_scene(V, I, env), oracle_scene(*IM.flat(V, I), env)
+    a, b = oracle_scene([(V, I)], env), oracle_scene([IM.flat(V, I)], env)
     M, cam = O.camera(angle)
     p = O.default_params(use_bvh=1, accum_mode=1, max_refract=8)
     ra, rb = a.render(M, cam, W, H, p, want_rays=True), b.render(M, cam, W, H, p, want_rays=True)
@@ -160,7 +146,7 @@ def test_oracle_renders_and_traces_a_variant_as_its_flat_twin(name, var):
     assert ra["stats"].hits > 100 and n_hit > 5                                # the mesh is in view and in the rays' way
     if var in ("welded", "shuffled", "holes", "padded"):
         # ... and as the un-indexed source itself
-        src = oracle_scene(verts, idx, procedural_env(64, 32, seed=7)).render(*O.camera(0.4), 96, 72, O.default_params(use_bvh=1, accum_mode=1, max_refract=8))
+        src = oracle_scene([(verts, idx)], procedural_env(64, 32, seed=7)).render(*O.camera(0.4), 96, 72, O.default_params(use_bvh=1, accum_mode=1, max_refract=8))
         assert np.array_equal(ra["rgb"].view(np.uint32), src["rgb"].view(np.uint32))
         assert stat_tuple(ra["stats"])[:8] == stat_tuple(src["stats"])[:8]
 
@@ -185,7 +171,7 @@ def test_oracle_on_the_single_triangle_and_the_degenerate_additions():
     nrm /= np.linalg.norm(nrm)
     env = procedural_env(16, 8)
     for t in [p, dup] + deg:
-        one = oracle_scene(D, np.ascontiguousarray(DI[3 * t:3 * t + 3]), env)
+        one = oracle_scene([(D, np.ascontiguousarray(DI[3 * t:3 * t + 3]))], env)
         for sign in (1.0, -1.0):
             h = one.trace(c + sign * 0.5 * nrm, -sign * nrm, 1e-4, 100.0, 0, use_bvh=0)
             assert bool(h.hit) == (t in (p, dup)), t

@@ -502,6 +502,37 @@ int  rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height,
                                float threshold, void* d_rgba32f, void* d_rgba8, void* d_n_rays, void* d_n_taken,
                                void* d_workspace, uint64_t workspace_bytes);
 
+/* ---- thin-lens frames: depth of field in the supersampling kernel (present from ABI version 3) ---------------------------------
+ * A supersampled frame whose primary rays start on a lens of finite aperture instead of at camera_loc: what lies at
+ * focus_distance along the centre ray is sharp, everything else goes soft.  With M = constants->proj_inv, O = camera_loc and
+ * R(sx, sy) the un-normalised vector GenerateCameraRay forms, ((sx*M[0] + sy*M[1]) + M[3], (sx*M[4] + sy*M[5]) + M[7],
+ * (sx*M[8] + sy*M[9]) + M[11]), once per frame on the host in fp32 (normalize: v * (1 / sqrt(dot(v, v))), the ray generators'):
+ *   A = radius * normalize(M[0], M[4], M[8]),  B = radius * normalize(M[1], M[5], M[9]),  s = focus_distance / |(M[3], M[7], M[11])|
+ * so s * R spans the focal plane.  Sample k of pixel (x, y) has the pixel offset (ox, oy) of offsets and the lens offset (lx, ly)
+ * of lens_offsets, in units of the radius; in fp32, one rounding per operation and nothing fused:
+ *   sx, sy, R   as for rr_render_samples
+ *   off    = (lx*A.x + ly*B.x, lx*A.y + ly*B.y, lx*A.z + ly*B.z)
+ *   origin = O + off
+ *   dir    = normalize(s*R.x - off.x, s*R.y - off.y, s*R.z - off.z)
+ * over params' primary interval with RayGen's payload: the rays of rr_host_lens_rays.  The frame is the fold of rr_shade_rays on
+ * those rays by the resolve rule of rr_render_samples.  radius == 0 takes the pinhole's rays as they are, origin O and dir
+ * normalize(R): the frame is rr_render_samples byte for byte.
+ * offsets as for rr_render_samples (NULL: the built-in pattern, n_samples 1, 2, 4, 8 or 16).  lens_offsets: host array of
+ * 2 * n_samples floats, each finite and in [-1, 1]; NULL: rr_host_lens_pattern(n_samples).  lens: not NULL, radius finite and
+ * >= 0, focus_distance finite and > 0; the centre column (M[3], M[7], M[11]) and, with radius > 0, both axis columns must have a
+ * finite non-zero length (RR_ERR_INVALID_ARGUMENT otherwise, before any output memory is looked at).
+ * Blocks of 8 x 8 pixels outside rr_host_lens_screen_rect of the scene are shaded as one Miss per sample on that sample's lens
+ * direction; RR_DISPATCH_DEBUG_NO_CULL traces them, with the same output.  Outputs, resolve, tone mapping, errors and state
+ * exactly as rr_render_samples[_device]: not a dispatch, rr_set_tile_partition is ignored, the _device variant is stream-ordered
+ * and neither synchronises nor allocates. */
+typedef struct rr_lens { float radius; float focus_distance; } rr_lens;
+int  rr_render_lens(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                    const rr_dispatch_params* params, const float* offsets, const float* lens_offsets, uint32_t n_samples,
+                    const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_lens_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                           const rr_dispatch_params* params, const float* offsets, const float* lens_offsets, uint32_t n_samples,
+                           const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */
@@ -561,6 +592,20 @@ uint64_t rr_host_adaptive_workspace_bytes(uint32_t width, uint32_t height);
  * over [tmin, tmax] with flags 0 and instance_mask 0xff.  width, height: 1..32768. */
 int  rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,
                          rr_ray* rays);
+/* The rays of rr_render_lens for one (pixel offset, lens offset) pair, every pixel of a width x height frame, row-major, as
+ * rr_ray records shaped like those of rr_host_camera_rays: ox, oy in [0, 1], lx, ly finite and in [-1, 1], lens as rr_render_lens
+ * takes it (RR_ERR_INVALID_ARGUMENT otherwise).  radius == 0: exactly rr_host_camera_rays. */
+int  rr_host_lens_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float lx, float ly,
+                       const rr_lens* lens, float tmin, float tmax, rr_ray* rays);
+/* The built-in lens offsets of rr_render_lens, 1 <= n_samples <= RR_MAX_SAMPLES: 2 * n_samples floats, point i of a golden-angle
+ * spiral inside the unit disk, r = sqrtf((i + 0.5f) / n), theta = i * 2.3999632f, (r * cosf(theta), r * sinf(theta)). */
+int  rr_host_lens_pattern(uint32_t n_samples, float* lens_offsets);
+/* rr_host_screen_rect for a lens: where the box can be seen from any point of the lens disk -- the union of the rectangles of five
+ * pinhole cameras, the lens centre and the corners +-A +-B of the square round the disk, each at camera_loc + off with the centre
+ * column of proj_inv reduced by off / s.  The whole frame whenever one of them cannot be trusted or constants == NULL; radius == 0
+ * gives the pinhole's rectangle.  A lens rr_render_lens refuses is RR_ERR_INVALID_ARGUMENT. */
+int  rr_host_lens_screen_rect(const float bounds[6], const rr_scene_constants* constants, const rr_lens* lens, uint32_t width,
+                              uint32_t height, uint32_t rect[4]);
 /* Mesh::load, Mesh.cpp:6-37.  Arrays are malloc'ed, release with rr_host_free.  A file that cannot
  * be opened returns RR_ERR_IO (Mesh::load returns false). */
 int  rr_host_mesh_load_obj(const char* filename, rr_vertex** verts, uint32_t* n_verts,

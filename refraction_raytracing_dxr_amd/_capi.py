@@ -62,6 +62,14 @@ class DispatchParams(C.Structure):
                 ("tmin_secondary", C.c_float), ("tmax_secondary", C.c_float), ("flags", C.c_uint32)]
 
 
+class Lens(C.Structure):
+    """rr_lens: the thin lens of render_lens -- aperture radius and distance of the focal plane along the centre ray, world units"""
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def __init__(self, radius=0.0, focus_distance=1.0):
+        super().__init__(float(radius), float(focus_distance))
+
+
 class Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary", C.c_uint64), ("secondary", C.c_uint64), ("hits", C.c_uint64),
                 ("misses", C.c_uint64), ("terminal_hits", C.c_uint64), ("tir", C.c_uint64),
@@ -153,6 +161,10 @@ SYMBOLS = {
     "rr_render_adaptive_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
                                             C.c_uint32, C.c_float, _P, _P, _P, _P, _P, C.c_uint64]),
     "rr_host_adaptive_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "rr_render_lens": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
+                                 C.POINTER(Lens), _P, _P, _P]),
+    "rr_render_lens_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
+                                        C.POINTER(Lens), _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -170,6 +182,11 @@ SYMBOLS = {
     "rr_host_camera_orbit": (C.c_int, [C.c_float] * 5 + [C.POINTER(SceneConstants)]),
     "rr_host_sample_pattern": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
     "rr_host_camera_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "rr_host_lens_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Lens),
+                                    C.c_float, C.c_float, _P]),
+    "rr_host_lens_pattern": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "rr_host_lens_screen_rect": (C.c_int, [C.POINTER(C.c_float), C.POINTER(SceneConstants), C.POINTER(Lens), C.c_uint32, C.c_uint32,
+                                           C.POINTER(C.c_uint32)]),
     "rr_host_screen_rect": (C.c_int, [C.POINTER(C.c_float), C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rr_host_mesh_tile_home": (C.c_int, [C.POINTER(MeshPartition), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rr_host_mesh_tiles_of_rank": (C.c_uint32, [C.POINTER(MeshPartition), C.c_uint32]),

@@ -89,6 +89,21 @@ int drawFrameSamples(int spp)
     return RR_OK;
 }
 
+int drawFrameLens(int spp, float radius, float focus_distance)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameLens: spp must be 1, 2, 4, 8 or 16");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    const rr_lens lens = { radius, focus_distance };
+    if ((rc = rr_render_lens(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, nullptr, (uint32_t)spp, &lens,
+                             nullptr, g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_lens");
+    return RR_OK;
+}
+
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined)
 {
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");

@@ -30,6 +30,8 @@ int drawFrame();                          // RefractionDemo.cpp:557-612; returns
 // drawFrame with spp primary rays per pixel (rr_render_samples, the built-in pattern of 1, 2, 4, 8 or 16 samples): the orbit
 // advances as in drawFrame and the resolved frame lands in backBuffer()
 int drawFrameSamples(int spp);
+// drawFrameSamples through a thin lens (rr_render_lens, the built-in lens offsets): aperture radius and focus distance in world units
+int drawFrameLens(int spp, float radius, float focus_distance);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

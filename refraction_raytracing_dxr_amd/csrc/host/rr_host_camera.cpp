@@ -1,5 +1,5 @@
 // rr_host_camera.cpp -- the per-frame camera constants of RefractionDemo::drawFrame
-// (RefractionDemo.cpp:559-566), host side, no device.
+// (RefractionDemo.cpp:559-566), host side, no device; and the primary rays of the supersampled and thin-lens frames.
 //
 // The reference computes them with DirectXMath (Windows SDK header, not in its tree):
 //   proj  = XMMatrixPerspectiveFovLH(52/180*3.1415, 1.333, 1, 125)          :559
@@ -9,6 +9,7 @@
 //   proj_inv = XMMatrixInverse(proj * world * view)                        :563-565
 // DirectXMath's published algorithms are restated here in fp32 with its row-vector convention.
 #include "../../../include/rrdxr.h"
+#include "rr_host_lens.h"
 
 #include <cmath>
 #include <cstring>
@@ -166,6 +167,80 @@ extern "C" int rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, 
             rr_ray& r = rays[(size_t)y * width + x];
             std::memset(&r, 0, sizeof r);
             r.origin[0] = c->camera_loc[0]; r.origin[1] = c->camera_loc[1]; r.origin[2] = c->camera_loc[2];
+            r.tmin = tmin;
+            r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
+            r.tmax = tmax;
+            r.instance_mask = 0xffu;
+        }
+    }
+    return RR_OK;
+}
+
+// ---- the thin lens of rr_render_lens ----
+namespace {
+float length(Vec3 a) { return std::sqrt(dot(a, a)); }
+bool usable(float len) { return std::isfinite(len) && len > 0.0f; }
+bool in_unit(float v) { return v >= -1.0f && v <= 1.0f; }       // (NaN fails both comparisons)
+} // namespace
+
+int rr::lens_setup(const rr_scene_constants* c, const rr_lens* lens, rr::LensDev* out)
+{
+    if (!c || !lens || !out) return RR_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(lens->radius) || !(lens->radius >= 0.0f)) return RR_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(lens->focus_distance) || !(lens->focus_distance > 0.0f)) return RR_ERR_INVALID_ARGUMENT;
+    const float* M = c->proj_inv;
+    const Vec3 u = { M[0], M[4], M[8] }, v = { M[1], M[5], M[9] }, w = { M[3], M[7], M[11] };
+    const float lw = length(w);
+    if (!usable(lw)) return RR_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof *out);
+    out->s = lens->focus_distance / lw;
+    if (!usable(out->s)) return RR_ERR_INVALID_ARGUMENT;
+    out->pinhole = lens->radius == 0.0f ? 1u : 0u;
+    if (out->pinhole) return RR_OK;
+    if (!usable(length(u)) || !usable(length(v))) return RR_ERR_INVALID_ARGUMENT;
+    const Vec3 a = normalized(u), b = normalized(v);
+    out->A[0] = lens->radius * a.x; out->A[1] = lens->radius * a.y; out->A[2] = lens->radius * a.z;
+    out->B[0] = lens->radius * b.x; out->B[1] = lens->radius * b.y; out->B[2] = lens->radius * b.z;
+    for (int i = 0; i < 3; ++i) if (!std::isfinite(out->A[i]) || !std::isfinite(out->B[i])) return RR_ERR_INVALID_ARGUMENT;
+    return RR_OK;
+}
+
+// point i of a golden-angle spiral inside the unit disk
+extern "C" int rr_host_lens_pattern(uint32_t n_samples, float* lens_offsets)
+{
+    if (n_samples == 0 || n_samples > RR_MAX_SAMPLES || !lens_offsets) return RR_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n_samples; ++i) {
+        const float r = sqrtf(((float)i + 0.5f) / (float)n_samples), theta = (float)i * 2.3999632f;
+        lens_offsets[2 * i] = r * cosf(theta);
+        lens_offsets[2 * i + 1] = r * sinf(theta);
+    }
+    return RR_OK;
+}
+
+// lens_ray of rr_render_common.h for every pixel of a frame, operation by operation: the ray from the lens point
+// camera_loc + lx * A + ly * B through the point s * R of the focal plane, R being GenerateCameraRay's un-normalised vector
+extern "C" int rr_host_lens_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float lx, float ly,
+                                 const rr_lens* lens, float tmin, float tmax, rr_ray* rays)
+{
+    if (!c || !rays || width == 0 || height == 0 || width > 32768u || height > 32768u) return RR_ERR_INVALID_ARGUMENT;
+    if (!(ox >= 0.0f && ox <= 1.0f && oy >= 0.0f && oy <= 1.0f) || !in_unit(lx) || !in_unit(ly)) return RR_ERR_INVALID_ARGUMENT;
+    rr::LensDev L;
+    if (int r = rr::lens_setup(c, lens, &L)) return r;
+    if (L.pinhole) return rr_host_camera_rays(c, width, height, ox, oy, tmin, tmax, rays);
+    const float* M = c->proj_inv;
+    const Vec3 off = { lx * L.A[0] + ly * L.B[0], lx * L.A[1] + ly * L.B[1], lx * L.A[2] + ly * L.B[2] };
+    const Vec3 org = { c->camera_loc[0] + off.x, c->camera_loc[1] + off.y, c->camera_loc[2] + off.z };
+    for (uint32_t y = 0; y < height; ++y) {
+        const float py = (float)y + oy;
+        const float sy = -(py / (float)height * 2.0f - 1.0f);
+        for (uint32_t x = 0; x < width; ++x) {
+            const float px = (float)x + ox;
+            const float sx = px / (float)width * 2.0f - 1.0f;
+            const Vec3 R = { (sx * M[0] + sy * M[1]) + M[3], (sx * M[4] + sy * M[5]) + M[7], (sx * M[8] + sy * M[9]) + M[11] };
+            const Vec3 d = normalized(Vec3{ L.s * R.x - off.x, L.s * R.y - off.y, L.s * R.z - off.z });
+            rr_ray& r = rays[(size_t)y * width + x];
+            std::memset(&r, 0, sizeof r);
+            r.origin[0] = org.x; r.origin[1] = org.y; r.origin[2] = org.z;
             r.tmin = tmin;
             r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
             r.tmax = tmax;

@@ -1,6 +1,7 @@
 // rr_host_partition.cpp -- pure host geometry of a dispatch: where on the screen the scene can be seen at all, and how the
 // 32x32 tiles of a frame are dealt to the ranks of a multi-GPU run.  No device, no context: the same answers on every rank.
 #include "../../../include/rrdxr.h"
+#include "rr_host_lens.h"
 
 #include <algorithm>
 #include <cmath>
@@ -106,6 +107,34 @@ int rr_host_screen_rect(const float bounds[6], const rr_scene_constants* constan
 {
     if (!bounds || !rect || width == 0 || height == 0) return RR_ERR_INVALID_ARGUMENT;
     screen_rect(bounds, constants, n, width, height, rect);
+    return RR_OK;
+}
+
+// A lens point camera_loc + off sees pixel (sx, sy) along s * (R(sx, sy) - off / s): a pinhole at that point whose centre column
+// (M3, M7, M11) is reduced by off / s.  Both that camera and the point of the focal plane a scene point projects to are affine in
+// off, and the lens disk lies inside the square with the corners +-A +-B: the union of the centre's and the four corners'
+// rectangles holds what any point of the disk sees.
+int rr_host_lens_screen_rect(const float bounds[6], const rr_scene_constants* constants, const rr_lens* lens, uint32_t width,
+                             uint32_t height, uint32_t rect[4])
+{
+    if (!bounds || !rect || width == 0 || height == 0) return RR_ERR_INVALID_ARGUMENT;
+    if (!constants) { screen_rect(bounds, nullptr, 0, width, height, rect); return RR_OK; }       // the whole frame
+    rr::LensDev L;
+    if (int r = rr::lens_setup(constants, lens, &L)) return r;
+    rr_scene_constants cams[5];
+    cams[0] = *constants;
+    uint32_t n = 1;
+    for (int k = 0; k < 4 && !L.pinhole; ++k, ++n) {
+        const float lx = (k & 1) ? 1.0f : -1.0f, ly = (k & 2) ? 1.0f : -1.0f;
+        rr_scene_constants& q = cams[n];
+        q = *constants;
+        for (int i = 0; i < 3; ++i) {
+            const float off = lx * L.A[i] + ly * L.B[i];
+            q.camera_loc[i] = constants->camera_loc[i] + off;
+            q.proj_inv[4 * i + 3] = constants->proj_inv[4 * i + 3] - off / L.s;
+        }
+    }
+    screen_rect(bounds, cams, n, width, height, rect);
     return RR_OK;
 }
 

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -119,9 +119,9 @@ int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, Sample
 }
 
 // what the launch of a checked supersampled or adaptive frame takes: the scene, the frame's shading arguments with its screen
-// rectangle, the camera and the scene's kernel variant
+// rectangle (lens: the rectangle of its whole disk, rr_host_lens_screen_rect), the camera and the scene's kernel variant
 struct FrameArgs { SceneDev sc; DispatchDev a; CamDev cam; FusedVariant v; };
-FrameArgs frame_args(rr_context* ctx, const SamplesReq& q)
+FrameArgs frame_args(rr_context* ctx, const SamplesReq& q, const rr_lens* lens = nullptr)
 {
     const rr_dispatch_params p = params_or_default(q.params);
     FrameArgs f;
@@ -130,7 +130,9 @@ FrameArgs frame_args(rr_context* ctx, const SamplesReq& q)
     f.a.W = q.width; f.a.H = q.height;
     f.a.tmin_p = p.tmin_primary; f.a.tmax_p = p.tmax_primary;
     uint32_t hr[4];
-    (void)rr_host_screen_rect(ctx->scene_bounds, (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants, 1, q.width, q.height, hr);
+    const rr_scene_constants* const seen = (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants;
+    if (lens) (void)rr_host_lens_screen_rect(ctx->scene_bounds, seen, lens, q.width, q.height, hr);
+    else (void)rr_host_screen_rect(ctx->scene_bounds, seen, 1, q.width, q.height, hr);
     f.a.hx0 = hr[0]; f.a.hy0 = hr[1]; f.a.hx1 = hr[2]; f.a.hy1 = hr[3];
     memcpy(f.cam.M, q.constants->proj_inv, sizeof f.cam.M);
     memcpy(f.cam.cam, q.constants->camera_loc, sizeof f.cam.cam);
@@ -170,6 +172,42 @@ int adaptive_impl(rr_context* ctx, const AdaptiveReq& q, const SampleOffsets& of
     const FrameArgs f = frame_args(ctx, q.s);
     if (hipError_t e = launch_render_adaptive(f.sc, f.a, f.cam, off, q.n_base, q.s.n_samples, q.threshold, ws, out.f32, out.rgba8, out.n_rays, n_taken,
                                               f.v.stack, f.v.pend, f.v.stack16, (uint32_t)ctx->dbg_refine_groups, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
+    return RR_OK;
+}
+
+// a thin-lens frame: a supersampled frame with a lens and one lens offset per sample
+struct LensReq { SamplesReq s; const float* lens_offsets; const rr_lens* lens; };
+
+// what both variants of rr_render_lens refuse before they look at their outputs' memory or allocate anything: what
+// rr_render_samples refuses, then the lens and its offsets; fills both tables and the lens
+int check_lens(rr_context* ctx, const LensReq& q, bool have_colour, SampleOffsets& off, SampleOffsets& loff, LensDev& lens)
+{
+    if (int r = check_samples(ctx, q.s, have_colour, off)) return r;
+    const std::string w(q.s.who);
+    if (!q.lens) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null lens").c_str());
+    if (lens_setup(q.s.constants, q.lens, &lens))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need a finite radius >= 0, a finite focus_distance > 0 and proj_inv columns of finite non-zero length").c_str());
+    memset(&loff, 0, sizeof loff);
+    if (!q.lens_offsets) {
+        (void)rr_host_lens_pattern(q.s.n_samples, loff.v);      // (1 <= n_samples <= 64: check_samples)
+        return RR_OK;
+    }
+    for (uint32_t i = 0; i < 2 * q.s.n_samples; ++i) {
+        if (!(q.lens_offsets[i] >= -1.0f && q.lens_offsets[i] <= 1.0f))     // (NaN fails both comparisons)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": lens offsets must lie in [-1, 1]").c_str());
+        loff.v[i] = q.lens_offsets[i];
+    }
+    return RR_OK;
+}
+
+// launches a checked thin-lens frame: out holds device pointers.  As samples_impl: nothing of the context but its error text,
+// nothing allocated or copied.
+int lens_impl(rr_context* ctx, const LensReq& q, const SampleOffsets& off, const SampleOffsets& loff, const LensDev& lens, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q.s, q.lens);
+    if (hipError_t e = launch_render_lens(f.sc, f.a, f.cam, off, loff, lens, q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend,
+                                          f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -354,6 +392,36 @@ int rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height, 
                     "rr_render_adaptive_device: need a 16-byte aligned workspace of at least rr_host_adaptive_workspace_bytes(width, height) bytes");
     return adaptive_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) },
                          static_cast<uint32_t*>(d_n_taken), AdaptiveWorkspace(d_workspace, width, height));
+}
+
+int rr_render_lens(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                   const float* offsets, const float* lens_offsets, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8,
+                   uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const LensReq q = { { "rr_render_lens", width, height, constants, params, offsets, n_samples }, lens_offsets, lens };
+    SampleOffsets off, loff;
+    LensDev ld;
+    if (int r = check_lens(ctx, q, rgba32f || rgba8, off, loff, ld)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = lens_impl(ctx, q, off, loff, ld, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_lens_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                          const float* offsets, const float* lens_offsets, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
+                          void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const LensReq q = { { "rr_render_lens_device", width, height, constants, params, offsets, n_samples }, lens_offsets, lens };
+    SampleOffsets off, loff;
+    LensDev ld;
+    if (int r = check_lens(ctx, q, d_rgba32f || d_rgba8, off, loff, ld)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_lens_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return lens_impl(ctx, q, off, loff, ld, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rr_types.h"
+#include "host/rr_host_lens.h"
 
 namespace rr {
 
@@ -55,6 +56,13 @@ hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_
 struct SampleOffsets { static constexpr uint32_t MAX = 64; float v[2 * MAX]; };     // x0, y0, x1, y1, ...
 hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_samples,
                                  float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+// ---- rr_render_lens.hip: thin-lens frames (rr_render_lens[_device]): launch_render_samples with every sample's ray starting on
+// the lens (LensDev, host/rr_host_lens.h) at lens offset loff[s], in units of the radius, towards the focal-plane point of pixel
+// offset off[s]; lens.pinhole: the rays of launch_render_samples.  a.hx0..hy1: the scene's rectangle for the lens
+// (rr_host_lens_screen_rect).  Both tables and the lens travel as kernel arguments: 1056 bytes
+hipError_t launch_render_lens(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
+                              const LensDev& lens, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
+                              bool stack16, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

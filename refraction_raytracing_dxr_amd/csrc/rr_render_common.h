@@ -1,5 +1,5 @@
 // rr_render_common.h -- device code shared by the render kernels (rr_render_fused.hip, rr_render_paths.hip, rr_render_lds.hip,
-// rr_render_stream.hip, rr_shade_rays.hip, rr_render_samples.hip, rr_render_adaptive.hip): a pixel's ray tree as the
+// rr_render_stream.hip, rr_shade_rays.hip, rr_render_samples.hip, rr_render_adaptive.hip, rr_render_lens.hip): a pixel's ray tree as the
 // lanes walk it (RayGen, ClosestHit / Miss, the parked reflected rays), the frame store, the counters, and the numbering of a dispatch's 8x8 pixel blocks.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -137,6 +137,28 @@ __device__ __forceinline__ RayState sample_ray(const DispatchDev& a, const CamDe
     RayState r;
     r.O = mk3(cam.cam[0], cam.cam[1], cam.cam[2]);
     r.D = camera_ray_dir(cam.M, sx, sy);
+    r.w = 1.0f; r.count = 0; r.outside = true;
+    r.tmin = a.tmin_p; r.tmax = a.tmax_p;
+    return r;
+}
+
+// Sample s of pixel (fx, fy) through a thin lens, for k_render_lens: sample_ray's screen position and un-normalised vector R, then
+// the ray from the lens point cam + loff[s].x * A + loff[s].y * B through the focal-plane point cam + lens.s * R.  One rounding per
+// operation in this order (rr_host_lens_rays repeats it on the host); off and T are dead once the ray exists.
+__device__ __forceinline__ RayState lens_ray(const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
+                                             const LensDev& lens, uint32_t s, float fx, float fy, float fw, float fh)
+{
+    const float px = fx + off.v[2u * s], py = fy + off.v[2u * s + 1u];
+    const float sx = px / fw * 2.0f - 1.0f;
+    const float sy = -(py / fh * 2.0f - 1.0f);
+    const float* M = cam.M;
+    const f3 R = mk3((sx * M[0] + sy * M[1]) + M[3], (sx * M[4] + sy * M[5]) + M[7], (sx * M[8] + sy * M[9]) + M[11]);
+    const float lx = loff.v[2u * s], ly = loff.v[2u * s + 1u];
+    const f3 o = mk3(lx * lens.A[0] + ly * lens.B[0], lx * lens.A[1] + ly * lens.B[1], lx * lens.A[2] + ly * lens.B[2]);
+    const f3 T = mk3(lens.s * R.x - o.x, lens.s * R.y - o.y, lens.s * R.z - o.z);
+    RayState r;
+    r.O = mk3(cam.cam[0] + o.x, cam.cam[1] + o.y, cam.cam[2] + o.z);
+    r.D = normalize3(T);
     r.w = 1.0f; r.count = 0; r.outside = true;
     r.tmin = a.tmin_p; r.tmax = a.tmax_p;
     return r;

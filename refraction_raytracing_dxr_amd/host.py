@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, HIT_DTYPE, INSTANCE_DTYPE, NODE_DTYPE, RAY_DTYPE,
-                    TRI_DTYPE, VERTEX_DTYPE, DispatchParams, RRError, SceneConstants, Stats)
+                    TRI_DTYPE, VERTEX_DTYPE, DispatchParams, Lens, RRError, SceneConstants, Stats)
 
 FOV_Y = float(np.float32(52.0 / 180.0 * 3.1415))     # RefractionDemo.cpp:559
 ASPECT = float(np.float32(1.333))
@@ -90,6 +90,41 @@ def camera_rays(camera, w, h, ox=0.5, oy=0.5, tmin=1e-4, tmax=100.0):
     if rc:
         raise RRError(rc, "rr_host_camera_rays")
     return rays
+
+
+def lens_pattern(n):
+    """-> float32 [n, 2]: the built-in lens offsets of render_lens for n = 1..64 samples, a golden-angle spiral inside the unit disk,
+    in units of the lens radius"""
+    n = int(n)
+    out = np.zeros((max(n, 1), 2), np.float32)
+    rc = _capi.lib().rr_host_lens_pattern(n if n >= 0 else 0, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise RRError(rc, "rr_host_lens_pattern(%d)" % n)
+    return out
+
+
+def lens_rays(camera, w, h, ox, oy, lx, ly, lens, tmin=1e-4, tmax=100.0):
+    """-> RAY_DTYPE [w * h], row-major: what render_lens traces for the sample with sub-pixel position (ox, oy) (pixel units, in
+    [0, 1]) and lens offset (lx, ly) (units of lens.radius, each in [-1, 1]): rays from the lens point through the focal-plane point
+    of every pixel.  lens.radius == 0: camera_rays(camera, w, h, ox, oy, tmin, tmax)."""
+    rays = np.zeros(int(w) * int(h), RAY_DTYPE)
+    rc = _capi.lib().rr_host_lens_rays(C.byref(camera), int(w), int(h), float(ox), float(oy), float(lx), float(ly), C.byref(lens),
+                                       float(np.float32(tmin)), float(np.float32(tmax)), rays.ctypes.data)
+    if rc:
+        raise RRError(rc, "rr_host_lens_rays")
+    return rays
+
+
+def lens_screen_rect(bounds, camera, lens, w, h):
+    """-> (x0, y0, x1, y1): the pixels from which any point of the lens can see the box bounds = (lo xyz, hi xyz), aligned outward to
+    8 with 8 pixels of margin; the whole frame (rounded up to 8) when the projection cannot be trusted or camera is None.
+    render_lens traces the 8x8 blocks that touch it and shades the others as one Miss per sample."""
+    b = (C.c_float * 6)(*[float(v) for v in np.asarray(bounds, np.float32).reshape(6)])
+    r = (C.c_uint32 * 4)()
+    rc = _capi.lib().rr_host_lens_screen_rect(b, C.byref(camera) if camera is not None else None, C.byref(lens), int(w), int(h), r)
+    if rc:
+        raise RRError(rc, "rr_host_lens_screen_rect")
+    return tuple(int(v) for v in r)
 
 
 def make_instances(transforms=None, meshes=None, masks=None, flags=None):
@@ -574,6 +609,33 @@ class Renderer:
             self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples_device")
         else:
             self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples")
+        return _result(outs)
+
+    def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):
+        """Thin-lens frame (rr_render_lens): render_samples with a lens of finite aperture -- sample s of a pixel starts at lens
+        offset s on a disk of lens.radius round the camera and passes through the point its sub-pixel position sees at
+        lens.focus_distance, so what lies in that plane is sharp and the rest is averaged over the aperture.  Bit for bit the fold of
+        shade_rays on lens_rays(camera, width, height, *offset_s, *lens_offset_s, lens) by render_samples' resolve rule; with
+        lens.radius == 0, render_samples itself.  lens: Lens(radius, focus_distance).  samples: as for render_samples.  lens_samples:
+        None for the built-in lens_pattern(S), or an [S, 2] float32 array of offsets in [-1, 1] (units of the radius), S being the
+        number of samples.  The other arguments, the outputs and device=True as render_samples; not a dispatch either."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "render_lens: samples must be an int or an [S, 2] array")
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_lens: negative size")
+        loffp = None
+        if lens_samples is not None:
+            loff = np.ascontiguousarray(lens_samples, np.float32)
+            if loff.shape != (n, 2) or n == 0:
+                raise ValueError("render_lens: lens_samples must be an [S, 2] array with one row per sample")
+            loffp = loff.ctypes.data_as(C.c_void_p)
+        lp = C.byref(lens) if lens is not None else None
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_lens_device(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens_device")
+        else:
+            self._ck(self._L.rr_render_lens(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens")
         return _result(outs)
 
     def render_adaptive(self, width, height, camera, samples=(4, 16), threshold=ADAPTIVE_THRESHOLD, params=None, rgba8=False, ray_counts=False,

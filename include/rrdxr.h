@@ -533,6 +533,36 @@ int  rr_render_lens_device(rr_context* ctx, uint32_t width, uint32_t height, con
                            const rr_dispatch_params* params, const float* offsets, const float* lens_offsets, uint32_t n_samples,
                            const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
+/* ---- spectral frames: dispersion with an index of refraction per sample (present from ABI version 3) -----------------------------
+ * A supersampled frame in which every sample has its own index of refraction and its own weight per colour channel: distribution
+ * ray tracing over the wavelength, which puts colour fringes on refracting glass.  Sample k of pixel (x, y) is sample k of
+ * rr_render_samples, the ray of rr_host_camera_rays with offset k, shaded by the ray tree of rr_shade_rays with params->ior
+ * replaced by bands[k].ior; the reciprocal the shader refracts with on the way in is 1.0f / ior in fp32, the expression every
+ * launcher forms it with.  With c_k that colour, channel ch of the pixel resolves in fp32, one rounding per operation and nothing
+ * fused:
+ *   p_k = bands[k].weight[ch] * c_k[ch]
+ *   sum = p_0, then sum = sum + p_k in sample order
+ *   out = sum / (float)n_samples
+ * n_rays[i] is the number of TraceRay calls of all the trees of pixel i.  bands == NULL: every band is { params->ior, 1, 1, 1 };
+ * such a frame, and any table with those values, is rr_render_samples byte for byte.  params->ior is validated as usual even when
+ * bands replaces it.
+ * offsets as for rr_render_samples (NULL: the built-in pattern, n_samples 1, 2, 4, 8 or 16).  bands: host array of n_samples
+ * records or NULL.  1 <= n_samples <= RR_MAX_SAMPLES; every band's ior finite and > 0; every weight finite -- negative weights
+ * are allowed (tables derived from XYZ matching functions have them) (RR_ERR_INVALID_ARGUMENT otherwise, before any output memory
+ * is looked at).
+ * Blocks of 8 x 8 pixels outside rr_host_screen_rect of the scene are shaded as one Miss per sample, which does not depend on the
+ * index of refraction, and weighted and resolved by the same rule; RR_DISPATCH_DEBUG_NO_CULL traces them, with the same output.
+ * The pinhole's rectangle holds because the primary rays are rr_render_samples'.  Outputs, tone mapping, alignment rules, errors and
+ * state exactly as rr_render_samples[_device]: not a dispatch, rr_set_tile_partition is ignored, the _device variant is
+ * stream-ordered and neither synchronises nor allocates (the tables travel as kernel arguments). */
+typedef struct rr_band { float ior; float weight[3]; } rr_band;      /* 16 bytes */
+int  rr_render_spectral(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                        const rr_dispatch_params* params, const float* offsets, const rr_band* bands, uint32_t n_samples,
+                        float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_spectral_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                               const rr_dispatch_params* params, const float* offsets, const rr_band* bands, uint32_t n_samples,
+                               void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */
@@ -592,6 +622,16 @@ uint64_t rr_host_adaptive_workspace_bytes(uint32_t width, uint32_t height);
  * over [tmin, tmax] with flags 0 and instance_mask 0xff.  width, height: 1..32768. */
 int  rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,
                          rr_ray* rays);
+/* A band table for rr_render_spectral, 1 <= n <= RR_MAX_SAMPLES records.  n == 1: { ior_d, 1, 1, 1 }.  Otherwise band i has the
+ * wavelength l_i = 400 + (i + 0.5) / n * 300 nm and, by Cauchy's law, ior = A + B / l^2 with
+ *   B = (ior_d - 1) / (abbe * (1 / 486.1^2 - 1 / 656.3^2)),  A = ior_d - B / 587.6^2
+ * (ior_d at the d line, abbe the Abbe number over the F and C lines), computed in double and rounded once.  The weights are three
+ * tent functions of half-width 100 nm centred at 650 nm (R), 550 nm (G) and 450 nm (B), t_c(l) = max(0, 1 - |l - centre_c| / 100),
+ * each channel normalised in double so that its n weights sum to n, weight = (float)(t_c(l_i) * n / sum_i t_c(l_i)): a white
+ * environment stays white.  A stated convention, not colorimetry: bring a table of your own for that.  ior_d finite and > 0; abbe
+ * > 0, +inf allowed (every ior is ior_d then); a table with an ior that is not finite and > 0 (abbe too small) is not handed out
+ * (RR_ERR_INVALID_ARGUMENT, as n == 0, n > RR_MAX_SAMPLES or bands == NULL). */
+int  rr_host_spectral_bands(uint32_t n, float ior_d, float abbe, rr_band* bands);
 /* The rays of rr_render_lens for one (pixel offset, lens offset) pair, every pixel of a width x height frame, row-major, as
  * rr_ray records shaped like those of rr_host_camera_rays: ox, oy in [0, 1], lx, ly finite and in [-1, 1], lens as rr_render_lens
  * takes it (RR_ERR_INVALID_ARGUMENT otherwise).  radius == 0: exactly rr_host_camera_rays. */

@@ -50,6 +50,9 @@ QNODE_DTYPE = np.dtype([("lox", "<f2", 2), ("loy", "<f2", 2), ("loz", "<f2", 2),
                         ("hiy", "<f2", 2), ("hiz", "<f2", 2), ("c", "<i4", 2)])
 assert QNODE_DTYPE.itemsize == 32
 assert HIT_DTYPE.itemsize == 24 and NODE_DTYPE.itemsize == 64 and TRI_DTYPE.itemsize == 48
+# rr_band: one sample's index of refraction and its colour's weight per channel (render_spectral)
+BAND_DTYPE = np.dtype([("ior", "<f4"), ("weight", "<f4", 3)])
+assert BAND_DTYPE.itemsize == 16
 
 
 class SceneConstants(C.Structure):
@@ -165,6 +168,10 @@ SYMBOLS = {
                                  C.POINTER(Lens), _P, _P, _P]),
     "rr_render_lens_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
                                         C.POINTER(Lens), _P, _P, _P]),
+    "rr_render_spectral": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
+                                     _P, _P, _P]),
+    "rr_render_spectral_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
+                                            _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -181,6 +188,7 @@ SYMBOLS = {
     "rr_default_dispatch_params": (None, [C.POINTER(DispatchParams)]),
     "rr_host_camera_orbit": (C.c_int, [C.c_float] * 5 + [C.POINTER(SceneConstants)]),
     "rr_host_sample_pattern": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "rr_host_spectral_bands": (C.c_int, [C.c_uint32, C.c_float, C.c_float, _P]),
     "rr_host_camera_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "rr_host_lens_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Lens),
                                     C.c_float, C.c_float, _P]),

@@ -104,6 +104,31 @@ int drawFrameLens(int spp, float radius, float focus_distance)
     return RR_OK;
 }
 
+int drawFrameSpectral(int spp, int n_bands, float abbe)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0 || n_bands <= 0 || spp * (long long)n_bands > RR_MAX_SAMPLES)
+        return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameSpectral: spp must be 1, 2, 4, 8 or 16 and spp * bands at most 64");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    float pos[2 * RR_MAX_SAMPLES], off[2 * RR_MAX_SAMPLES];
+    rr_band one[RR_MAX_SAMPLES], bands[RR_MAX_SAMPLES];
+    if ((rc = rr_host_sample_pattern((uint32_t)spp, pos)) != RR_OK) return fail(rc, "rr_host_sample_pattern");
+    if ((rc = rr_host_spectral_bands((uint32_t)n_bands, g_opt.dispatch.ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
+    g_angle += g_opt.angle_step;
+    for (int a = 0; a < spp; ++a)
+        for (int b = 0; b < n_bands; ++b) {
+            const int k = a * n_bands + b;
+            off[2 * k] = pos[2 * a]; off[2 * k + 1] = pos[2 * a + 1];
+            bands[k] = one[b];
+        }
+    if ((rc = rr_render_spectral(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, off, bands, (uint32_t)(spp * n_bands),
+                                 nullptr, g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_spectral");
+    return RR_OK;
+}
+
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined)
 {
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");

@@ -32,6 +32,9 @@ int drawFrame();                          // RefractionDemo.cpp:557-612; returns
 int drawFrameSamples(int spp);
 // drawFrameSamples through a thin lens (rr_render_lens, the built-in lens offsets): aperture radius and focus distance in world units
 int drawFrameLens(int spp, float radius, float focus_distance);
+// drawFrameSamples with dispersion (rr_render_spectral): the spp built-in positions crossed with the n_bands bands of
+// rr_host_spectral_bands(n_bands, the dispatch's ior, abbe), sample a * n_bands + b being position a in band b; spp * n_bands <= 64
+int drawFrameSpectral(int spp, int n_bands, float abbe);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

@@ -149,6 +149,32 @@ extern "C" int rr_host_sample_pattern(uint32_t n_samples, float* offsets)
     return RR_OK;
 }
 
+// The built-in band table of rr_render_spectral: n bands at the midpoints of n equal slices of 400..700 nm, Cauchy's law through
+// ior_d at the d line (587.6 nm) with the Abbe number over the F (486.1) and C (656.3) lines, and three tent functions of
+// half-width 100 nm round 650, 550 and 450 nm as channel weights, each normalised to sum to n.  All in double, rounded once.
+extern "C" int rr_host_spectral_bands(uint32_t n, float ior_d, float abbe, rr_band* bands)
+{
+    if (n == 0 || n > RR_MAX_SAMPLES || !bands) return RR_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(ior_d) || !(ior_d > 0.0f) || !(abbe > 0.0f)) return RR_ERR_INVALID_ARGUMENT;      // (NaN fails the comparisons; abbe may be +inf)
+    if (n == 1) { bands[0] = rr_band{ ior_d, { 1.0f, 1.0f, 1.0f } }; return RR_OK; }
+    const double B = ((double)ior_d - 1.0) / ((double)abbe * (1.0 / (486.1 * 486.1) - 1.0 / (656.3 * 656.3)));
+    const double A = (double)ior_d - B / (587.6 * 587.6);
+    static const double centre[3] = { 650.0, 550.0, 450.0 };
+    double tent[RR_MAX_SAMPLES][3], total[3] = { 0.0, 0.0, 0.0 };
+    for (uint32_t i = 0; i < n; ++i) {
+        const double l = 400.0 + ((double)i + 0.5) / (double)n * 300.0;
+        bands[i].ior = (float)(A + B / (l * l));
+        if (!std::isfinite(bands[i].ior) || !(bands[i].ior > 0.0f)) return RR_ERR_INVALID_ARGUMENT;     // (an Abbe number too small for ior_d)
+        for (int c = 0; c < 3; ++c) {
+            tent[i][c] = std::fmax(0.0, 1.0 - std::fabs(l - centre[c]) / 100.0);
+            total[c] += tent[i][c];
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c) bands[i].weight[c] = (float)(tent[i][c] * (double)n / total[c]);
+    return RR_OK;
+}
+
 // GenerateCameraRay (RayTracing.hlsl:27-40) for every pixel of a frame, with the literal 0.5 replaced by (ox, oy): the
 // arithmetic of k_render_samples' sample ray (screen_coord of rr_frame.hip and camera_ray_dir of rr_device.h), operation by operation
 extern "C" int rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t height, float ox, float oy, float tmin, float tmax,

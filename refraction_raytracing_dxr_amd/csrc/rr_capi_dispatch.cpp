@@ -211,7 +211,7 @@ DispatchDev make_dispatch(const rr_context* ctx, const DispatchRequest& req, con
     a.compact_out = o.compact ? (o.rgb8 ? 2u : 1u) : 0u;
     a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
     a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
-    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
+    a.ior = p.ior; a.inv_ior = inv_ior_of(p.ior);
     a.tmin_p = p.tmin_primary; a.tmax_p = p.tmax_primary; a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
     a.out_rgba8 = req.ext_tiles ? req.ext_tiles : ctx->d_rgba8.get() + o.out_base;
     a.out_f32 = o.want_f32 ? ctx->d_f32.get() + o.out_base : nullptr;

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -37,7 +37,7 @@ DispatchDev shading_args(const rr_dispatch_params& p)
     memset(&a, 0, sizeof a);
     a.tonemap = (p.flags & RR_DISPATCH_TONEMAP_REINHARD) ? 1u : 0u;
     a.max_refract = p.max_refract; a.max_reflect = p.max_reflect;
-    a.ior = p.ior; a.inv_ior = 1.0f / p.ior;
+    a.ior = p.ior; a.inv_ior = inv_ior_of(p.ior);
     a.tmin_s = p.tmin_secondary; a.tmax_s = p.tmax_secondary;
     return a;
 }
@@ -208,6 +208,41 @@ int lens_impl(rr_context* ctx, const LensReq& q, const SampleOffsets& off, const
     const FrameArgs f = frame_args(ctx, q.s, q.lens);
     if (hipError_t e = launch_render_lens(f.sc, f.a, f.cam, off, loff, lens, q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend,
                                           f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
+    return RR_OK;
+}
+
+// a spectral frame: a supersampled frame with one band (index of refraction, channel weights) per sample
+struct SpectralReq { SamplesReq s; const rr_band* bands; };
+
+// what both variants of rr_render_spectral refuse before they look at their outputs' memory or allocate anything: what
+// rr_render_samples refuses (params->ior included, although the bands replace it), then the bands; fills both tables.
+// bands == NULL: every row is { params->ior, 1, 1, 1 }, the frame of rr_render_samples
+int check_spectral(rr_context* ctx, const SpectralReq& q, bool have_colour, SampleOffsets& off, BandTable& bands)
+{
+    if (int r = check_samples(ctx, q.s, have_colour, off)) return r;
+    const std::string w(q.s.who);
+    const float ior = params_or_default(q.s.params).ior;
+    memset(&bands, 0, sizeof bands);
+    for (uint32_t k = 0; k < q.s.n_samples; ++k) {              // (1 <= n_samples <= 64: check_samples)
+        const rr_band b = q.bands ? q.bands[k] : rr_band{ ior, { 1.0f, 1.0f, 1.0f } };
+        if (!std::isfinite(b.ior) || !(b.ior > 0.0f)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": every band's ior must be finite and > 0").c_str());
+        for (int ch = 0; ch < 3; ++ch) {
+            if (!std::isfinite(b.weight[ch])) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": every band's weights must be finite").c_str());
+            bands.weight[k][ch] = b.weight[ch];
+        }
+        bands.ior[k] = b.ior; bands.inv_ior[k] = inv_ior_of(b.ior);
+    }
+    return RR_OK;
+}
+
+// launches a checked spectral frame: out holds device pointers.  As samples_impl: nothing of the context but its error text,
+// nothing allocated or copied.
+int spectral_impl(rr_context* ctx, const SpectralReq& q, const SampleOffsets& off, const BandTable& bands, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q.s);
+    if (hipError_t e = launch_render_spectral(f.sc, f.a, f.cam, off, bands, q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend,
+                                              f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -422,6 +457,34 @@ int rr_render_lens_device(rr_context* ctx, uint32_t width, uint32_t height, cons
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_lens_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return lens_impl(ctx, q, off, loff, ld, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_spectral(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                       const float* offsets, const rr_band* bands, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const SpectralReq q = { { "rr_render_spectral", width, height, constants, params, offsets, n_samples }, bands };
+    SampleOffsets off;
+    BandTable bt;
+    if (int r = check_spectral(ctx, q, rgba32f || rgba8, off, bt)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = spectral_impl(ctx, q, off, bt, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_spectral_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                              const float* offsets, const rr_band* bands, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    const SpectralReq q = { { "rr_render_spectral_device", width, height, constants, params, offsets, n_samples }, bands };
+    SampleOffsets off;
+    BandTable bt;
+    if (int r = check_spectral(ctx, q, d_rgba32f || d_rgba8, off, bt)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_spectral_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return spectral_impl(ctx, q, off, bt, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -63,6 +63,14 @@ hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const
 hipError_t launch_render_lens(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
                               const LensDev& lens, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
                               bool stack16, hipStream_t s);
+// ---- rr_render_spectral.hip: spectral frames (rr_render_spectral[_device]): launch_render_samples with sample k shaded with the
+// index of refraction of band k instead of a.ior / a.inv_ior, and its colour weighted per channel before the resolve's sum:
+// sum = w_0 * c_0, then sum + w_k * c_k in sample order, / n_samples.  inv_ior[k] = inv_ior_of(ior[k]) (rr_types.h), filled by the
+// host.  The band table travels as a kernel argument beside the offsets: 1280 bytes
+struct BandTable { static constexpr uint32_t MAX = SampleOffsets::MAX; float ior[MAX]; float inv_ior[MAX]; float weight[MAX][3]; };
+hipError_t launch_render_spectral(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const BandTable& bands,
+                                  uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
+                                  hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

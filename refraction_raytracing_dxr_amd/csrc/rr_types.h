@@ -140,6 +140,9 @@ struct DispatchDev {
     uint32_t* error_flag;
     unsigned long long* diag;       // diagnostic builds only: 4 x u64 per wave {start, cycles, rays(max lane), loop trips}
 };
+// DispatchDev::inv_ior for an index of refraction, on the host in fp32: the one expression every launcher uses (the dispatches, the
+// radiance queries and frames, and per band the spectral frames), so that the same ior refracts alike everywhere
+inline float inv_ior_of(float ior) { return 1.0f / ior; }
 
 // k_render_lds (persistent workgroups, BLAS nodes in LDS): the work queues of one launch.
 // Work is handed out in two phases, a ticket at a time; the wave that draws a ticket shares its blocks with its workgroup

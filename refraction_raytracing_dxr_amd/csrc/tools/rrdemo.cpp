@@ -6,6 +6,7 @@
 //          [--spp N]                                               (N = 1, 2, 4, 8, 16 samples per pixel, per-frame path only)
 //          [--adaptive BASE:THRESHOLD]                             (with --spp N: BASE samples everywhere, N where contrast exceeds THRESHOLD)
 //          [--lens RADIUS:FOCUS]                                   (with --spp N: a thin lens of that aperture radius, sharp at distance FOCUS)
+//          [--dispersion BANDS[:ABBE]]                             (with --spp N, default 1: N positions x BANDS bands of the Abbe number, default 30)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cstdio>
@@ -69,8 +70,8 @@ static int launch_ranks(int argc, char** argv, int gpus)
 int main(int argc, char** argv)
 {
     RefractionDemo::Options opt;
-    int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0;
-    float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f;
+    int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0;
+    float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f;
     bool have_lens = false, pump = false, stream = false;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
@@ -94,6 +95,10 @@ int main(int argc, char** argv)
             if (sscanf(argv[++i], "%f:%f", &lens_radius, &lens_focus) != 2 || !(lens_radius >= 0.0f) || !(lens_focus > 0.0f)) { fprintf(stderr, "--lens takes RADIUS:FOCUS, RADIUS >= 0, FOCUS > 0\n"); return 2; }
             have_lens = true;
         }
+        else if (arg("--dispersion")) {
+            const int got = sscanf(argv[++i], "%d:%f", &n_bands, &abbe);
+            if (got < 1 || n_bands < 1 || n_bands > 64 || (got == 1 && strchr(argv[i], ':')) || !(abbe > 0.0f)) { fprintf(stderr, "--dispersion takes BANDS[:ABBE], 1 <= BANDS <= 64, ABBE > 0\n"); return 2; }
+        }
         else if (arg("--device")) opt.device = atoi(argv[++i]);
         else if (arg("--gpus")) gpus = atoi(argv[++i]);
         else if (arg("--frames-per-gather")) fpg = atoi(argv[++i]);
@@ -103,11 +108,17 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (base && (!spp || base > spp)) { fprintf(stderr, "--adaptive BASE:THRESHOLD needs --spp N with BASE <= N\n"); return 2; }
     if (have_lens && (!spp || base)) { fprintf(stderr, "--lens RADIUS:FOCUS needs --spp N and cannot be combined with --adaptive\n"); return 2; }
+    if (n_bands) {
+        if (base || have_lens) { fprintf(stderr, "--dispersion BANDS[:ABBE] cannot be combined with --adaptive or --lens\n"); return 2; }
+        if (stream || pump || gpus > 0) { fprintf(stderr, "--dispersion renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
+        if (!spp) spp = 1;
+        if (spp < 0 || (long long)spp * n_bands > 64) { fprintf(stderr, "--dispersion: --spp N times BANDS must not exceed 64 samples\n"); return 2; }
+    }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
         unsigned char id[128];
@@ -200,7 +211,7 @@ int main(int argc, char** argv)
     uint64_t refined = 0;
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
-        rc = base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -218,6 +229,9 @@ int main(int argc, char** argv)
     if (frames && base)
         printf("%d frames of %dx%d at %d to %d samples per pixel (threshold %g) in %.3f s (%.1f fps incl. readback); %.2f %% of the pixels refined\n", frames,
                opt.width, opt.height, base, spp, threshold, s, frames / s, 100.0 * (double)refined / ((double)frames * opt.width * opt.height));
+    else if (frames && n_bands)
+        printf("%d frames of %dx%d at %d samples per pixel x %d bands of Abbe number %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
+               opt.height, spp, n_bands, abbe, s, frames / s);
     else if (frames && have_lens)
         printf("%d frames of %dx%d at %d samples per pixel through a lens of radius %g focused at %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, lens_radius, lens_focus, s, frames / s);

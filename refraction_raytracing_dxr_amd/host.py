@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, HIT_DTYPE, INSTANCE_DTYPE, NODE_DTYPE, RAY_DTYPE,
+from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, BAND_DTYPE, HIT_DTYPE, INSTANCE_DTYPE, NODE_DTYPE, RAY_DTYPE,
                     TRI_DTYPE, VERTEX_DTYPE, DispatchParams, Lens, RRError, SceneConstants, Stats)
 
 FOV_Y = float(np.float32(52.0 / 180.0 * 3.1415))     # RefractionDemo.cpp:559
@@ -77,6 +77,19 @@ def sample_pattern(n):
     rc = _capi.lib().rr_host_sample_pattern(n if n >= 0 else 0, out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc:
         raise RRError(rc, "rr_host_sample_pattern(%d)" % n)
+    return out
+
+
+def spectral_bands(n, ior_d=1.3, abbe=30.0):
+    """-> BAND_DTYPE [n]: a band table for render_spectral (rr_host_spectral_bands), n = 1..64 bands at the midpoints of n equal
+    slices of 400..700 nm.  ior follows Cauchy's law through ior_d at 587.6 nm with the Abbe number abbe (smaller: more dispersion;
+    inf: none); the weights are tents of half-width 100 nm round 650 (R), 550 (G) and 450 nm (B), each channel summing to n, so a
+    white environment stays white.  n == 1: (ior_d, 1, 1, 1)."""
+    n = int(n)
+    out = np.zeros(max(n, 1), BAND_DTYPE)
+    rc = _capi.lib().rr_host_spectral_bands(n if n >= 0 else 0, float(np.float32(ior_d)), float(abbe), out.ctypes.data)
+    if rc:
+        raise RRError(rc, "rr_host_spectral_bands(%d, %r, %r)" % (n, ior_d, abbe))
     return out
 
 
@@ -636,6 +649,45 @@ class Renderer:
             self._ck(self._L.rr_render_lens_device(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens_device")
         else:
             self._ck(self._L.rr_render_lens(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens")
+        return _result(outs)
+
+    def render_spectral(self, width, height, camera, bands=8, samples=4, params=None, abbe=30.0, paired=False, rgba8=False, ray_counts=False,
+                        device=False):
+        """Spectral frame (rr_render_spectral): render_samples with dispersion -- sample k of a pixel is shaded with the index of
+        refraction of band k instead of params.ior, and its colour is weighted per channel: channel ch of the pixel is
+        ((w_0 * c_0 + w_1 * c_1) + ...) / S in fp32, each product and sum rounded once, c_k being what shade_rays gives the ray of
+        camera_rays(camera, width, height, *offset_k) under default_params(ior=ior_k, ...).  Refracting glass gets colour fringes.
+        bands: an int B for spectral_bands(B, params.ior, abbe) (abbe is used for nothing else), a BAND_DTYPE array of your own
+        (negative weights allowed), or None for (params.ior, 1, 1, 1) throughout, which is render_samples byte for byte.
+        samples: as for render_samples, A positions.  By default the positions are crossed with the bands: S = A * B <= 64 samples,
+        sample a * B + b is position a in band b.  paired=True: both tables have S rows and sample k takes row k of each
+        (bands=None is always paired).  The other arguments, the outputs and device=True as render_samples; not a dispatch either."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "render_spectral: samples must be an int or an [S, 2] array")
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_spectral: negative size")
+        bandp = None
+        if bands is not None:
+            tab = spectral_bands(bands, p.ior, abbe) if isinstance(bands, (int, np.integer)) else np.ascontiguousarray(bands, BAND_DTYPE)
+            if tab.ndim != 1 or len(tab) == 0:
+                raise ValueError("render_spectral: bands must be an int, None or a non-empty one-dimensional BAND_DTYPE array")
+            if paired:
+                if len(tab) != n:
+                    raise ValueError("render_spectral: paired=True needs one band per sample")
+            else:
+                if n * len(tab) > _capi.MAX_SAMPLES:
+                    raise ValueError("render_spectral: positions x bands must not exceed %d samples" % _capi.MAX_SAMPLES)
+                pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
+                off = np.ascontiguousarray(np.repeat(pos, len(tab), axis=0))        # sample a * B + b: position a, band b
+                tab = np.ascontiguousarray(np.tile(tab, n))
+                offp, n = off.ctypes.data_as(C.c_void_p), len(off)
+            bandp = tab.ctypes.data_as(C.c_void_p)
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_spectral_device(self._h, w, h, C.byref(camera), C.byref(p), offp, bandp, n, *ptrs), "rr_render_spectral_device")
+        else:
+            self._ck(self._L.rr_render_spectral(self._h, w, h, C.byref(camera), C.byref(p), offp, bandp, n, *ptrs), "rr_render_spectral")
         return _result(outs)
 
     def render_adaptive(self, width, height, camera, samples=(4, 16), threshold=ADAPTIVE_THRESHOLD, params=None, rgba8=False, ray_counts=False,

@@ -563,6 +563,45 @@ int  rr_render_spectral_device(rr_context* ctx, uint32_t width, uint32_t height,
                                const rr_dispatch_params* params, const float* offsets, const rr_band* bands, uint32_t n_samples,
                                void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
+/* ---- hit groups: per-instance glass with its own index of refraction and tint (present from ABI version 3) ------------------------
+ * The context holds a material table.  An instance selects a row with the low 24 bits of rr_instance_desc::hitgroup_flags (DXR's
+ * InstanceContributionToHitGroupIndex), in rr_build_tlas and in its RR_BUILD_PERFORM_UPDATE alike.  A material is an index of
+ * refraction and an absorption coefficient per unit length and colour channel (R, G, B).  Only the two calls below read the table:
+ * the dispatches, rr_shade_rays and the other frames shade every instance with params->ior and absorb nothing.
+ *
+ * rr_set_materials copies n rows into a device buffer the context owns; n == 0 clears the table.  It may come before or after
+ * rr_build_tlas and may be repeated: the new table takes effect on the next call, without a rebuild.  Every ior finite and > 0,
+ * every sigma_a finite and >= 0, n <= 2^24 (RR_ERR_INVALID_ARGUMENT otherwise; the table in force stays).  Waits for the
+ * context's stream.
+ *
+ * rr_shade_rays_materials[_device] is rr_shade_rays[_device] and rr_render_materials[_device] is rr_render_samples[_device] -- the
+ * same arguments, rays, outputs, resolve, culling, alignment rules and state: not dispatches -- with this ray tree instead:
+ *   1. the path weight is one float per channel.  RayGen sets (1, 1, 1); every w * (1 - R) and w * R is taken per channel; a Miss
+ *      adds acc.c = fmaf(w.c, e.c, acc.c);
+ *   2. ClosestHit on instance i refracts with material m = hitgroup_flags_i & 0xffffff: eta = outside ? 1.0f / ior_m : ior_m;
+ *   3. a ray that reaches ClosestHit from inside the glass (it was refracted into instance i and now hits its inner side) is
+ *      absorbed over the distance t it travelled, before anything else: w.c = w.c * E(-(sigma_a_m[c] * t)), each operation rounded
+ *      once.  Secondary directions have unit length, so t is a length; a caller's primary ray always starts outside.  The medium
+ *      is that of the surface being left, which for overlapping or nested instances is an approximation.  A Miss from inside (an
+ *      open mesh) absorbs nothing.
+ * E is rr_host_expf_neg, fp32 with explicit fused operations, the same on host and device: exactly 1 at +0 and -0, 0 from -87 down.
+ * So a table whose rows are all { ior, 0, 0, 0 } makes both calls equal rr_shade_rays / rr_render_samples under params->ior = ior,
+ * byte for byte.  params->ior is ignored (not even validated); the rest of params is used and checked as by the scalar calls.
+ * RR_ERR_STATE without a built TLAS or without a table; RR_ERR_INVALID_ARGUMENT when an instance's index is >= the table's
+ * length. */
+typedef struct rr_material { float ior; float sigma_a[3]; } rr_material;      /* 16 bytes */
+int  rr_set_materials(rr_context* ctx, const rr_material* mats, uint32_t n);
+int  rr_shade_rays_materials(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f,
+                             uint8_t* rgba8, uint32_t* n_rays);
+int  rr_shade_rays_materials_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f,
+                                    void* d_rgba8, void* d_n_rays);
+int  rr_render_materials(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                         const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8,
+                         uint32_t* n_rays);
+int  rr_render_materials_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                                const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
+                                void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */
@@ -632,6 +671,11 @@ int  rr_host_camera_rays(const rr_scene_constants* c, uint32_t width, uint32_t h
  * > 0, +inf allowed (every ior is ior_d then); a table with an ior that is not finite and > 0 (abbe too small) is not handed out
  * (RR_ERR_INVALID_ARGUMENT, as n == 0, n > RR_MAX_SAMPLES or bands == NULL). */
 int  rr_host_spectral_bands(uint32_t n, float ior_d, float abbe, rr_band* bands);
+/* exp(x) for x <= 0 as the material kernels compute Beer-Lambert absorption: if (!(x > -87)) 0; k = floorf(fmaf(x, 1.44269504f,
+ * 0.5f)); r = fmaf(k, -0.693359375f, x); r = fmaf(k, 2.12194440e-4f, r); p by Horner with fmaf over 1.9875691500e-4,
+ * 1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1; y = fmaf(p, r * r, r) + 1.0f; y times 2^k
+ * built from the exponent bits.  Within 1 ulp of the correctly rounded value on [-87, 0]. */
+float rr_host_expf_neg(float x);
 /* The rays of rr_render_lens for one (pixel offset, lens offset) pair, every pixel of a width x height frame, row-major, as
  * rr_ray records shaped like those of rr_host_camera_rays: ox, oy in [0, 1], lx, ly finite and in [-1, 1], lens as rr_render_lens
  * takes it (RR_ERR_INVALID_ARGUMENT otherwise).  radius == 0: exactly rr_host_camera_rays. */

@@ -53,6 +53,9 @@ assert HIT_DTYPE.itemsize == 24 and NODE_DTYPE.itemsize == 64 and TRI_DTYPE.item
 # rr_band: one sample's index of refraction and its colour's weight per channel (render_spectral)
 BAND_DTYPE = np.dtype([("ior", "<f4"), ("weight", "<f4", 3)])
 assert BAND_DTYPE.itemsize == 16
+# rr_material: one row of the material table (set_materials) -- index of refraction, absorption per unit length for R, G, B
+MATERIAL_DTYPE = np.dtype([("ior", "<f4"), ("sigma_a", "<f4", 3)])
+assert MATERIAL_DTYPE.itemsize == 16
 
 
 class SceneConstants(C.Structure):
@@ -172,6 +175,12 @@ SYMBOLS = {
                                      _P, _P, _P]),
     "rr_render_spectral_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, _P, C.c_uint32,
                                             _P, _P, _P]),
+    "rr_set_materials": (C.c_int, [_P, _P, C.c_uint32]),
+    "rr_shade_rays_materials": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_shade_rays_materials_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_render_materials": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_render_materials_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P,
+                                             _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -189,6 +198,7 @@ SYMBOLS = {
     "rr_host_camera_orbit": (C.c_int, [C.c_float] * 5 + [C.POINTER(SceneConstants)]),
     "rr_host_sample_pattern": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
     "rr_host_spectral_bands": (C.c_int, [C.c_uint32, C.c_float, C.c_float, _P]),
+    "rr_host_expf_neg": (C.c_float, [C.c_float]),
     "rr_host_camera_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "rr_host_lens_rays": (C.c_int, [C.POINTER(SceneConstants), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Lens),
                                     C.c_float, C.c_float, _P]),

@@ -129,6 +129,28 @@ int drawFrameSpectral(int spp, int n_bands, float abbe)
     return RR_OK;
 }
 
+int setMaterials(const rr_material* mats, int n)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (n <= 0 || !mats) return fail(RR_ERR_INVALID_ARGUMENT, "setMaterials: need at least one material");
+    const int rc = rr_set_materials(g_ctx, mats, (uint32_t)n);
+    return rc == RR_OK ? RR_OK : fail(rc, "rr_set_materials");
+}
+
+int drawFrameMaterials(int spp)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameMaterials: spp must be 1, 2, 4, 8 or 16");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    if ((rc = rr_render_materials(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)spp, nullptr,
+                                  g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_materials");
+    return RR_OK;
+}
+
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined)
 {
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");

@@ -35,6 +35,11 @@ int drawFrameLens(int spp, float radius, float focus_distance);
 // drawFrameSamples with dispersion (rr_render_spectral): the spp built-in positions crossed with the n_bands bands of
 // rr_host_spectral_bands(n_bands, the dispatch's ior, abbe), sample a * n_bands + b being position a in band b; spp * n_bands <= 64
 int drawFrameSpectral(int spp, int n_bands, float abbe);
+// The material table of the scene (rr_set_materials).  Instance i is made of row i modulo n: the demo's one instance keeps hit-group
+// index 0, which is row 0 of any table.  drawFrameMaterials is drawFrameSamples shaded with it (rr_render_materials): the glass's
+// index of refraction and tint come from the table, the dispatch's ior is not used
+int setMaterials(const rr_material* mats, int n);
+int drawFrameMaterials(int spp);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

@@ -168,6 +168,7 @@ int tlas_inputs(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, 
                 scene_scale = std::max(scene_scale, std::fabs(d.transform[4 * r] * x + d.transform[4 * r + 1] * y + d.transform[4 * r + 2] * z + d.transform[4 * r + 3]));
         }
         o.flags = d.hitgroup_flags >> 24;
+        o.material = d.hitgroup_flags & 0xffffffu;
         o.mask = d.instance_id_mask >> 24;
         memcpy(&xb[(size_t)i * 12], d.transform, 48);
         memcpy(&xb[(size_t)n * 12 + (size_t)i * 6], m.bounds, 24);
@@ -226,6 +227,8 @@ int finish_tlas(rr_context* ctx, const rr_instance_desc* instances, uint32_t n, 
     ctx->inst_host.assign(instances, instances + n);
     ctx->n_insts = n;
     ctx->scene_scale = scene_scale;
+    ctx->max_material = 0;
+    for (uint32_t i = 0; i < n; ++i) ctx->max_material = std::max(ctx->max_material, instances[i].hitgroup_flags & 0xffffffu);
     const rr_instance_desc& d0 = instances[0];
     ctx->single_identity = n == 1 && inst0.identity && (d0.hitgroup_flags >> 24) == 0 && ((d0.instance_id_mask >> 24) & 0xffu) != 0;
     if (scene_stack_need(ctx) > 64) return fail(ctx, RR_ERR_UNSUPPORTED, "rr_build_tlas: TLAS+BLAS deeper than the 64-entry stack");

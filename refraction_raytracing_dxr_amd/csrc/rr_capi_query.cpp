@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -246,6 +246,45 @@ int spectral_impl(rr_context* ctx, const SpectralReq& q, const SampleOffsets& of
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
+
+// What both material calls need beside their scalar twins' checks: a table, and every instance of the scene inside it.  The index
+// of refraction comes from the table, so the one in params is not looked at: the checks and shading_args see a valid one instead.
+int check_materials(rr_context* ctx, const char* who, rr_dispatch_params& p)
+{
+    const std::string w(who);
+    if (!ctx->n_mats) return fail(ctx, RR_ERR_STATE, (w + ": set a material table first (rr_set_materials)").c_str());
+    if (ctx->max_material >= ctx->n_mats)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": an instance's hit-group index is not below the material table's length").c_str());
+    p.ior = 1.0f;
+    return RR_OK;
+}
+
+// the hit-group index of instance 0, which the kernels take as an argument where the scene skips the top level
+uint32_t inst0_material(const rr_context* ctx) { return ctx->inst_host.empty() ? 0u : ctx->inst_host[0].hitgroup_flags & 0xffffffu; }
+
+// shade_impl with the material table (p: after check_materials)
+int shade_mat_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+{
+    if (int r = check_shading_params(ctx, "shade_rays_materials", p)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    const DispatchDev a = shading_args(p);
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_shade_rays_mat(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend,
+                                             v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+
+// samples_impl with the material table (q.params: after check_materials)
+int materials_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q);
+    if (hipError_t e = launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
+                                               f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.who, e);
+    return RR_OK;
+}
 } // namespace
 
 extern "C" {
@@ -485,6 +524,105 @@ int rr_render_spectral_device(rr_context* ctx, uint32_t width, uint32_t height, 
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_spectral_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return spectral_impl(ctx, q, off, bt, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+float rr_host_expf_neg(float x) { return rr_expf_neg(x); }
+
+int rr_set_materials(rr_context* ctx, const rr_material* mats, uint32_t n)
+{
+    if (int r = use_device(ctx)) return r;
+    if (n == 0) { ctx->n_mats = 0; return RR_OK; }
+    if (!mats) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: null table");
+    if (n > 0x1000000u) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: a hit-group index has 24 bits, so at most 16 777 216 materials");
+    std::vector<MatDev> rows(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const rr_material& m = mats[i];
+        if (!std::isfinite(m.ior) || !(m.ior > 0.0f)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: every ior must be finite and > 0");
+        MatDev& o = rows[i];
+        memset(&o, 0, sizeof o);
+        o.ior = m.ior; o.inv_ior = inv_ior_of(m.ior);
+        for (int ch = 0; ch < 3; ++ch) {
+            if (!std::isfinite(m.sigma_a[ch]) || !(m.sigma_a[ch] >= 0.0f))
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: every sigma_a must be finite and >= 0");
+            o.sigma[ch] = m.sigma_a[ch];
+        }
+    }
+    // the old table stays in force until the new one is whole: launches in flight on the stream read it, and the copy is ordered
+    // behind them (grow waits for the stream before it lets the old buffer go)
+    if (n > ctx->d_mats.size()) {
+        ctx->n_mats = 0;
+        if (int r = ctx->d_mats.grow(ctx, n)) return r;
+    }
+    RR_HIP(hipMemcpyAsync(ctx->d_mats.get(), rows.data(), (size_t)n * sizeof(MatDev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));   // (rows goes away with this call)
+    ctx->n_mats = n;
+    return RR_OK;
+}
+
+int rr_shade_rays_materials(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
+                            uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_materials: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_materials(ctx, "rr_shade_rays_materials", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials: need rgba32f or rgba8");
+    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials: null rays");
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_mat_impl(ctx, "rr_shade_rays_materials", ctx->d_rays.get(), n, p, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_shade_rays_materials_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
+                                   void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_materials_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_materials(ctx, "rr_shade_rays_materials_device", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials_device: need d_rgba32f or d_rgba8");
+    const char* const align = "rr_shade_rays_materials_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
+    return shade_mat_impl(ctx, "rr_shade_rays_materials_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
+                          { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_materials(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                        const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_materials: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_materials(ctx, "rr_render_materials", p)) return r;
+    const SamplesReq q = { "rr_render_materials", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = materials_impl(ctx, q, off, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_materials_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                               const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_materials_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_materials(ctx, "rr_render_materials_device", p)) return r;
+    const SamplesReq q = { "rr_render_materials_device", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_materials_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return materials_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -233,6 +233,10 @@ struct rr_context {
     // rr_render_adaptive's own: its sample counts and its workspace, in units of 16 bytes
     DevBuf<uint32_t>   d_adaptive_taken;
     DevBuf<float4>     d_adaptive_ws;
+    // the material table (rr_set_materials): n_mats rows at the head of d_mats, 0 = none set; max_material: the largest
+    // hit-group index (hitgroup_flags & 0xffffff) among the instances of the current TLAS
+    DevBuf<MatDev>     d_mats;
+    uint32_t n_mats = 0, max_material = 0;
 };
 
 namespace rr {

@@ -71,6 +71,16 @@ struct BandTable { static constexpr uint32_t MAX = SampleOffsets::MAX; float ior
 hipError_t launch_render_spectral(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const BandTable& bands,
                                   uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
                                   hipStream_t s);
+// ---- rr_render_materials.hip: per-instance glass (rr_shade_rays_materials[_device], rr_render_materials[_device]):
+// launch_shade_rays and launch_render_samples with the ray tree of rr_render_materials.h -- an RGB path weight, the index of
+// refraction of the hit instance's material instead of a.ior / a.inv_ior, and Beer-Lambert absorption over the path inside the
+// glass.  mats: the context's table in device memory (rows of 32 bytes), which every InstDev::material of the scene indexes; mat0:
+// the index of instance 0, used where the scene skips the top level.  mats == nullptr is hipErrorInvalidValue
+hipError_t launch_shade_rays_mat(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, uint32_t mat0, const rr_ray_dev* rays, uint32_t n,
+                                 float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+hipError_t launch_render_materials(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
+                                   uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
+                                   bool stack16, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

@@ -8,6 +8,7 @@
 //   NrmRec   48 B  the three vertex normals of the same triangle (ClosestHit, RayTracing.hlsl:83-85)
 //   env      16 B  per texel (RGB32F padded to float4: one dwordx4 load per Miss)
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace rr {
@@ -72,7 +73,7 @@ struct alignas(16) InstDev {
     uint32_t identity;
     float    scale;           // largest |coordinate| of the BLAS bounds (box-test padding in object space)
     QGrid    grid;            // of the BLAS this instance refers to
-    uint32_t pad;
+    uint32_t material;        // InstanceContributionToHitGroupIndex (hitgroup_flags & 0xffffff): read by the material kernels only
 };
 static_assert(sizeof(InstDev) == 96, "InstDev must be 96 B");
 
@@ -143,6 +144,40 @@ struct DispatchDev {
 // DispatchDev::inv_ior for an index of refraction, on the host in fp32: the one expression every launcher uses (the dispatches, the
 // radiance queries and frames, and per band the spectral frames), so that the same ior refracts alike everywhere
 inline float inv_ior_of(float ior) { return 1.0f / ior; }
+
+// One row of the material table (rr_set_materials) as the material kernels read it (rr_render_materials.h): a lane fetches the
+// first half at every ClosestHit and the second only when its ray arrives from inside the glass.  inv_ior = inv_ior_of(ior).
+struct alignas(32) MatDev {
+    float ior, inv_ior;
+    float sigma[3];           // absorption per unit length, R G B
+    uint32_t pad[3];
+};
+static_assert(sizeof(MatDev) == 32, "MatDev must be 32 B");
+
+// exp(x) for x <= 0 (Beer-Lambert: x = -(sigma * t)), the one definition host and device share, in fp32 with every fused
+// operation written as fmaf (Cephes' expf: x = k ln 2 + r with ln 2 split in two, a degree-5 polynomial in r, 2^k from the exponent
+// bits).  Exactly 1 for +0 and -0; 0 from -87 down (and for a NaN); k >= -126 above the cut, so 2^k is a normal number.
+#if defined(__HIPCC__)
+#define RR_HOST_DEVICE __host__ __device__
+#else
+#define RR_HOST_DEVICE
+#endif
+RR_HOST_DEVICE inline float rr_expf_neg(float x)
+{
+    if (!(x > -87.0f)) return 0.0f;
+    const float k = floorf(fmaf(x, 1.44269504f, 0.5f));
+    float r = fmaf(k, -0.693359375f, x);
+    r = fmaf(k, 2.12194440e-4f, r);
+    float p = 1.9875691500e-4f;
+    p = fmaf(p, r, 1.3981999507e-3f);
+    p = fmaf(p, r, 8.3334519073e-3f);
+    p = fmaf(p, r, 4.1665795894e-2f);
+    p = fmaf(p, r, 1.6666665459e-1f);
+    p = fmaf(p, r, 5.0000001201e-1f);
+    const float y = fmaf(p, r * r, r) + 1.0f;
+    const uint32_t two_k = (uint32_t)((int32_t)k + 127) << 23;
+    return y * __builtin_bit_cast(float, two_k);
+}
 
 // k_render_lds (persistent workgroups, BLAS nodes in LDS): the work queues of one launch.
 // Work is handed out in two phases, a ticket at a time; the wave that draws a ticket shares its blocks with its workgroup

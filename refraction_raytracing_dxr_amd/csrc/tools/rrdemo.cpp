@@ -7,6 +7,7 @@
 //          [--adaptive BASE:THRESHOLD]                             (with --spp N: BASE samples everywhere, N where contrast exceeds THRESHOLD)
 //          [--lens RADIUS:FOCUS]                                   (with --spp N: a thin lens of that aperture radius, sharp at distance FOCUS)
 //          [--dispersion BANDS[:ABBE]]                             (with --spp N, default 1: N positions x BANDS bands of the Abbe number, default 30)
+//          [--materials "IOR:R,G,B;IOR:R,G,B;..."]                 (with --spp N, default 1: a material table, absorption per unit length; instance i is made of row i modulo the rows)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cstdio>
@@ -73,6 +74,7 @@ int main(int argc, char** argv)
     int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0;
     float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f;
     bool have_lens = false, pump = false, stream = false;
+    std::vector<rr_material> materials;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
         auto arg = [&](const char* name) { return !strcmp(argv[i], name) && i + 1 < argc; };
@@ -99,6 +101,18 @@ int main(int argc, char** argv)
             const int got = sscanf(argv[++i], "%d:%f", &n_bands, &abbe);
             if (got < 1 || n_bands < 1 || n_bands > 64 || (got == 1 && strchr(argv[i], ':')) || !(abbe > 0.0f)) { fprintf(stderr, "--dispersion takes BANDS[:ABBE], 1 <= BANDS <= 64, ABBE > 0\n"); return 2; }
         }
+        else if (arg("--materials")) {
+            bool ok = true;
+            for (const char* q = argv[++i]; ok && *q;) {
+                rr_material m;
+                int used = 0;
+                ok = sscanf(q, "%f:%f,%f,%f%n", &m.ior, &m.sigma_a[0], &m.sigma_a[1], &m.sigma_a[2], &used) == 4 && (q[used] == ';' || q[used] == 0) &&
+                     m.ior > 0.0f && m.sigma_a[0] >= 0.0f && m.sigma_a[1] >= 0.0f && m.sigma_a[2] >= 0.0f;
+                materials.push_back(m);
+                q += used + (q[used] == ';' ? 1 : 0);
+            }
+            if (!ok || materials.empty()) { fprintf(stderr, "--materials takes IOR:R,G,B rows separated by ';', IOR > 0, R, G, B >= 0\n"); return 2; }
+        }
         else if (arg("--device")) opt.device = atoi(argv[++i]);
         else if (arg("--gpus")) gpus = atoi(argv[++i]);
         else if (arg("--frames-per-gather")) fpg = atoi(argv[++i]);
@@ -108,7 +122,7 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;...]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (base && (!spp || base > spp)) { fprintf(stderr, "--adaptive BASE:THRESHOLD needs --spp N with BASE <= N\n"); return 2; }
@@ -118,6 +132,11 @@ int main(int argc, char** argv)
         if (stream || pump || gpus > 0) { fprintf(stderr, "--dispersion renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
         if (!spp) spp = 1;
         if (spp < 0 || (long long)spp * n_bands > 64) { fprintf(stderr, "--dispersion: --spp N times BANDS must not exceed 64 samples\n"); return 2; }
+    }
+    if (!materials.empty()) {
+        if (base || have_lens || n_bands) { fprintf(stderr, "--materials cannot be combined with --adaptive, --lens or --dispersion\n"); return 2; }
+        if (stream || pump || gpus > 0) { fprintf(stderr, "--materials renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
+        if (!spp) spp = 1;
     }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
@@ -159,6 +178,10 @@ int main(int argc, char** argv)
     }
     int rc = RefractionDemo::initialize(opt);
     if (rc != RR_OK) { fprintf(stderr, "initialize failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
+    if (!materials.empty() && (rc = RefractionDemo::setMaterials(materials.data(), (int)materials.size())) != RR_OK) {
+        fprintf(stderr, "setMaterials failed (%d): %s\n", rc, RefractionDemo::lastError());
+        return 1;
+    }
     auto t0 = std::chrono::steady_clock::now();
     if (pump) {
         rr_stats st;
@@ -211,7 +234,7 @@ int main(int argc, char** argv)
     uint64_t refined = 0;
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
-        rc = base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -232,6 +255,9 @@ int main(int argc, char** argv)
     else if (frames && n_bands)
         printf("%d frames of %dx%d at %d samples per pixel x %d bands of Abbe number %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, n_bands, abbe, s, frames / s);
+    else if (frames && !materials.empty())
+        printf("%d frames of %dx%d at %d samples per pixel with %d materials in %.3f s (%.1f fps incl. readback)\n", frames, opt.width, opt.height, spp,
+               (int)materials.size(), s, frames / s);
     else if (frames && have_lens)
         printf("%d frames of %dx%d at %d samples per pixel through a lens of radius %g focused at %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, lens_radius, lens_focus, s, frames / s);

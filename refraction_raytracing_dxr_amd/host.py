@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, BAND_DTYPE, HIT_DTYPE, INSTANCE_DTYPE, NODE_DTYPE, RAY_DTYPE,
+from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, BAND_DTYPE, HIT_DTYPE, INSTANCE_DTYPE, MATERIAL_DTYPE, NODE_DTYPE, RAY_DTYPE,
                     TRI_DTYPE, VERTEX_DTYPE, DispatchParams, Lens, RRError, SceneConstants, Stats)
 
 FOV_Y = float(np.float32(52.0 / 180.0 * 3.1415))     # RefractionDemo.cpp:559
@@ -140,8 +140,10 @@ def lens_screen_rect(bounds, camera, lens, w, h):
     return tuple(int(v) for v in r)
 
 
-def make_instances(transforms=None, meshes=None, masks=None, flags=None):
-    """64-byte instance records (RefractionDemo.cpp:324-334 fills exactly one: identity, mask 1, flags 0)."""
+def make_instances(transforms=None, meshes=None, masks=None, flags=None, materials=None):
+    """64-byte instance records (RefractionDemo.cpp:324-334 fills exactly one: identity, mask 1, flags 0).  materials: per instance
+    the row of the material table (Renderer.set_materials) it is made of -- DXR's InstanceContributionToHitGroupIndex, the low 24
+    bits of hitgroup_flags; default 0."""
     if transforms is None:
         transforms = [np.eye(4, dtype=np.float32)[:3]]
     n = len(transforms)
@@ -149,7 +151,7 @@ def make_instances(transforms=None, meshes=None, masks=None, flags=None):
     for i, t in enumerate(transforms):
         inst["transform"][i] = np.asarray(t, np.float32).reshape(12)
         inst["instance_id_mask"][i] = (i & 0xffffff) | (((masks[i] if masks is not None else 1) & 0xff) << 24)
-        inst["hitgroup_flags"][i] = ((flags[i] if flags is not None else 0) & 0xff) << 24
+        inst["hitgroup_flags"][i] = (((flags[i] if flags is not None else 0) & 0xff) << 24) | ((int(materials[i]) if materials is not None else 0) & 0xffffff)
         inst["blas"][i] = meshes[i] if meshes is not None else 0
     return inst
 
@@ -622,6 +624,52 @@ class Renderer:
             self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples_device")
         else:
             self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples")
+        return _result(outs)
+
+    def set_materials(self, table):
+        """The material table (rr_set_materials): a MATERIAL_DTYPE array, or rows of (ior, (sigma_r, sigma_g, sigma_b)) -- index of
+        refraction and absorption per unit length and channel.  Instance i is made of row make_instances(materials=...)[i].  Copied;
+        an empty table or None clears it.  May come before or after build_tlas and takes effect on the next shade_rays_materials /
+        render_materials without a rebuild."""
+        t = np.zeros(0, MATERIAL_DTYPE) if table is None else np.ascontiguousarray(table, MATERIAL_DTYPE).reshape(-1)
+        self._ck(self._L.rr_set_materials(self._h, t.ctypes.data if len(t) else None, len(t)), "rr_set_materials")
+
+    def shade_rays_materials(self, rays, params=None, rgba8=False, ray_counts=False):
+        """shade_rays with the material table (rr_shade_rays_materials): the same rays, outputs and stream order, shaded by the ray
+        tree with an RGB path weight -- ClosestHit refracts with the index of refraction of the hit instance's material, and a ray
+        that crossed the glass of an instance is absorbed per channel by exp(-sigma_a * distance) before it is shaded.  params.ior is
+        ignored.  A table whose rows are all (ior, (0, 0, 0)) gives shade_rays under default_params(ior=ior) byte for byte."""
+        p = params if params is not None else default_params()
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("shade_rays_materials: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("shade_rays_materials: need a contiguous [n, 12] int32 or float32 tensor")
+            n = t.shape[0]
+            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
+            self._ck(self._L.rr_shade_rays_materials_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
+                     "rr_shade_rays_materials_device")
+        else:
+            rays = np.ascontiguousarray(rays, RAY_DTYPE)
+            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
+            self._ck(self._L.rr_shade_rays_materials(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_materials")
+        return _result(outs)
+
+    def render_materials(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
+        """render_samples with the material table (rr_render_materials): the same arguments, samples, resolve and outputs, every
+        sample shaded as shade_rays_materials shades camera_rays(camera, width, height, *offset_s).  params.ior is ignored."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "render_materials: samples must be an int or an [S, 2] array")
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_materials: negative size")
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_materials_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_materials_device")
+        else:
+            self._ck(self._L.rr_render_materials(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_materials")
         return _result(outs)
 
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):

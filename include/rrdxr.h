@@ -602,6 +602,59 @@ int  rr_render_materials_device(rr_context* ctx, uint32_t width, uint32_t height
                                 const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
                                 void* d_rgba8, void* d_n_rays);
 
+/* ---- nested media: instances inside, or overlapping, other instances (present from ABI version 3) ---------------------------------
+ * The material tree above traces with CULL_BACK outside and CULL_FRONT inside, so a ray inside one glass instance cannot see the
+ * front faces of anything placed in it: an ice cube in water is invisible from inside the water, eta at the outer surface is always
+ * taken against air and the outer glass absorbs over the whole chord.  The four calls below are their _materials twins -- the same
+ * arguments, table (rr_set_materials, rr_material), rays, sample offsets, resolve, tone mapping, RGBA8, culling of background blocks,
+ * alignment rules and state: not dispatches, on the context's stream, params->ior ignored -- with a ray tree in which every ray knows
+ * the media it is in.  One rounding per written operation, fmaf only where written:
+ *
+ * A ray carries (O, D, w[3], count, L).  L is the list of the material rows of the media it is in, in the order it entered them,
+ * RR_NESTED_MAX_MEDIA (4) at most; empty means air (ior 1, no absorption).  A caller's primary ray starts with L empty.
+ * TraceRay is called with cull flags 0 (both faces), mask 0xff and [tmin, tmax] as before.  The face of the hit is the HitKind of
+ * rr_query_rays_multi: front = (det > 0) != the instance's RR_INSTANCE_FLAG_TRIANGLE_FRONT_COUNTERCLOCKWISE, det in object space.
+ *   Miss: acc.c = fmaf(w.c, e.c, acc.c).  Nothing is absorbed, whatever L holds (an open mesh).
+ *   ClosestHit on an instance of row m at distance t with count < max_refract (a hit at the limit adds nothing):
+ *     1. c = top(L), the medium entered last.  If c is not air: w.ch = w.ch * E(-(sigma_a[c].ch * t)), E = rr_host_expf_neg: the
+ *        medium crossed, not the one hit.
+ *     2. Front face: L' = push(L, m); a push onto a full list is dropped.  Back face: L' = L without its last occurrence of m;
+ *        removing an absent row changes nothing.  c' = top(L').
+ *     3. X = fmaf(t, D, O).  Children have count + 1 and [tmin_secondary, tmax_secondary].
+ *     4. c' and c the same row: NOT AN INTERFACE.  (The ray leaves something whose surface lies inside a medium entered later, or
+ *        enters a second body of the same row, or its push was dropped, or it meets a back face from outside.)  One child
+ *        (X, D, w, L'): D and w keep their bits, no reflection, no Fresnel factor.  The pass still costs one count, which keeps the
+ *        tree bounded as before: a branch ends at max_refract whatever it meets.
+ *     5. Otherwise AN INTERFACE.  N is the shading normal, Nf = front ? N : -N, R the shader's expression (hlsl:92-93),
+ *        eta = ior[c] * (1.0f / ior[c']) with air as 1.0f on either side (1.0f / ior is the value rr_set_materials stores), and
+ *        RefractRay(D, Nf, eta).  The refracted child carries L' and w * (1 - R) per channel; the reflected child exists if
+ *        count < max_reflect, stays where it was (L) and carries w * R; on total internal reflection only the reflected child
+ *        exists (hlsl:118-122).  Depth-first, refracted child first, as before.
+ *
+ * Reduction: on a scene in which culled and unculled TraceRay find the same hit for every ray of every tree -- closed, consistently
+ * wound, pairwise disjoint instances -- these calls equal rr_shade_rays_materials / rr_render_materials byte for byte, colours, RGBA8
+ * and ray counts: 1.0f * inv_ior and ior * 1.0f are exact, top(L) is the instance being left, front is outside.  (An open mesh such
+ * as the shipped monkey.obj does not qualify.)
+ * Overlap is handled without priorities: where a liquid's mesh reaches slightly into its container's wall, the interface is taken at
+ * the first of the two surfaces met and the second is "not an interface".
+ * Not covered: more than RR_NESTED_MAX_MEDIA simultaneous media (the dropped push); rays that start inside a medium; R0 recomputed
+ * from the two indices (it stays the shader's constant); lens, spectral and adaptive frames; the dispatch kernels.
+ *
+ * RR_ERR_STATE without a built TLAS or without a table; RR_ERR_INVALID_ARGUMENT when an instance's row is >= the table's length
+ * or > RR_NESTED_MAX_MATERIAL (a list entry is one byte); the table itself may be longer. */
+#define RR_NESTED_MAX_MEDIA 4
+#define RR_NESTED_MAX_MATERIAL 254
+int  rr_shade_rays_nested(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f,
+                          uint8_t* rgba8, uint32_t* n_rays);
+int  rr_shade_rays_nested_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f,
+                                 void* d_rgba8, void* d_n_rays);
+int  rr_render_nested(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                      const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8,
+                      uint32_t* n_rays);
+int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                             const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
+                             void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */

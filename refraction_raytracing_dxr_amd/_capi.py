@@ -28,7 +28,9 @@ RAY_FLAG_CULL_BACK = 0x10
 RAY_FLAG_CULL_FRONT = 0x20
 MAX_SAMPLES = 64                         # RR_MAX_SAMPLES: most samples per pixel of render_samples
 QUERY_MAX_HITS = 16                      # RR_QUERY_MAX_HITS: largest k of query_rays_multi
-HIT_KIND_FRONT_FACE = 0xFE               # RR_HIT_KIND_TRIANGLE_FRONT_FACE (query_rays_multi's hit word)
+NESTED_MAX_MEDIA = 4                     # RR_NESTED_MAX_MEDIA: media a ray of shade_rays_nested / render_nested can be in at once
+NESTED_MAX_MATERIAL = 254                # RR_NESTED_MAX_MATERIAL: highest material row an instance of such a scene may use
+HIT_KIND_FRONT_FACE = 0xFE              # RR_HIT_KIND_TRIANGLE_FRONT_FACE (query_rays_multi's hit word)
 HIT_KIND_BACK_FACE = 0xFF
 INSTANCE_FLAG_CULL_DISABLE = 0x1
 INSTANCE_FLAG_FRONT_CCW = 0x2
@@ -181,6 +183,10 @@ SYMBOLS = {
     "rr_render_materials": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
     "rr_render_materials_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P,
                                              _P]),
+    "rr_shade_rays_nested": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_shade_rays_nested_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_render_nested": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_render_nested_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -151,6 +151,20 @@ int drawFrameMaterials(int spp)
     return RR_OK;
 }
 
+int drawFrameNested(int spp)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameNested: spp must be 1, 2, 4, 8 or 16");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    if ((rc = rr_render_nested(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)spp, nullptr,
+                               g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_nested");
+    return RR_OK;
+}
+
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined)
 {
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");

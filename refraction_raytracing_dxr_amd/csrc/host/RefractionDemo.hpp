@@ -40,6 +40,8 @@ int drawFrameSpectral(int spp, int n_bands, float abbe);
 // index of refraction and tint come from the table, the dispatch's ior is not used
 int setMaterials(const rr_material* mats, int n);
 int drawFrameMaterials(int spp);
+// drawFrameMaterials with the nested-media ray tree (rr_render_nested): instances may sit inside, or overlap, other instances
+int drawFrameNested(int spp);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

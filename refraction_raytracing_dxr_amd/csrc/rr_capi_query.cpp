@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -282,6 +282,39 @@ int materials_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& of
     const FrameArgs f = frame_args(ctx, q);
     if (hipError_t e = launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
                                                f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.who, e);
+    return RR_OK;
+}
+
+// What the nested calls need beside check_materials: a list entry is one byte holding row + 1, so no instance's row above 254
+int check_nested(rr_context* ctx, const char* who, rr_dispatch_params& p)
+{
+    if (int r = check_materials(ctx, who, p)) return r;
+    if (ctx->max_material > RR_NESTED_MAX_MATERIAL)
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (std::string(who) + ": an instance's hit-group index is above RR_NESTED_MAX_MATERIAL (254)").c_str());
+    return RR_OK;
+}
+
+// shade_mat_impl with the nested tree (p: after check_nested)
+int shade_nested_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+{
+    if (int r = check_shading_params(ctx, "shade_rays_nested", p)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    const DispatchDev a = shading_args(p);
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_shade_rays_nested(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend,
+                                                v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+
+// materials_impl with the nested tree (q.params: after check_nested)
+int nested_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q);
+    if (hipError_t e = launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
+                                            f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.who, e);
     return RR_OK;
 }
@@ -623,6 +656,72 @@ int rr_render_materials_device(rr_context* ctx, uint32_t width, uint32_t height,
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_materials_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return materials_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_shade_rays_nested(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
+                         uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_nested: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_shade_rays_nested", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested: need rgba32f or rgba8");
+    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested: null rays");
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_nested_impl(ctx, "rr_shade_rays_nested", ctx->d_rays.get(), n, p, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_shade_rays_nested_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
+                                void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_nested_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_shade_rays_nested_device", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested_device: need d_rgba32f or d_rgba8");
+    const char* const align = "rr_shade_rays_nested_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
+    return shade_nested_impl(ctx, "rr_shade_rays_nested_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
+                             { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_nested(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                     const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_nested: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_render_nested", p)) return r;
+    const SamplesReq q = { "rr_render_nested", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = nested_impl(ctx, q, off, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                            const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_nested_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_render_nested_device", p)) return r;
+    const SamplesReq q = { "rr_render_nested_device", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_nested_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return nested_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

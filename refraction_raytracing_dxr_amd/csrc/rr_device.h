@@ -613,6 +613,28 @@ __device__ __forceinline__ void hits_end_scene(const SceneDev& sc, f3 O, f3 D, H
 template <int KB, bool COUNT>
 __device__ __forceinline__ void hits_end_scene(const SceneDev&, f3, f3, MultiHits<KB, COUNT>&) {}
 
+// The closest hit with the face it was hit on (the nested-media kernels, rr_render_nested.h, which trace with cull flags 0).  It is
+// HitRec's walk in every step but the last -- hits_begin, hit_bound, leaf_test and hit_found bind to HitRec's overloads -- and its
+// end steps keep what hit_attributes returns and HitRec's drop: front = (det > 0) != the instance's FRONT_COUNTERCLOCKWISE flag,
+// det in object space, which is the HitKind of rr_query_rays_multi.  A scene without a top level has no instance flags.
+struct HitRecFace : HitRec { bool front; };
+__device__ __forceinline__ void hits_end_blas(const TriRec* __restrict__ tris, f3 O, f3 D, HitRecFace& best)
+{
+    best.front = false;
+    if (best.hit) best.front = hit_attributes(tris, O, D, best) > 0.0f;
+}
+__device__ __forceinline__ void hits_end_scene(const SceneDev& sc, f3 O, f3 D, HitRecFace& best)
+{
+    best.front = false;
+    if (best.hit) {
+        const InstDev in = inst_record(sc.insts, best.inst);
+        f3 Oh = O, Dh = D;
+        if (!in.identity) { Oh = xform_point(in.inv, O); Dh = xform_dir(in.inv, D); }
+        const float det = hit_attributes(sc.pool_tris, Oh, Dh, best);
+        best.front = (det > 0.0f) != ((in.flags & 0x2u) != 0u);
+    }
+}
+
 // TraceRay(Scene, flags, 0xff, 0,0,0, ray, payload): closest hit over TLAS -> BLAS.
 // TLAS = false: the reference's scene, one BLAS.  TLAS = true: the wave walks the top level in world space until every lane
 // holds an instance leaf or has finished; the lanes at a leaf then walk their instances (walk_blas: the single-BLAS loop with

@@ -81,6 +81,15 @@ hipError_t launch_shade_rays_mat(const SceneDev& sc, const DispatchDev& a, const
 hipError_t launch_render_materials(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
                                    uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
                                    bool stack16, hipStream_t s);
+// ---- rr_render_nested.hip: nested media (rr_shade_rays_nested[_device], rr_render_nested[_device]): launch_shade_rays_mat and
+// launch_render_materials with the ray tree of rr_render_nested.h -- every ray carries the list of the media it is in, TraceRay sees
+// both faces, an interface refracts with n_from / n_to and absorption is the crossed medium's.  mats, mat0: as above, every row of
+// the scene <= NESTED_MAX_MATERIAL (the host checks)
+hipError_t launch_shade_rays_nested(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, uint32_t mat0, const rr_ray_dev* rays, uint32_t n,
+                                    float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+hipError_t launch_render_nested(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
+                                uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
+                                bool stack16, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

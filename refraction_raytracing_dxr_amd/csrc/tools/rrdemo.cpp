@@ -8,6 +8,7 @@
 //          [--lens RADIUS:FOCUS]                                   (with --spp N: a thin lens of that aperture radius, sharp at distance FOCUS)
 //          [--dispersion BANDS[:ABBE]]                             (with --spp N, default 1: N positions x BANDS bands of the Abbe number, default 30)
 //          [--materials "IOR:R,G,B;IOR:R,G,B;..."]                 (with --spp N, default 1: a material table, absorption per unit length; instance i is made of row i modulo the rows)
+//          [--nested]                                              (with --materials: the nested-media ray tree, rr_render_nested)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cstdio>
@@ -73,7 +74,7 @@ int main(int argc, char** argv)
     RefractionDemo::Options opt;
     int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0;
     float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f;
-    bool have_lens = false, pump = false, stream = false;
+    bool have_lens = false, pump = false, stream = false, nested = false;
     std::vector<rr_material> materials;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
@@ -84,6 +85,7 @@ int main(int argc, char** argv)
         else if (arg("--out")) out = argv[++i];
         else if (!strcmp(argv[i], "--pump")) pump = true;
         else if (!strcmp(argv[i], "--stream")) stream = true;
+        else if (!strcmp(argv[i], "--nested")) nested = true;
         else if (arg("--frames-per-dispatch")) fpd = atoi(argv[++i]);
         else if (arg("--in-flight")) in_flight = atoi(argv[++i]);
         else if (arg("--spp")) {
@@ -122,7 +124,7 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;...]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (base && (!spp || base > spp)) { fprintf(stderr, "--adaptive BASE:THRESHOLD needs --spp N with BASE <= N\n"); return 2; }
@@ -138,6 +140,7 @@ int main(int argc, char** argv)
         if (stream || pump || gpus > 0) { fprintf(stderr, "--materials renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
         if (!spp) spp = 1;
     }
+    if (nested && materials.empty()) { fprintf(stderr, "--nested needs --materials\n"); return 2; }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
         unsigned char id[128];
@@ -234,7 +237,7 @@ int main(int argc, char** argv)
     uint64_t refined = 0;
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
-        rc = !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -256,8 +259,8 @@ int main(int argc, char** argv)
         printf("%d frames of %dx%d at %d samples per pixel x %d bands of Abbe number %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, n_bands, abbe, s, frames / s);
     else if (frames && !materials.empty())
-        printf("%d frames of %dx%d at %d samples per pixel with %d materials in %.3f s (%.1f fps incl. readback)\n", frames, opt.width, opt.height, spp,
-               (int)materials.size(), s, frames / s);
+        printf("%d frames of %dx%d at %d samples per pixel with %d materials%s in %.3f s (%.1f fps incl. readback)\n", frames, opt.width, opt.height, spp,
+               (int)materials.size(), nested ? " (nested media)" : "", s, frames / s);
     else if (frames && have_lens)
         printf("%d frames of %dx%d at %d samples per pixel through a lens of radius %g focused at %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, lens_radius, lens_focus, s, frames / s);

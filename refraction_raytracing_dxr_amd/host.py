@@ -672,6 +672,46 @@ class Renderer:
             self._ck(self._L.rr_render_materials(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_materials")
         return _result(outs)
 
+    def shade_rays_nested(self, rays, params=None, rgba8=False, ray_counts=False):
+        """shade_rays_materials for instances inside, or overlapping, other instances (rr_shade_rays_nested): the same rays, table,
+        outputs and stream order, but every ray carries the list of the media it is in (NESTED_MAX_MEDIA at most, empty = air) and
+        sees both faces of every triangle.  A front face enters the hit instance's material, a back face leaves it; a surface between
+        two different media refracts with ior_from / ior_to, a surface inside one medium is passed straight on; absorption is that of
+        the medium crossed.  On closed, consistently wound, pairwise disjoint instances this is shade_rays_materials byte for byte.
+        Every instance's row must be <= NESTED_MAX_MATERIAL.  params.ior is ignored."""
+        p = params if params is not None else default_params()
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("shade_rays_nested: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("shade_rays_nested: need a contiguous [n, 12] int32 or float32 tensor")
+            n = t.shape[0]
+            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
+            self._ck(self._L.rr_shade_rays_nested_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
+                     "rr_shade_rays_nested_device")
+        else:
+            rays = np.ascontiguousarray(rays, RAY_DTYPE)
+            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
+            self._ck(self._L.rr_shade_rays_nested(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_nested")
+        return _result(outs)
+
+    def render_nested(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
+        """render_materials with the ray tree of shade_rays_nested (rr_render_nested): the same arguments, samples, resolve and
+        outputs, every sample shaded as shade_rays_nested shades camera_rays(camera, width, height, *offset_s)."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "render_nested: samples must be an int or an [S, 2] array")
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_nested: negative size")
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_nested_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested_device")
+        else:
+            self._ck(self._L.rr_render_nested(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested")
+        return _result(outs)
+
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):
         """Thin-lens frame (rr_render_lens): render_samples with a lens of finite aperture -- sample s of a pixel starts at lens
         offset s on a disk of lens.radius round the camera and passes through the point its sub-pixel position sees at

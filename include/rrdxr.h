@@ -655,6 +655,55 @@ int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, c
                              const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
                              void* d_rgba8, void* d_n_rays);
 
+/* ---- composed frames: a lens and dispersion on the nested-media tree (present from ABI version 3) ---------------------------------
+ * One frame call that takes the primary rays of rr_render_lens, the ray tree of rr_render_nested and the weighted resolve of
+ * rr_render_spectral, with dispersion per material instead of per frame: the glass of water with an ice cube, photographed with
+ * depth of field and colour fringes.
+ *
+ * The band set.  rr_set_material_bands gives the context n_bands variants T_0 .. T_(n_bands-1) of the material table in force, n_rows
+ * rows each.  Row r of T_b is row r of the table with ior = iors[b * n_rows + r] (band-major) and the reciprocal 1.0f / ior that
+ * rr_set_materials would store for it; sigma_a is unchanged.  weights: n_bands x 3 floats, the weight of band b's colour per channel;
+ * NULL: all 1.  1 <= n_bands <= RR_MAX_SAMPLES, every ior finite and > 0, every weight finite (negative weights are allowed, as in
+ * rr_band): RR_ERR_INVALID_ARGUMENT otherwise, and the set in force stays.  RR_ERR_STATE when no table is set.  n_bands == 0 clears
+ * the set.  The context owns the copies; the call waits for the context's stream, like rr_set_materials.  rr_set_materials clears
+ * the set, because the row count may have changed.  Without a set there is exactly one band, band 0: the table in force with
+ * weights 1.  Only the two calls below read the set.
+ *
+ * The frame.  Sample k of a pixel has the sub-pixel position samples[k].offset (as rr_render_samples' offsets, each in [0, 1]), the
+ * lens offset samples[k].lens_offset (as rr_render_lens' lens offsets, each in [-1, 1]) and the band samples[k].band, which must be
+ * below the number of bands in force; pad is ignored.  Let c_k be what rr_shade_rays_nested returns for the rays of
+ * rr_host_lens_rays(constants, width, height, offset_k, lens_offset_k, lens) with T_(band_k) as the table in force; with lens ==
+ * NULL or radius == 0 the rays are those of rr_host_camera_rays(constants, width, height, offset_k) and the lens offsets are not
+ * looked at.  Channel ch of the pixel resolves in fp32, one rounding per operation and nothing fused, by rr_render_spectral's rule:
+ *   p_k = weights[band_k][ch] * c_k[ch]
+ *   sum = p_0, then sum = sum + p_k in sample order
+ *   out = sum / (float)n_samples
+ * and n_rays[i] is the sum of the samples' TraceRay counts.  Consequences, all byte for byte in colours, RGBA8 and counts:
+ *   - no lens, band 0 throughout and no band set (or a one-band set that repeats the table, weights 1): rr_render_nested with the
+ *     same offsets;
+ *   - one closed convex instance of row { ior, 0, 0, 0 }, no band set, a lens: rr_render_lens under params->ior = ior;
+ *   - the same scene, no lens, a band set made from rr_host_spectral_bands(B, ior, abbe): rr_render_spectral with that band table
+ *     in the same sample order.
+ * The last two hold where culled and unculled TraceRay agree for every ray used, as the reduction of the nested calls does.
+ *
+ * samples: host array of n_samples records, not NULL; 1 <= n_samples <= RR_MAX_SAMPLES.  lens: NULL for a pinhole, else validated as
+ * by rr_render_lens.  A lens disk must lie outside every instance: the rays start in air (the nested calls do not cover a start
+ * inside a medium).  Blocks of 8 x 8 pixels outside rr_host_lens_screen_rect of the scene (lens == NULL: rr_host_screen_rect) are
+ * shaded as one Miss per sample on that sample's own direction, counted as one ray and weighted like any other sample;
+ * RR_DISPATCH_DEBUG_NO_CULL traces them, with the same output.  State and parameters as rr_render_nested[_device]: RR_ERR_STATE
+ * without a built TLAS or without a table, the same checks of the instances' rows, params->ior ignored, not a dispatch,
+ * rr_set_tile_partition ignored; outputs, tone mapping and alignment rules as rr_render_samples[_device].  The _device variant is
+ * stream-ordered on the context's stream and neither synchronises nor allocates: the band set is already on the device.
+ * Only the nested tree is offered: on closed, pairwise disjoint instances it is the material tree byte for byte. */
+typedef struct rr_composed_sample { float offset[2]; float lens_offset[2]; uint32_t band; uint32_t pad[3]; } rr_composed_sample; /* 32 bytes */
+int  rr_set_material_bands(rr_context* ctx, const float* iors, const float* weights, uint32_t n_bands);
+int  rr_render_composed(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                        const rr_dispatch_params* params, const rr_composed_sample* samples, uint32_t n_samples, const rr_lens* lens,
+                        float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_composed_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                               const rr_dispatch_params* params, const rr_composed_sample* samples, uint32_t n_samples,
+                               const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */

@@ -58,6 +58,9 @@ assert BAND_DTYPE.itemsize == 16
 # rr_material: one row of the material table (set_materials) -- index of refraction, absorption per unit length for R, G, B
 MATERIAL_DTYPE = np.dtype([("ior", "<f4"), ("sigma_a", "<f4", 3)])
 assert MATERIAL_DTYPE.itemsize == 16
+# rr_composed_sample: one sample of render_composed -- sub-pixel position, lens offset, band of the context's band set
+COMPOSED_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("pad", "<u4", 3)])
+assert COMPOSED_SAMPLE_DTYPE.itemsize == 32
 
 
 class SceneConstants(C.Structure):
@@ -187,6 +190,11 @@ SYMBOLS = {
     "rr_shade_rays_nested_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
     "rr_render_nested": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
     "rr_render_nested_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_set_material_bands": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "rr_render_composed": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                     C.POINTER(Lens), _P, _P, _P]),
+    "rr_render_composed_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                            C.POINTER(Lens), _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -3,6 +3,7 @@
 // acceleration structures, then per frame: camera constants, DispatchRays, copy out, wait.
 #include "RefractionDemo.hpp"
 
+#include <cstdio>
 #include <cstring>
 
 namespace RefractionDemo {
@@ -16,6 +17,7 @@ bool g_back_pinned = false;
 std::string g_err;
 void* g_comm = nullptr;                      // RCCL communicator of the sharded form
 int g_rank = 0, g_world = 1;
+std::vector<rr_material> g_mats;             // the table of setMaterials: drawFrameComposed derives its band set from it
 
 int fail(int code, const char* what)
 {
@@ -134,7 +136,9 @@ int setMaterials(const rr_material* mats, int n)
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
     if (n <= 0 || !mats) return fail(RR_ERR_INVALID_ARGUMENT, "setMaterials: need at least one material");
     const int rc = rr_set_materials(g_ctx, mats, (uint32_t)n);
-    return rc == RR_OK ? RR_OK : fail(rc, "rr_set_materials");
+    if (rc != RR_OK) return fail(rc, "rr_set_materials");
+    g_mats.assign(mats, mats + n);
+    return RR_OK;
 }
 
 int drawFrameMaterials(int spp)
@@ -162,6 +166,49 @@ int drawFrameNested(int spp)
     if ((rc = rr_render_nested(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)spp, nullptr,
                                g_back.data(), nullptr)) != RR_OK)
         return fail(rc, "rr_render_nested");
+    return RR_OK;
+}
+
+int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (g_mats.empty()) return fail(RR_ERR_STATE, "drawFrameComposed: setMaterials first");
+    if (n_bands < 1) n_bands = 1;
+    if (spp <= 0 || spp * (long long)n_bands > RR_MAX_SAMPLES)
+        return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameComposed: spp must be 1, 2, 4, 8 or 16 and spp * bands at most 64");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    const int n = spp * n_bands, rows = (int)g_mats.size();
+    float pos[2 * RR_MAX_SAMPLES], lpos[2 * RR_MAX_SAMPLES];
+    rr_band one[RR_MAX_SAMPLES];
+    if ((rc = rr_host_sample_pattern((uint32_t)spp, pos)) != RR_OK) return fail(rc, "rr_host_sample_pattern");
+    if ((rc = rr_host_lens_pattern((uint32_t)n, lpos)) != RR_OK) return fail(rc, "rr_host_lens_pattern");
+    // the band set: every row's index spread by Cauchy's law through its own value; the weights are the same for every row
+    std::vector<float> iors((size_t)n_bands * rows), weights((size_t)n_bands * 3);
+    for (int r = 0; r < rows; ++r) {
+        if ((rc = rr_host_spectral_bands((uint32_t)n_bands, g_mats[r].ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
+        for (int b = 0; b < n_bands; ++b) {
+            iors[(size_t)b * rows + r] = one[b].ior;
+            for (int ch = 0; ch < 3; ++ch) weights[(size_t)b * 3 + ch] = one[b].weight[ch];
+        }
+    }
+    if ((rc = rr_set_material_bands(g_ctx, iors.data(), weights.data(), (uint32_t)n_bands)) != RR_OK) return fail(rc, "rr_set_material_bands");
+    g_angle += g_opt.angle_step;
+    rr_composed_sample samples[RR_MAX_SAMPLES];
+    memset(samples, 0, sizeof samples);
+    for (int a = 0; a < spp; ++a)
+        for (int b = 0; b < n_bands; ++b) {                     // sample a * n_bands + b: position a in band b, lens point a * n_bands + b
+            rr_composed_sample& k = samples[a * n_bands + b];
+            k.offset[0] = pos[2 * a]; k.offset[1] = pos[2 * a + 1];
+            k.lens_offset[0] = lpos[2 * (a * n_bands + b)]; k.lens_offset[1] = lpos[2 * (a * n_bands + b) + 1];
+            k.band = (uint32_t)b;
+        }
+    if ((rc = rr_render_composed(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, samples, (uint32_t)n, lens, nullptr,
+                                 g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_composed");
+    printf("composed frame: %d positions x %d bands (Abbe number %g) of %d materials, %s, nested media\n", spp, n_bands, abbe, rows,
+           lens && lens->radius > 0.0f ? "thin lens" : "pinhole");
     return RR_OK;
 }
 
@@ -306,6 +353,7 @@ void shutdown()
         if (g_back_pinned) { rr_host_unregister(g_ctx, g_back.data()); g_back_pinned = false; }
         rr_destroy(g_ctx); g_ctx = nullptr;
     }
+    g_mats.clear();
 }
 
 } // namespace RefractionDemo

@@ -42,6 +42,12 @@ int setMaterials(const rr_material* mats, int n);
 int drawFrameMaterials(int spp);
 // drawFrameMaterials with the nested-media ray tree (rr_render_nested): instances may sit inside, or overlap, other instances
 int drawFrameNested(int spp);
+// drawFrameNested composed with a lens and dispersion per material (rr_render_composed): the spp built-in positions crossed with
+// n_bands bands, sample a * n_bands + b being position a in band b, each sample with the lens point of rr_host_lens_pattern(spp *
+// n_bands); lens may be null (a pinhole).  The band set (rr_set_material_bands) gives every row of the table of setMaterials the
+// indices of rr_host_spectral_bands(n_bands, its own ior, abbe) and every band that table's weights; n_bands <= 1: no dispersion.
+// Prints one line that names the composition
+int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_material_bands, rr_render_composed*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -318,6 +318,57 @@ int nested_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, 
         return fail(ctx, RR_ERR_DEVICE, q.who, e);
     return RR_OK;
 }
+
+// a composed frame: a nested frame whose samples each have a lens offset and a band of the context's band set; lens may be null
+// (a pinhole).  s.offsets is not the caller's: check_composed points it at the sub-pixel positions it takes from the samples
+struct ComposedReq { SamplesReq s; const rr_composed_sample* samples; const rr_lens* lens; };
+struct ComposedTables { SampleOffsets off, loff; LensDev lens; SampleBands band; float pos[2 * RR_MAX_SAMPLES]; };
+
+// what both variants of rr_render_composed refuse before they look at their outputs' memory or allocate anything: what
+// rr_render_nested refuses (p: its check_nested result, which q.s.params points at), then the lens and its offsets as
+// rr_render_lens (a pinhole looks at no lens offset), then the bands; fills the tables
+int check_composed(rr_context* ctx, ComposedReq& q, rr_dispatch_params& p, bool have_colour, ComposedTables& t)
+{
+    const std::string w(q.s.who);
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (w + ": build the BLAS and TLAS first").c_str());
+    if (int r = check_nested(ctx, q.s.who, p)) return r;
+    if (!q.samples) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null samples").c_str());
+    if (q.s.n_samples == 0 || q.s.n_samples > RR_MAX_SAMPLES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need 1 <= n_samples <= 64").c_str());
+    for (uint32_t k = 0; k < q.s.n_samples; ++k) { t.pos[2 * k] = q.samples[k].offset[0]; t.pos[2 * k + 1] = q.samples[k].offset[1]; }
+    q.s.offsets = t.pos;
+    if (int r = check_samples(ctx, q.s, have_colour, t.off)) return r;
+    memset(&t.loff, 0, sizeof t.loff);
+    memset(&t.lens, 0, sizeof t.lens);
+    t.lens.pinhole = 1u;
+    if (q.lens && lens_setup(q.s.constants, q.lens, &t.lens))
+        return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need a finite radius >= 0, a finite focus_distance > 0 and proj_inv columns of finite non-zero length").c_str());
+    const uint32_t n_bands = ctx->n_bands ? ctx->n_bands : 1u;
+    memset(&t.band, 0, sizeof t.band);
+    for (uint32_t k = 0; k < q.s.n_samples; ++k) {
+        const rr_composed_sample& c = q.samples[k];
+        if (!t.lens.pinhole) for (int i = 0; i < 2; ++i) {
+            if (!(c.lens_offset[i] >= -1.0f && c.lens_offset[i] <= 1.0f))       // (NaN fails both comparisons)
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": lens offsets must lie in [-1, 1]").c_str());
+            t.loff.v[2 * k + i] = c.lens_offset[i];
+        }
+        if (c.band >= n_bands) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a sample's band is not below the number of bands in force (1 without rr_set_material_bands)").c_str());
+        t.band.set(k, c.band);                                  // (n_bands <= 64: a byte)
+    }
+    return RR_OK;
+}
+
+// launches a checked composed frame: out holds device pointers.  As nested_impl: nothing of the context but its error text,
+// nothing allocated, copied or waited for -- the band set, or the table in force and the weights 1 in its place, is on the device
+int composed_impl(rr_context* ctx, const ComposedReq& q, const ComposedTables& t, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q.s, q.lens);
+    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
+    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
+    if (hipError_t e = launch_render_composed(f.sc, f.a, f.cam, t.off, t.loff, t.lens, t.band, mats, ctx->n_mats, weights, inst0_material(ctx),
+                                              q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
+    return RR_OK;
+}
 } // namespace
 
 extern "C" {
@@ -564,7 +615,7 @@ float rr_host_expf_neg(float x) { return rr_expf_neg(x); }
 int rr_set_materials(rr_context* ctx, const rr_material* mats, uint32_t n)
 {
     if (int r = use_device(ctx)) return r;
-    if (n == 0) { ctx->n_mats = 0; return RR_OK; }
+    if (n == 0) { ctx->n_mats = 0; ctx->n_bands = 0; return RR_OK; }
     if (!mats) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: null table");
     if (n > 0x1000000u) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_materials: a hit-group index has 24 bits, so at most 16 777 216 materials");
     std::vector<MatDev> rows(n);
@@ -582,13 +633,59 @@ int rr_set_materials(rr_context* ctx, const rr_material* mats, uint32_t n)
     }
     // the old table stays in force until the new one is whole: launches in flight on the stream read it, and the copy is ordered
     // behind them (grow waits for the stream before it lets the old buffer go)
+    // a band set (rr_set_material_bands) was made from the old table, whose row count may differ: it goes with it.  What
+    // rr_render_composed weights its one band with while no set is in force is made here, with the first table: its launch
+    // allocates nothing
+    ctx->n_bands = 0;
     if (n > ctx->d_mats.size()) {
         ctx->n_mats = 0;
         if (int r = ctx->d_mats.grow(ctx, n)) return r;
     }
+    if (!ctx->d_band_one.size()) {
+        static const float one[3] = { 1.0f, 1.0f, 1.0f };
+        RR_HIP(ctx->d_band_one.alloc(3));
+        RR_HIP(hipMemcpyAsync(ctx->d_band_one.get(), one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    }
     RR_HIP(hipMemcpyAsync(ctx->d_mats.get(), rows.data(), (size_t)n * sizeof(MatDev), hipMemcpyHostToDevice, ctx->stream));
     RR_HIP(hipStreamSynchronize(ctx->stream));   // (rows goes away with this call)
+    ctx->mats_host.swap(rows);
     ctx->n_mats = n;
+    return RR_OK;
+}
+
+int rr_set_material_bands(rr_context* ctx, const float* iors, const float* weights, uint32_t n_bands)
+{
+    if (int r = use_device(ctx)) return r;
+    if (n_bands == 0) { ctx->n_bands = 0; return RR_OK; }
+    if (!ctx->n_mats) return fail(ctx, RR_ERR_STATE, "rr_set_material_bands: set a material table first (rr_set_materials)");
+    if (!iors) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_material_bands: null iors");
+    if (n_bands > RR_MAX_SAMPLES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_material_bands: need n_bands <= 64");
+    const uint32_t n_rows = ctx->n_mats;
+    const size_t n = (size_t)n_bands * n_rows;
+    std::vector<MatDev> rows(n);
+    std::vector<float> w((size_t)n_bands * 3, 1.0f);
+    for (size_t i = 0; i < n; ++i) {                            // band i / n_rows, row i % n_rows: the table's row with the band's index
+        if (!std::isfinite(iors[i]) || !(iors[i] > 0.0f)) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_material_bands: every ior must be finite and > 0");
+        rows[i] = ctx->mats_host[i % n_rows];
+        rows[i].ior = iors[i]; rows[i].inv_ior = inv_ior_of(iors[i]);
+    }
+    if (weights) for (size_t i = 0; i < w.size(); ++i) {
+        if (!std::isfinite(weights[i])) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_material_bands: every weight must be finite");
+        w[i] = weights[i];
+    }
+    // as rr_set_materials: the set in force stays until the new one is whole, and the copies are ordered behind what is in flight
+    if (n > ctx->d_band_mats.size()) {
+        ctx->n_bands = 0;
+        if (int r = ctx->d_band_mats.grow(ctx, n)) return r;
+    }
+    if (w.size() > ctx->d_band_w.size()) {
+        ctx->n_bands = 0;
+        if (int r = ctx->d_band_w.grow(ctx, w.size())) return r;
+    }
+    RR_HIP(hipMemcpyAsync(ctx->d_band_mats.get(), rows.data(), n * sizeof(MatDev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipMemcpyAsync(ctx->d_band_w.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));   // (rows and w go away with this call)
+    ctx->n_bands = n_bands;
     return RR_OK;
 }
 
@@ -722,6 +819,35 @@ int rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, co
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_nested_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return nested_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_composed(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                       const rr_composed_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    ComposedReq q = { { "rr_render_composed", width, height, constants, &p, nullptr, n_samples }, samples, lens };
+    ComposedTables t;
+    if (int r = check_composed(ctx, q, p, rgba32f || rgba8, t)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = composed_impl(ctx, q, t, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_composed_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                              const rr_composed_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
+                              void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    ComposedReq q = { { "rr_render_composed_device", width, height, constants, &p, nullptr, n_samples }, samples, lens };
+    ComposedTables t;
+    if (int r = check_composed(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_composed_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return composed_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

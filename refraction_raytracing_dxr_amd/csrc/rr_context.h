@@ -237,6 +237,14 @@ struct rr_context {
     // hit-group index (hitgroup_flags & 0xffffff) among the instances of the current TLAS
     DevBuf<MatDev>     d_mats;
     uint32_t n_mats = 0, max_material = 0;
+    // the band set of rr_render_composed (rr_set_material_bands): n_bands copies of the table in force, each with a column of
+    // indices of its own, one behind the other at the head of d_band_mats, and three weights per band at the head of d_band_w;
+    // n_bands == 0: none set, the one band is d_mats itself with the weights of d_band_one (1, 1, 1; made with the first table).
+    // mats_host: the rows of d_mats, which a band set is made from
+    std::vector<MatDev> mats_host;
+    DevBuf<MatDev>     d_band_mats;
+    DevBuf<float>      d_band_w, d_band_one;
+    uint32_t n_bands = 0;
 };
 
 namespace rr {

@@ -90,6 +90,20 @@ hipError_t launch_shade_rays_nested(const SceneDev& sc, const DispatchDev& a, co
 hipError_t launch_render_nested(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
                                 uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
                                 bool stack16, hipStream_t s);
+// ---- rr_render_composed.hip: composed frames (rr_render_composed[_device]): launch_render_nested with launch_render_lens' primary
+// rays (off, loff, lens; a.hx0..hy1 the lens rectangle, or the pinhole's when lens.pinhole) and launch_render_spectral's resolve.
+// Sample k is shaded under the table band_mats + b_k * n_rows (the context's band set: the bands' tables one behind the other,
+// every b_k below their number -- the host checks) and weighted with band_w[3 * b_k + channel]; band_mats and band_w are device
+// memory.  The band indices travel as a kernel argument beside the two offset tables, a byte each: b_k is byte k & 3 of
+// w[k >> 2], least significant first, so that a scalar load fetches it; 64 bytes
+struct SampleBands {
+    uint32_t w[SampleOffsets::MAX / 4];
+    void set(uint32_t k, uint32_t band) { w[k >> 2] = (w[k >> 2] & ~(0xffu << ((k & 3u) * 8u))) | ((band & 0xffu) << ((k & 3u) * 8u)); }
+};
+hipError_t launch_render_composed(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
+                                  const LensDev& lens, const SampleBands& band, const MatDev* band_mats, uint32_t n_rows, const float* band_w,
+                                  uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
+                                  bool stack16, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

@@ -9,6 +9,7 @@
 //          [--dispersion BANDS[:ABBE]]                             (with --spp N, default 1: N positions x BANDS bands of the Abbe number, default 30)
 //          [--materials "IOR:R,G,B;IOR:R,G,B;..."]                 (with --spp N, default 1: a material table, absorption per unit length; instance i is made of row i modulo the rows)
 //          [--nested]                                              (with --materials: the nested-media ray tree, rr_render_nested)
+//          [--compose]                                             (with --spp N and --materials: --lens, --dispersion and --nested together, rr_render_composed; the Abbe number applies to every row)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cstdio>
@@ -74,7 +75,7 @@ int main(int argc, char** argv)
     RefractionDemo::Options opt;
     int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0;
     float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f;
-    bool have_lens = false, pump = false, stream = false, nested = false;
+    bool have_lens = false, pump = false, stream = false, nested = false, compose = false;
     std::vector<rr_material> materials;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
@@ -86,6 +87,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--pump")) pump = true;
         else if (!strcmp(argv[i], "--stream")) stream = true;
         else if (!strcmp(argv[i], "--nested")) nested = true;
+        else if (!strcmp(argv[i], "--compose")) compose = true;
         else if (arg("--frames-per-dispatch")) fpd = atoi(argv[++i]);
         else if (arg("--in-flight")) in_flight = atoi(argv[++i]);
         else if (arg("--spp")) {
@@ -124,19 +126,24 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]] [--compose]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
+    if (compose) {          // the frames that refuse each other below, in one call: a lens and dispersion on the nested-media tree
+        if (!spp || materials.empty()) { fprintf(stderr, "--compose needs --spp N and --materials\n"); return 2; }
+        if (base || pump) { fprintf(stderr, "--compose cannot be combined with --adaptive or --pump\n"); return 2; }
+        if ((long long)spp * (n_bands ? n_bands : 1) > 64) { fprintf(stderr, "--compose: --spp N times BANDS must not exceed 64 samples\n"); return 2; }
+    }
     if (base && (!spp || base > spp)) { fprintf(stderr, "--adaptive BASE:THRESHOLD needs --spp N with BASE <= N\n"); return 2; }
     if (have_lens && (!spp || base)) { fprintf(stderr, "--lens RADIUS:FOCUS needs --spp N and cannot be combined with --adaptive\n"); return 2; }
     if (n_bands) {
-        if (base || have_lens) { fprintf(stderr, "--dispersion BANDS[:ABBE] cannot be combined with --adaptive or --lens\n"); return 2; }
+        if (!compose && (base || have_lens)) { fprintf(stderr, "--dispersion BANDS[:ABBE] cannot be combined with --adaptive or --lens\n"); return 2; }
         if (stream || pump || gpus > 0) { fprintf(stderr, "--dispersion renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
         if (!spp) spp = 1;
         if (spp < 0 || (long long)spp * n_bands > 64) { fprintf(stderr, "--dispersion: --spp N times BANDS must not exceed 64 samples\n"); return 2; }
     }
     if (!materials.empty()) {
-        if (base || have_lens || n_bands) { fprintf(stderr, "--materials cannot be combined with --adaptive, --lens or --dispersion\n"); return 2; }
+        if (!compose && (base || have_lens || n_bands)) { fprintf(stderr, "--materials cannot be combined with --adaptive, --lens or --dispersion\n"); return 2; }
         if (stream || pump || gpus > 0) { fprintf(stderr, "--materials renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
         if (!spp) spp = 1;
     }
@@ -237,7 +244,8 @@ int main(int argc, char** argv)
     uint64_t refined = 0;
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
-        rc = nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        const rr_lens lens = { lens_radius, lens_focus };
+        rc = compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -252,7 +260,10 @@ int main(int argc, char** argv)
         }
     }
     double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (frames && base)
+    if (frames && compose)
+        printf("%d composed frames of %dx%d at %d samples per pixel x %d bands with %d materials in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
+               opt.height, spp, n_bands ? n_bands : 1, (int)materials.size(), s, frames / s);
+    else if (frames && base)
         printf("%d frames of %dx%d at %d to %d samples per pixel (threshold %g) in %.3f s (%.1f fps incl. readback); %.2f %% of the pixels refined\n", frames,
                opt.width, opt.height, base, spp, threshold, s, frames / s, 100.0 * (double)refined / ((double)frames * opt.width * opt.height));
     else if (frames && n_bands)

@@ -93,6 +93,20 @@ def spectral_bands(n, ior_d=1.3, abbe=30.0):
     return out
 
 
+def material_bands(table, abbe=30.0, n=8):
+    """-> (iors float32 [n, rows], weights float32 [n, 3]): a band set for Renderer.set_material_bands -- dispersion per material.
+    Column r of iors is spectral_bands(n, table[r].ior, abbe_r)["ior"]: Cauchy's law through the row's own index.  abbe: one Abbe
+    number for every row or one per row; inf gives that row no dispersion.  The weights are those of spectral_bands(n): they
+    do not depend on the row.  table: a MATERIAL_DTYPE array or rows of (ior, (sigma_r, sigma_g, sigma_b))."""
+    t = np.ascontiguousarray(table, MATERIAL_DTYPE).reshape(-1)
+    ab = np.broadcast_to(np.asarray(abbe, np.float64), (len(t),))
+    n = int(n)
+    iors = np.zeros((max(n, 1), len(t)), np.float32)
+    for r in range(len(t)):
+        iors[:, r] = spectral_bands(n, t["ior"][r], float(ab[r]))["ior"]
+    return iors, np.ascontiguousarray(spectral_bands(n)["weight"], np.float32)
+
+
 def camera_rays(camera, w, h, ox=0.5, oy=0.5, tmin=1e-4, tmax=100.0):
     """-> RAY_DTYPE [w * h], row-major: the primary ray of every pixel of a w x h frame through the sub-pixel position (ox, oy)
     (pixel units, in [0, 1]) -- with the default, the pixel centre, the rays of a dispatch; what render_samples traces for
@@ -633,6 +647,7 @@ class Renderer:
         render_materials without a rebuild."""
         t = np.zeros(0, MATERIAL_DTYPE) if table is None else np.ascontiguousarray(table, MATERIAL_DTYPE).reshape(-1)
         self._ck(self._L.rr_set_materials(self._h, t.ctypes.data if len(t) else None, len(t)), "rr_set_materials")
+        self._n_materials = len(t)
 
     def shade_rays_materials(self, rays, params=None, rgba8=False, ray_counts=False):
         """shade_rays with the material table (rr_shade_rays_materials): the same rays, outputs and stream order, shaded by the ray
@@ -710,6 +725,84 @@ class Renderer:
             self._ck(self._L.rr_render_nested_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested_device")
         else:
             self._ck(self._L.rr_render_nested(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested")
+        return _result(outs)
+
+    def set_material_bands(self, iors, weights=None):
+        """The band set of render_composed (rr_set_material_bands): iors is a float32 [B, rows] array, row b the indices of
+        refraction that the rows of the material table in force take in band b (material_bands makes one); weights a float32 [B, 3]
+        array, the weight of band b's colour per channel (None: all 1; negative weights allowed).  Copied.  None or an empty array
+        clears the set; so does set_materials.  Without a set there is one band, band 0: the table itself, weights 1."""
+        if iors is None or np.size(iors) == 0:
+            self._ck(self._L.rr_set_material_bands(self._h, None, None, 0), "rr_set_material_bands")
+            return
+        t = np.ascontiguousarray(iors, np.float32)
+        if t.ndim != 2:
+            raise ValueError("set_material_bands: iors must be a [B, rows] array")
+        wp = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float32)
+            if w.shape != (t.shape[0], 3):
+                raise ValueError("set_material_bands: weights must be a [B, 3] array with one row per band")
+            wp = w.ctypes.data_as(C.c_void_p)
+        rows = getattr(self, "_n_materials", 0)                 # (no table: the library says so)
+        if rows and t.shape[1] != rows:
+            raise ValueError("set_material_bands: iors needs one column per row of the material table (%d)" % rows)
+        self._ck(self._L.rr_set_material_bands(self._h, t.ctypes.data_as(C.c_void_p), wp, t.shape[0]), "rr_set_material_bands")
+
+    def render_composed(self, width, height, camera, samples=4, lens=None, lens_samples=None, bands=None, paired=False, params=None, rgba8=False,
+                        ray_counts=False, device=False):
+        """Composed frame (rr_render_composed): render_nested with render_lens' primary rays and render_spectral's resolve over the
+        band set of set_material_bands.  Sample k starts at lens offset k of the lens (None or radius 0: a pinhole), is shaded as
+        shade_rays_nested shades lens_rays(camera, width, height, *offset_k, *lens_offset_k, lens) under band band_k of the set, and
+        channel ch of the pixel is ((w[band_0] * c_0 + w[band_1] * c_1) + ...) / S in fp32, each product and sum rounded once.
+        samples: an int (1, 2, 4, 8, 16: sample_pattern), an [A, 2] array of offsets in [0, 1], or a COMPOSED_SAMPLE_DTYPE record
+        array, which is passed straight through (lens_samples, bands and paired must then be left alone).  bands: None for band 0
+        throughout; an int B crosses the A positions with bands 0 .. B-1, S = A * B <= 64, sample a * B + b being position a in
+        band b; with paired=True an [S] array of band indices, one per position.  lens_samples: None for lens_pattern(S), or an
+        [S, 2] array in [-1, 1], one row per sample after crossing.  Without a band set only band 0 exists.  A lens disk must lie
+        outside every instance.  The other arguments, the outputs and device=True as render_nested; not a dispatch either."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        if w < 0 or h < 0:
+            raise ValueError("render_composed: negative size")
+        if isinstance(samples, np.ndarray) and samples.dtype == _capi.COMPOSED_SAMPLE_DTYPE:
+            if lens_samples is not None or bands is not None or paired:
+                raise ValueError("render_composed: a record array of samples carries its own lens offsets and bands")
+            rec = np.ascontiguousarray(samples).reshape(-1)
+        else:
+            offp, n = _sample_offsets(samples, "render_composed: samples must be an int, an [S, 2] array or a COMPOSED_SAMPLE_DTYPE array")
+            pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
+            if bands is None:
+                if paired:
+                    raise ValueError("render_composed: paired=True needs an array of band indices")
+                idx = np.zeros(len(pos), np.uint32)
+            elif paired:
+                idx = np.ascontiguousarray(bands, np.int64).reshape(-1)
+                if len(idx) != len(pos) or (idx < 0).any():
+                    raise ValueError("render_composed: paired=True needs one band index >= 0 per sample")
+            else:
+                if not isinstance(bands, (int, np.integer)) or bands < 1:
+                    raise ValueError("render_composed: bands must be None, an int >= 1 or, with paired=True, an array of indices")
+                if len(pos) * int(bands) > _capi.MAX_SAMPLES:
+                    raise ValueError("render_composed: positions x bands must not exceed %d samples" % _capi.MAX_SAMPLES)
+                idx = np.tile(np.arange(int(bands)), len(pos))                      # sample a * B + b: position a, band b
+                pos = np.repeat(pos, int(bands), axis=0)
+            rec = np.zeros(len(pos), _capi.COMPOSED_SAMPLE_DTYPE)
+            rec["offset"], rec["band"] = pos, idx
+            if lens_samples is not None:
+                loff = np.ascontiguousarray(lens_samples, np.float32)
+                if loff.shape != (len(rec), 2) or len(rec) == 0:
+                    raise ValueError("render_composed: lens_samples must be an [S, 2] array with one row per sample")
+                rec["lens_offset"] = loff
+            elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
+                rec["lens_offset"] = lens_pattern(len(rec))
+        recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
+        lp = C.byref(lens) if lens is not None else None
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_composed_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed_device")
+        else:
+            self._ck(self._L.rr_render_composed(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed")
         return _result(outs)
 
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):

@@ -704,6 +704,54 @@ int  rr_render_composed_device(rr_context* ctx, uint32_t width, uint32_t height,
                                const rr_dispatch_params* params, const rr_composed_sample* samples, uint32_t n_samples,
                                const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
+/* ---- shutter frames: motion blur over captured scene keys (present from ABI version 3) --------------------------------------------
+ * Time as one more sample dimension.  The context keeps up to RR_MAX_SCENE_KEYS frozen copies of the scene, "keys"; a shutter
+ * frame is a composed frame whose every sample also names the key it is traced in.
+ *
+ * Keys.  rr_capture_scene_key(ctx, key) freezes the scene that a render call issued at that point would trace: it copies the
+ * instance records, the flattened node pool and the triangle and normal pools (for a scene without a top level: the mesh's own
+ * nodes, triangles and normals) into buffers the key owns, device to device on the context's stream, so a capture right after
+ * rr_build_tlas_ex(.., RR_BUILD_PERFORM_UPDATE) sees that update; nothing is waited for unless a buffer of the key must grow.
+ * RR_ERR_STATE where rr_render_nested would refuse the scene's state (no TLAS, or a BLAS rebuilt or updated since the TLAS);
+ * RR_ERR_INVALID_ARGUMENT for key >= RR_MAX_SCENE_KEYS; after RR_ERR_OUT_OF_MEMORY the key is empty.  Capturing into a used key
+ * replaces it and reuses its buffers where they are large enough.  The live scene is never touched, and no later build, refit,
+ * vertex update or new scene changes a key.  A key holds geometry and the instances' material rows, nothing else: the environment
+ * map, the material table and the band set are the context's at the time of the render call.
+ * rr_release_scene_key frees one key (RR_ALL_SCENE_KEYS: every key; an empty key is fine) after waiting for the context's stream.
+ * rr_scene_key_info: captured (0: everything else is 0), top_level (0: one identity instance, traced without a top level),
+ * instance and triangle counts, the world-space bounds (lo.xyz, hi.xyz), the deepest traversal stack the key can need, the largest
+ * material row among its instances, and the bytes of device memory it holds.
+ *
+ * The frame.  rr_render_shutter[_device] is rr_render_composed[_device] with one word added: sample k is shaded as
+ * rr_shade_rays_nested shades the rays of rr_host_lens_rays (without a lens: rr_host_camera_rays) in the scene of key samples[k].key
+ * under the band table samples[k].band, and the pixel resolves by the same rule, ((w_0 * c_0 + w_1 * c_1) + ...) / n_samples with
+ * every operation rounded once.  Outputs, tone mapping, ray counts, device pointers and their alignment as rr_render_composed.
+ * Refused as rr_render_composed refuses its arguments, and with RR_ERR_INVALID_ARGUMENT: a key >= RR_MAX_SCENE_KEYS or not
+ * captured; non-zero pad; keys of one frame that disagree on top_level; a key whose max_material is not below the rows of the
+ * table in force or is above RR_NESTED_MAX_MATERIAL.  The live scene need not be built: no key, no frame.  The camera and every
+ * lens point must lie outside every instance of every key used.  Blocks of 8 x 8 pixels outside the screen rectangle of the union
+ * of the used keys' bounds are one Miss per sample, as in rr_render_composed; RR_DISPATCH_DEBUG_NO_CULL traces them.  Nothing is
+ * allocated, copied or waited for by the _device variant.
+ * Not covered: a camera per key, interpolation between keys, more than RR_MAX_SAMPLES samples. */
+#define RR_MAX_SCENE_KEYS 16
+#define RR_ALL_SCENE_KEYS 0xffffffffu
+struct rr_scene_key_info {              /* a tag only: the call below has the name, so write `struct rr_scene_key_info` */
+    uint32_t captured, top_level, n_instances, n_triangles;
+    float    bounds[6];
+    uint32_t stack_need, max_material;
+    uint64_t bytes;
+};
+typedef struct rr_shutter_sample { float offset[2]; float lens_offset[2]; uint32_t band; uint32_t key; uint32_t pad[2]; } rr_shutter_sample; /* 32 bytes */
+int  rr_capture_scene_key(rr_context* ctx, uint32_t key);
+int  rr_release_scene_key(rr_context* ctx, uint32_t key);
+int  rr_scene_key_info(rr_context* ctx, uint32_t key, struct rr_scene_key_info* out);
+int  rr_render_shutter(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                       const rr_dispatch_params* params, const rr_shutter_sample* samples, uint32_t n_samples, const rr_lens* lens,
+                       float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                              const rr_dispatch_params* params, const rr_shutter_sample* samples, uint32_t n_samples,
+                              const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel
  * address and the zero returned outside the texture (reached at atan2 = pi and at r.y = -1); used by the parity tests. */

@@ -61,6 +61,11 @@ assert MATERIAL_DTYPE.itemsize == 16
 # rr_composed_sample: one sample of render_composed -- sub-pixel position, lens offset, band of the context's band set
 COMPOSED_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("pad", "<u4", 3)])
 assert COMPOSED_SAMPLE_DTYPE.itemsize == 32
+# rr_shutter_sample: one sample of render_shutter -- a composed sample and the scene key it is traced in
+SHUTTER_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("key", "<u4"), ("pad", "<u4", 2)])
+assert SHUTTER_SAMPLE_DTYPE.itemsize == 32
+MAX_SCENE_KEYS = 16                      # RR_MAX_SCENE_KEYS: scene keys a context holds (capture_scene_key)
+ALL_SCENE_KEYS = 0xFFFFFFFF              # RR_ALL_SCENE_KEYS: release_scene_key's "every key"
 
 
 class SceneConstants(C.Structure):
@@ -94,6 +99,12 @@ class Stats(C.Structure):
     def clock_ghz(self):
         """shader clock of the COLLECT_STATS launches (s_memtime / s_memrealtime x 100 MHz), 0.0 without them"""
         return self.clock_ticks / self.clock_ref_ticks * 0.1 if self.clock_ref_ticks else 0.0
+
+
+class SceneKeyInfo(C.Structure):
+    """rr_scene_key_info: what a captured scene key holds (Renderer.scene_key_info)"""
+    _fields_ = [("captured", C.c_uint32), ("top_level", C.c_uint32), ("n_instances", C.c_uint32), ("n_triangles", C.c_uint32),
+                ("bounds", C.c_float * 6), ("stack_need", C.c_uint32), ("max_material", C.c_uint32), ("bytes", C.c_uint64)]
 
 
 class MeshPartition(C.Structure):
@@ -195,6 +206,13 @@ SYMBOLS = {
                                      C.POINTER(Lens), _P, _P, _P]),
     "rr_render_composed_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
                                             C.POINTER(Lens), _P, _P, _P]),
+    "rr_capture_scene_key": (C.c_int, [_P, C.c_uint32]),
+    "rr_release_scene_key": (C.c_int, [_P, C.c_uint32]),
+    "rr_scene_key_info": (C.c_int, [_P, C.c_uint32, C.POINTER(SceneKeyInfo)]),
+    "rr_render_shutter": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                    C.POINTER(Lens), _P, _P, _P]),
+    "rr_render_shutter_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                           C.POINTER(Lens), _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -3,6 +3,7 @@
 // acceleration structures, then per frame: camera constants, DispatchRays, copy out, wait.
 #include "RefractionDemo.hpp"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -18,6 +19,7 @@ std::string g_err;
 void* g_comm = nullptr;                      // RCCL communicator of the sharded form
 int g_rank = 0, g_world = 1;
 std::vector<rr_material> g_mats;             // the table of setMaterials: drawFrameComposed derives its band set from it
+bool g_shutter_tlas = false;                 // drawFrameShutter built the top level it updates per key
 
 int fail(int code, const char* what)
 {
@@ -32,6 +34,7 @@ int initialize(const Options& opt)
     shutdown();
     g_opt = opt;
     g_angle = opt.angle0;
+    g_shutter_tlas = false;
     int rc = rr_create(opt.device, &g_ctx);                               // createDevice :142-172
     if (rc != RR_OK) return fail(rc, "rr_create");
 
@@ -169,6 +172,25 @@ int drawFrameNested(int spp)
     return RR_OK;
 }
 
+// the band set of the composed and shutter frames: every row's index spread by Cauchy's law through its own value; the weights are
+// the same for every row
+static int setBandSet(int n_bands, float abbe)
+{
+    const int rows = (int)g_mats.size();
+    int rc;
+    rr_band one[RR_MAX_SAMPLES];
+    std::vector<float> iors((size_t)n_bands * rows), weights((size_t)n_bands * 3);
+    for (int r = 0; r < rows; ++r) {
+        if ((rc = rr_host_spectral_bands((uint32_t)n_bands, g_mats[r].ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
+        for (int b = 0; b < n_bands; ++b) {
+            iors[(size_t)b * rows + r] = one[b].ior;
+            for (int ch = 0; ch < 3; ++ch) weights[(size_t)b * 3 + ch] = one[b].weight[ch];
+        }
+    }
+    if ((rc = rr_set_material_bands(g_ctx, iors.data(), weights.data(), (uint32_t)n_bands)) != RR_OK) return fail(rc, "rr_set_material_bands");
+    return RR_OK;
+}
+
 int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe)
 {
     if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
@@ -181,19 +203,9 @@ int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe)
     if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
     const int n = spp * n_bands, rows = (int)g_mats.size();
     float pos[2 * RR_MAX_SAMPLES], lpos[2 * RR_MAX_SAMPLES];
-    rr_band one[RR_MAX_SAMPLES];
     if ((rc = rr_host_sample_pattern((uint32_t)spp, pos)) != RR_OK) return fail(rc, "rr_host_sample_pattern");
     if ((rc = rr_host_lens_pattern((uint32_t)n, lpos)) != RR_OK) return fail(rc, "rr_host_lens_pattern");
-    // the band set: every row's index spread by Cauchy's law through its own value; the weights are the same for every row
-    std::vector<float> iors((size_t)n_bands * rows), weights((size_t)n_bands * 3);
-    for (int r = 0; r < rows; ++r) {
-        if ((rc = rr_host_spectral_bands((uint32_t)n_bands, g_mats[r].ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
-        for (int b = 0; b < n_bands; ++b) {
-            iors[(size_t)b * rows + r] = one[b].ior;
-            for (int ch = 0; ch < 3; ++ch) weights[(size_t)b * 3 + ch] = one[b].weight[ch];
-        }
-    }
-    if ((rc = rr_set_material_bands(g_ctx, iors.data(), weights.data(), (uint32_t)n_bands)) != RR_OK) return fail(rc, "rr_set_material_bands");
+    if ((rc = setBandSet(n_bands, abbe)) != RR_OK) return rc;
     g_angle += g_opt.angle_step;
     rr_composed_sample samples[RR_MAX_SAMPLES];
     memset(samples, 0, sizeof samples);
@@ -209,6 +221,57 @@ int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe)
         return fail(rc, "rr_render_composed");
     printf("composed frame: %d positions x %d bands (Abbe number %g) of %d materials, %s, nested media\n", spp, n_bands, abbe, rows,
            lens && lens->radius > 0.0f ? "thin lens" : "pinhole");
+    return RR_OK;
+}
+
+int drawFrameShutter(int spp, const rr_lens* lens, int n_bands, float abbe, int n_keys, float dt)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (g_mats.empty()) return fail(RR_ERR_STATE, "drawFrameShutter: setMaterials first");
+    if (n_bands < 1) n_bands = 1;
+    if (spp <= 0 || n_keys < 1 || n_keys > RR_MAX_SCENE_KEYS || spp * (long long)n_keys * n_bands > RR_MAX_SAMPLES)
+        return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameShutter: spp must be 1, 2, 4, 8 or 16, keys 1 to 16 and spp * keys * bands at most 64");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    const int n = spp * n_keys * n_bands, rows = (int)g_mats.size();
+    float pos[2 * RR_MAX_SAMPLES], lpos[2 * RR_MAX_SAMPLES];
+    if ((rc = rr_host_sample_pattern((uint32_t)spp, pos)) != RR_OK) return fail(rc, "rr_host_sample_pattern");
+    if ((rc = rr_host_lens_pattern((uint32_t)n, lpos)) != RR_OK) return fail(rc, "rr_host_lens_pattern");
+    if ((rc = setBandSet(n_bands, abbe)) != RR_OK) return rc;
+    // The camera is what moves in this demo, and a shutter frame has one camera: seen from the camera at angle a, the scene at
+    // orbit angle a + d is the scene turned by -d about the y axis, so key j is the mesh under that turn (the environment map stays
+    // where it is).  The top level is built once with ALLOW_UPDATE and updated per key.  Every key needs a top level -- a frame
+    // cannot mix keys with and without one -- and the turn by 0 is the identity, which alone would be traced without: the instance
+    // carries TRIANGLE_CULL_DISABLE, which keeps the top level and changes nothing else, the nested tree seeing both faces anyway
+    const RaytracingGeometry geo = cubeMesh.raytracingGeometry();
+    for (int j = 0; j < n_keys; ++j) {
+        const float d = n_keys > 1 ? dt * (float)j / (float)(n_keys - 1) : 0.0f, c = std::cos(d), s = std::sin(d);
+        rr_instance_desc inst;
+        std::memset(&inst, 0, sizeof inst);
+        inst.transform[0] = c; inst.transform[2] = s; inst.transform[5] = 1.0f; inst.transform[8] = -s; inst.transform[10] = c;
+        inst.instance_id_mask = 1u << 24;
+        inst.hitgroup_flags = RR_INSTANCE_FLAG_TRIANGLE_CULL_DISABLE << 24;
+        inst.blas = geo.mesh_id;
+        if ((rc = rr_build_tlas_ex(g_ctx, &inst, 1, g_shutter_tlas ? RR_BUILD_PERFORM_UPDATE : RR_BUILD_ALLOW_UPDATE)) != RR_OK) return fail(rc, "rr_build_tlas_ex");
+        g_shutter_tlas = true;
+        if ((rc = rr_capture_scene_key(g_ctx, (uint32_t)j)) != RR_OK) return fail(rc, "rr_capture_scene_key");
+    }
+    g_angle += g_opt.angle_step;
+    rr_shutter_sample samples[RR_MAX_SAMPLES];
+    memset(samples, 0, sizeof samples);
+    for (int k = 0; k < n; ++k) {                               // sample (a * n_keys + j) * n_bands + b: position a, key j, band b, lens point k
+        const int a = k / (n_keys * n_bands);
+        samples[k].offset[0] = pos[2 * a]; samples[k].offset[1] = pos[2 * a + 1];
+        samples[k].lens_offset[0] = lpos[2 * k]; samples[k].lens_offset[1] = lpos[2 * k + 1];
+        samples[k].key = (uint32_t)(k / n_bands % n_keys);
+        samples[k].band = (uint32_t)(k % n_bands);
+    }
+    if ((rc = rr_render_shutter(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, samples, (uint32_t)n, lens, nullptr,
+                                g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_shutter");
+    printf("shutter frame: %d positions x %d keys over %g rad x %d bands (Abbe number %g) of %d materials, %s, nested media\n", spp, n_keys, dt, n_bands,
+           abbe, rows, lens && lens->radius > 0.0f ? "thin lens" : "pinhole");
     return RR_OK;
 }
 

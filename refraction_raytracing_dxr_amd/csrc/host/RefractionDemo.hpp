@@ -48,6 +48,12 @@ int drawFrameNested(int spp);
 // indices of rr_host_spectral_bands(n_bands, its own ior, abbe) and every band that table's weights; n_bands <= 1: no dispersion.
 // Prints one line that names the composition
 int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe);
+// drawFrameComposed with a shutter (rr_render_shutter): the scene at n_keys orbit angles, the frame's own and up to dt beyond it
+// (angle + j * dt / (n_keys - 1)), each captured as a scene key, and the spp positions crossed with the keys and the bands -- sample
+// (a * n_keys + j) * n_bands + b being position a in key j and band b; spp * n_keys * n_bands <= 64.  The camera is what orbits here,
+// so key j holds the mesh turned by the opposite angle about y under the frame's one camera; the environment map does not turn with
+// it.  From the first call on the scene has a top level (one instance, updated per key).  Prints one line that names the frame
+int drawFrameShutter(int spp, const rr_lens* lens, int n_bands, float abbe, int n_keys, float dt);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

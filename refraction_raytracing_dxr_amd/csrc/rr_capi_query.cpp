@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_material_bands, rr_render_composed*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -94,11 +94,11 @@ struct SamplesReq {
 };
 
 // what both variants of rr_render_samples refuse before they look at their outputs' memory or allocate anything (bounce limits
-// and ior included); fills the offsets
-int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, SampleOffsets& off)
+// and ior included); fills the offsets.  live: the frame traces the live scene, which must be built (a shutter frame traces keys)
+int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, SampleOffsets& off, bool live = true)
 {
     const std::string w(q.who);
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (w + ": build the BLAS and TLAS first").c_str());
+    if (live && !ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (w + ": build the BLAS and TLAS first").c_str());
     if (!q.constants) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null constants").c_str());
     if (q.width == 0 || q.height == 0 || q.width > 32768u || q.height > 32768u)
         return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": width and height must be 1..32768").c_str());
@@ -121,23 +121,30 @@ int check_samples(rr_context* ctx, const SamplesReq& q, bool have_colour, Sample
 // what the launch of a checked supersampled or adaptive frame takes: the scene, the frame's shading arguments with its screen
 // rectangle (lens: the rectangle of its whole disk, rr_host_lens_screen_rect), the camera and the scene's kernel variant
 struct FrameArgs { SceneDev sc; DispatchDev a; CamDev cam; FusedVariant v; };
-FrameArgs frame_args(rr_context* ctx, const SamplesReq& q, const rr_lens* lens = nullptr)
+// everything of FrameArgs but the scene, for what is traced having the world-space box `bounds` and the facts `sf`
+FrameArgs frame_args_of(rr_context* ctx, const SamplesReq& q, const rr_lens* lens, const float bounds[6], const SceneFacts& sf)
 {
     const rr_dispatch_params p = params_or_default(q.params);
     FrameArgs f;
-    fill_scene(ctx, f.sc);
+    memset(&f.sc, 0, sizeof f.sc);
     f.a = shading_args(p);
     f.a.W = q.width; f.a.H = q.height;
     f.a.tmin_p = p.tmin_primary; f.a.tmax_p = p.tmax_primary;
     uint32_t hr[4];
     const rr_scene_constants* const seen = (p.flags & RR_DISPATCH_DEBUG_NO_CULL) ? nullptr : q.constants;
-    if (lens) (void)rr_host_lens_screen_rect(ctx->scene_bounds, seen, lens, q.width, q.height, hr);
-    else (void)rr_host_screen_rect(ctx->scene_bounds, seen, 1, q.width, q.height, hr);
+    if (lens) (void)rr_host_lens_screen_rect(bounds, seen, lens, q.width, q.height, hr);
+    else (void)rr_host_screen_rect(bounds, seen, 1, q.width, q.height, hr);
     f.a.hx0 = hr[0]; f.a.hy0 = hr[1]; f.a.hx1 = hr[2]; f.a.hy1 = hr[3];
     memcpy(f.cam.M, q.constants->proj_inv, sizeof f.cam.M);
     memcpy(f.cam.cam, q.constants->camera_loc, sizeof f.cam.cam);
     // the kernel of a launch of many slices, as a radiance query's: S trees per lane, not a frame that ends on its longest wave
-    f.v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    f.v = fused_variant(sf, 64u, p.max_reflect, ctx->dbg);
+    return f;
+}
+FrameArgs frame_args(rr_context* ctx, const SamplesReq& q, const rr_lens* lens = nullptr)
+{
+    FrameArgs f = frame_args_of(ctx, q, lens, ctx->scene_bounds, scene_facts(ctx));
+    fill_scene(ctx, f.sc);
     return f;
 }
 
@@ -327,16 +334,15 @@ struct ComposedTables { SampleOffsets off, loff; LensDev lens; SampleBands band;
 // what both variants of rr_render_composed refuse before they look at their outputs' memory or allocate anything: what
 // rr_render_nested refuses (p: its check_nested result, which q.s.params points at), then the lens and its offsets as
 // rr_render_lens (a pinhole looks at no lens offset), then the bands; fills the tables
-int check_composed(rr_context* ctx, ComposedReq& q, rr_dispatch_params& p, bool have_colour, ComposedTables& t)
+// check_composed behind the scene's state: the samples, the lens and the bands (live: as check_samples)
+int check_composed_args(rr_context* ctx, ComposedReq& q, bool have_colour, ComposedTables& t, bool live)
 {
     const std::string w(q.s.who);
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (w + ": build the BLAS and TLAS first").c_str());
-    if (int r = check_nested(ctx, q.s.who, p)) return r;
     if (!q.samples) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null samples").c_str());
     if (q.s.n_samples == 0 || q.s.n_samples > RR_MAX_SAMPLES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need 1 <= n_samples <= 64").c_str());
     for (uint32_t k = 0; k < q.s.n_samples; ++k) { t.pos[2 * k] = q.samples[k].offset[0]; t.pos[2 * k + 1] = q.samples[k].offset[1]; }
     q.s.offsets = t.pos;
-    if (int r = check_samples(ctx, q.s, have_colour, t.off)) return r;
+    if (int r = check_samples(ctx, q.s, have_colour, t.off, live)) return r;
     memset(&t.loff, 0, sizeof t.loff);
     memset(&t.lens, 0, sizeof t.lens);
     t.lens.pinhole = 1u;
@@ -356,6 +362,12 @@ int check_composed(rr_context* ctx, ComposedReq& q, rr_dispatch_params& p, bool 
     }
     return RR_OK;
 }
+int check_composed(rr_context* ctx, ComposedReq& q, rr_dispatch_params& p, bool have_colour, ComposedTables& t)
+{
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, (std::string(q.s.who) + ": build the BLAS and TLAS first").c_str());
+    if (int r = check_nested(ctx, q.s.who, p)) return r;
+    return check_composed_args(ctx, q, have_colour, t, true);
+}
 
 // launches a checked composed frame: out holds device pointers.  As nested_impl: nothing of the context but its error text,
 // nothing allocated, copied or waited for -- the band set, or the table in force and the weights 1 in its place, is on the device
@@ -367,6 +379,76 @@ int composed_impl(rr_context* ctx, const ComposedReq& q, const ComposedTables& t
     if (hipError_t e = launch_render_composed(f.sc, f.a, f.cam, t.off, t.loff, t.lens, t.band, mats, ctx->n_mats, weights, inst0_material(ctx),
                                               q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
+    return RR_OK;
+}
+
+// a shutter frame: a composed frame whose samples each name a captured scene key.  c: the samples as composed records (what
+// check_composed_args reads), used: which keys the frame traces in
+struct ShutterReq { ComposedReq c; const rr_shutter_sample* samples; };
+struct ShutterTables { ComposedTables c; SampleKeys key; rr_composed_sample rec[RR_MAX_SAMPLES]; bool used[RR_MAX_SCENE_KEYS]; };
+
+// what both variants of rr_render_shutter refuse before they look at their outputs' memory: a missing table, what rr_render_composed
+// refuses of its arguments (the live scene's state is not looked at: the frame traces keys), then the keys; fills the tables
+int check_shutter(rr_context* ctx, ShutterReq& q, rr_dispatch_params& p, bool have_colour, ShutterTables& t)
+{
+    const std::string w(q.c.s.who);
+    if (!ctx->n_mats) return fail(ctx, RR_ERR_STATE, (w + ": set a material table first (rr_set_materials)").c_str());
+    p.ior = 1.0f;                                               // (not looked at, as check_materials has it)
+    if (!q.samples) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": null samples").c_str());
+    if (q.c.s.n_samples == 0 || q.c.s.n_samples > RR_MAX_SAMPLES) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": need 1 <= n_samples <= 64").c_str());
+    for (uint32_t k = 0; k < q.c.s.n_samples; ++k) {
+        const rr_shutter_sample& s = q.samples[k];
+        t.rec[k] = rr_composed_sample{ { s.offset[0], s.offset[1] }, { s.lens_offset[0], s.lens_offset[1] }, s.band, { 0u, 0u, 0u } };
+    }
+    q.c.samples = t.rec;
+    if (int r = check_composed_args(ctx, q.c, have_colour, t.c, false)) return r;
+    memset(&t.key, 0, sizeof t.key);
+    memset(t.used, 0, sizeof t.used);
+    const SceneKey* first = nullptr;
+    for (uint32_t k = 0; k < q.c.s.n_samples; ++k) {
+        const rr_shutter_sample& s = q.samples[k];
+        if (s.pad[0] || s.pad[1]) return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a sample's pad must be zero").c_str());
+        if (s.key >= RR_MAX_SCENE_KEYS || !ctx->keys[s.key].captured)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a sample's key is not a captured scene key (rr_capture_scene_key)").c_str());
+        const SceneKey& sk = ctx->keys[s.key];
+        if (!first) first = &sk;
+        if (sk.facts.single_identity != first->facts.single_identity)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": the keys of one frame must all have a top level or all be without one").c_str());
+        if (sk.max_material >= ctx->n_mats)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a key's hit-group index is not below the material table's length").c_str());
+        if (sk.max_material > RR_NESTED_MAX_MATERIAL)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a key's hit-group index is above RR_NESTED_MAX_MATERIAL (254)").c_str());
+        t.used[s.key] = true;
+        t.key.set(k, s.key);
+    }
+    return RR_OK;
+}
+
+// launches a checked shutter frame: out holds device pointers.  As composed_impl: nothing allocated, copied or waited for -- the
+// key records are on the device since their capture.  The rectangle is that of the union of the used keys' boxes; the kernel
+// variant comes from fused_variant over the used keys' facts merged: the deepest stack need, the largest mesh and pools (16-bit
+// stack entries only where every key's references fit them)
+int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, const ShadeOut& out)
+{
+    float box[6] = { 3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f };
+    SceneFacts sf = { false, 0, 0, 0, 0, false };
+    for (uint32_t k = 0; k < RR_MAX_SCENE_KEYS; ++k) {
+        if (!t.used[k]) continue;
+        const SceneKey& sk = ctx->keys[k];
+        for (int i = 0; i < 3; ++i) { box[i] = std::min(box[i], sk.bounds[i]); box[3 + i] = std::max(box[3 + i], sk.bounds[3 + i]); }
+        sf.single_identity = sk.facts.single_identity;          // (the same in every used key: check_shutter)
+        sf.need = std::max(sf.need, sk.facts.need);
+        sf.blas_tris = std::max(sf.blas_tris, sk.facts.blas_tris);
+        sf.pool_nodes = std::max(sf.pool_nodes, sk.facts.pool_nodes);
+        sf.pool_refs = std::max(sf.pool_refs, sk.facts.pool_refs);
+    }
+    const FrameArgs f = frame_args_of(ctx, q.c.s, q.c.lens, box, sf);
+    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
+    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
+    if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), sf.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, mats,
+                                             ctx->n_mats, weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out.f32, out.rgba8,
+                                             out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.c.s.who, e);
     return RR_OK;
 }
 } // namespace
@@ -848,6 +930,35 @@ int rr_render_composed_device(rr_context* ctx, uint32_t width, uint32_t height, 
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_composed_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return composed_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_shutter(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                      const rr_shutter_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    ShutterReq q = { { { "rr_render_shutter", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, samples };
+    ShutterTables t;
+    if (int r = check_shutter(ctx, q, p, rgba32f || rgba8, t)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = shutter_impl(ctx, q, t, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                             const rr_shutter_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
+                             void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    ShutterReq q = { { { "rr_render_shutter_device", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, samples };
+    ShutterTables t;
+    if (int r = check_shutter(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_shutter_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return shutter_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -117,6 +117,26 @@ struct StreamSet {
     DevBuf<uint8_t>  pending;        // one per pixel (allocated after slots: its size is the set's pixel count)
 };
 
+// One captured scene (rr_capture_scene_key): copies of everything fill_scene points a SceneDev at, in buffers the key owns, and
+// what the host needs of the scene when a shutter frame uses the key.  Buffers are kept when the key is captured again and only
+// grow; the record the kernel reads is slot `key` of rr_context::d_key_scenes
+struct SceneKey {
+    bool captured = false;
+    DevBuf<InstDev> insts;
+    DevBuf<QNode>   pool_qnodes, qnodes0;        // (qnodes0, tris0, nrms0: the mesh's own, for a scene without a top level)
+    DevBuf<TriRec>  pool_tris, tris0;
+    DevBuf<NrmRec>  pool_nrms, nrms0;
+    SceneFacts facts = { false, 0, 0, 0, 0, false };     // scene_facts at the capture
+    float    bounds[6] = { 0, 0, 0, 0, 0, 0 };           // scene_bounds
+    uint32_t n_insts = 0, n_tris = 0, max_material = 0, mat0 = 0;
+    uint64_t bytes() const
+    {
+        return insts.size() * sizeof(InstDev) + (pool_qnodes.size() + qnodes0.size()) * sizeof(QNode) +
+               (pool_tris.size() + tris0.size()) * sizeof(TriRec) + (pool_nrms.size() + nrms0.size()) * sizeof(NrmRec);
+    }
+    void release() { *this = SceneKey(); }
+};
+
 } // namespace rr
 
 using namespace rr;          // (every source that includes this is written in terms of rr's types, as rr_context is)
@@ -245,6 +265,12 @@ struct rr_context {
     DevBuf<MatDev>     d_band_mats;
     DevBuf<float>      d_band_w, d_band_one;
     uint32_t n_bands = 0;
+    // the scene keys of rr_render_shutter (rr_capture_scene_key) and their records as the kernel reads them: RR_MAX_SCENE_KEYS
+    // slots, allocated and zeroed at the first capture, slot k written when key k is captured.  key_host: the host copy a slot is
+    // written from (it outlives the copy)
+    SceneKey keys[RR_MAX_SCENE_KEYS];
+    DevBuf<KeyDev> d_key_scenes;
+    KeyDev key_host[RR_MAX_SCENE_KEYS] = {};
 };
 
 namespace rr {

@@ -104,6 +104,23 @@ hipError_t launch_render_composed(const SceneDev& sc, const DispatchDev& a, cons
                                   const LensDev& lens, const SampleBands& band, const MatDev* band_mats, uint32_t n_rows, const float* band_w,
                                   uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
                                   bool stack16, hipStream_t s);
+// ---- rr_render_shutter.hip: shutter frames (rr_render_shutter[_device]): launch_render_composed with the scene as one more
+// per-sample table entry.  keys: the context's RR_MAX_SCENE_KEYS records in device memory, written at rr_capture_scene_key; sample k
+// is traced in keys[key_k].sc with keys[key_k].mat0 -- every key_k captured and of the same kind (single_identity: all without a
+// top level, else all with one), and stack, pend, stack16 valid for every key used: the host checks.  A record's env fields are
+// never read: the environment map is the context's at the launch and travels as env, env_w, env_h.  The key indices travel like
+// the band indices, a byte each, four to a word; 64 bytes
+struct KeyDev { SceneDev sc; uint32_t mat0; uint32_t pad; };
+static_assert(sizeof(KeyDev) % 16 == 0, "KeyDev: a multiple of 16 bytes");
+struct SampleKeys {
+    uint32_t w[SampleOffsets::MAX / 4];
+    void set(uint32_t k, uint32_t key) { w[k >> 2] = (w[k >> 2] & ~(0xffu << ((k & 3u) * 8u))) | ((key & 0xffu) << ((k & 3u) * 8u)); }
+};
+hipError_t launch_render_shutter(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
+                                 const SampleOffsets& loff, const LensDev& lens, const SampleBands& band, const SampleKeys& key,
+                                 const MatDev* band_mats, uint32_t n_rows, const float* band_w, const float4* env, int32_t env_w, int32_t env_h,
+                                 uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
+                                 hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

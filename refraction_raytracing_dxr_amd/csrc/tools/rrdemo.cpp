@@ -10,6 +10,7 @@
 //          [--materials "IOR:R,G,B;IOR:R,G,B;..."]                 (with --spp N, default 1: a material table, absorption per unit length; instance i is made of row i modulo the rows)
 //          [--nested]                                              (with --materials: the nested-media ray tree, rr_render_nested)
 //          [--compose]                                             (with --spp N and --materials: --lens, --dispersion and --nested together, rr_render_composed; the Abbe number applies to every row)
+//          [--shutter K:DT]                                        (with --compose: every frame over K scene keys spread over DT radians of the orbit, rr_render_shutter; N x K x BANDS <= 64)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cstdio>
@@ -73,8 +74,8 @@ static int launch_ranks(int argc, char** argv, int gpus)
 int main(int argc, char** argv)
 {
     RefractionDemo::Options opt;
-    int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0;
-    float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f;
+    int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0, n_keys = 0;
+    float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f, shutter_dt = 0.0f;
     bool have_lens = false, pump = false, stream = false, nested = false, compose = false;
     std::vector<rr_material> materials;
     std::string out, idfile;
@@ -105,6 +106,9 @@ int main(int argc, char** argv)
             const int got = sscanf(argv[++i], "%d:%f", &n_bands, &abbe);
             if (got < 1 || n_bands < 1 || n_bands > 64 || (got == 1 && strchr(argv[i], ':')) || !(abbe > 0.0f)) { fprintf(stderr, "--dispersion takes BANDS[:ABBE], 1 <= BANDS <= 64, ABBE > 0\n"); return 2; }
         }
+        else if (arg("--shutter")) {
+            if (sscanf(argv[++i], "%d:%f", &n_keys, &shutter_dt) != 2 || n_keys < 1 || n_keys > RR_MAX_SCENE_KEYS || !(shutter_dt >= 0.0f)) { fprintf(stderr, "--shutter takes K:DT, 1 <= K <= 16, DT >= 0\n"); return 2; }
+        }
         else if (arg("--materials")) {
             bool ok = true;
             for (const char* q = argv[++i]; ok && *q;) {
@@ -126,14 +130,16 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]] [--compose]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]] [--compose [--shutter K:DT]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (compose) {          // the frames that refuse each other below, in one call: a lens and dispersion on the nested-media tree
         if (!spp || materials.empty()) { fprintf(stderr, "--compose needs --spp N and --materials\n"); return 2; }
         if (base || pump) { fprintf(stderr, "--compose cannot be combined with --adaptive or --pump\n"); return 2; }
         if ((long long)spp * (n_bands ? n_bands : 1) > 64) { fprintf(stderr, "--compose: --spp N times BANDS must not exceed 64 samples\n"); return 2; }
+        if ((long long)spp * (n_keys ? n_keys : 1) * (n_bands ? n_bands : 1) > 64) { fprintf(stderr, "--shutter: --spp N times K times BANDS must not exceed 64 samples\n"); return 2; }
     }
+    if (n_keys && !compose) { fprintf(stderr, "--shutter K:DT needs --compose\n"); return 2; }
     if (base && (!spp || base > spp)) { fprintf(stderr, "--adaptive BASE:THRESHOLD needs --spp N with BASE <= N\n"); return 2; }
     if (have_lens && (!spp || base)) { fprintf(stderr, "--lens RADIUS:FOCUS needs --spp N and cannot be combined with --adaptive\n"); return 2; }
     if (n_bands) {
@@ -245,7 +251,7 @@ int main(int argc, char** argv)
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
         const rr_lens lens = { lens_radius, lens_focus };
-        rc = compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = n_keys ? RefractionDemo::drawFrameShutter(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -260,7 +266,10 @@ int main(int argc, char** argv)
         }
     }
     double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (frames && compose)
+    if (frames && n_keys)
+        printf("%d shutter frames of %dx%d at %d samples per pixel x %d keys x %d bands with %d materials in %.3f s (%.1f fps incl. key captures and readback)\n", frames,
+               opt.width, opt.height, spp, n_keys, n_bands ? n_bands : 1, (int)materials.size(), s, frames / s);
+    else if (frames && compose)
         printf("%d composed frames of %dx%d at %d samples per pixel x %d bands with %d materials in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, n_bands ? n_bands : 1, (int)materials.size(), s, frames / s);
     else if (frames && base)

@@ -154,6 +154,35 @@ def lens_screen_rect(bounds, camera, lens, w, h):
     return tuple(int(v) for v in r)
 
 
+def shutter_samples(positions, keys, bands=None, lens_offsets=None):
+    """The crossed sample records of render_shutter -> SHUTTER_SAMPLE_DTYPE [A * K * B].  positions: an int (sample_pattern) or an
+    [A, 2] array of offsets in [0, 1]; keys: an int K for the scene keys 0 .. K-1, or a sequence of K key indices; bands: None for
+    band 0, an int B for bands 0 .. B-1, or a sequence of B band indices.  Sample (a * K + j) * B + b has position a, key j and band
+    b.  lens_offsets: None for lens_pattern(S), or an [S, 2] array in [-1, 1], one row per sample after crossing."""
+    pos = sample_pattern(positions) if isinstance(positions, (int, np.integer)) else np.ascontiguousarray(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError("shutter_samples: positions must be an int or an [A, 2] array")
+    ks = np.arange(int(keys)) if isinstance(keys, (int, np.integer)) else np.ascontiguousarray(keys, np.int64).reshape(-1)
+    bs = np.zeros(1, np.int64) if bands is None else np.arange(int(bands)) if isinstance(bands, (int, np.integer)) else np.ascontiguousarray(bands, np.int64).reshape(-1)
+    if len(ks) == 0 or len(bs) == 0 or (ks < 0).any() or (bs < 0).any():
+        raise ValueError("shutter_samples: need at least one key and one band, none negative")
+    n = len(pos) * len(ks) * len(bs)
+    if n > _capi.MAX_SAMPLES:
+        raise ValueError("shutter_samples: positions x keys x bands must not exceed %d samples" % _capi.MAX_SAMPLES)
+    rec = np.zeros(n, _capi.SHUTTER_SAMPLE_DTYPE)
+    rec["offset"] = np.repeat(pos, len(ks) * len(bs), axis=0)
+    rec["key"] = np.tile(np.repeat(ks, len(bs)), len(pos))
+    rec["band"] = np.tile(bs, len(pos) * len(ks))
+    if lens_offsets is not None:
+        loff = np.ascontiguousarray(lens_offsets, np.float32)
+        if loff.shape != (n, 2) or n == 0:
+            raise ValueError("shutter_samples: lens_offsets must be an [S, 2] array with one row per sample")
+        rec["lens_offset"] = loff
+    elif n >= 1:
+        rec["lens_offset"] = lens_pattern(n)
+    return rec
+
+
 def make_instances(transforms=None, meshes=None, masks=None, flags=None, materials=None):
     """64-byte instance records (RefractionDemo.cpp:324-334 fills exactly one: identity, mask 1, flags 0).  materials: per instance
     the row of the material table (Renderer.set_materials) it is made of -- DXR's InstanceContributionToHitGroupIndex, the low 24
@@ -803,6 +832,77 @@ class Renderer:
             self._ck(self._L.rr_render_composed_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed_device")
         else:
             self._ck(self._L.rr_render_composed(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed")
+        return _result(outs)
+
+    def capture_scene_key(self, key):
+        """Freezes the scene a render call issued now would trace as scene key `key` (rr_capture_scene_key), 0 <= key <
+        MAX_SCENE_KEYS: its instances, hierarchy, triangles and normals are copied, device to device on the renderer's stream, into
+        buffers the key owns.  Needs a built TLAS.  Capturing into a used key replaces it.  Later builds, refits, vertex updates
+        and load_scene change no key; the environment map, the material table and the band set are not part of one."""
+        self._ck(self._L.rr_capture_scene_key(self._h, int(key)), "rr_capture_scene_key")
+
+    def release_scene_key(self, key=None):
+        """Frees scene key `key`, or every key with None (rr_release_scene_key); an empty key is fine."""
+        self._ck(self._L.rr_release_scene_key(self._h, _capi.ALL_SCENE_KEYS if key is None else int(key)), "rr_release_scene_key")
+
+    def scene_key_info(self, key):
+        """-> SceneKeyInfo of scene key `key` (rr_scene_key_info): captured, top_level, n_instances, n_triangles, bounds (lo xyz, hi
+        xyz), stack_need, max_material, bytes; all zero for an empty key."""
+        info = _capi.SceneKeyInfo()
+        self._ck(self._L.rr_scene_key_info(self._h, int(key), C.byref(info)), "rr_scene_key_info")
+        return info
+
+    def render_shutter(self, width, height, camera, samples=4, keys=None, lens=None, lens_samples=None, bands=None, paired=False, params=None,
+                       rgba8=False, ray_counts=False, device=False):
+        """Shutter frame (rr_render_shutter): render_composed with every sample traced in a captured scene key -- motion blur over
+        the instants capture_scene_key froze.  Sample k is shaded as shade_rays_nested shades lens_rays(...) (no lens: camera_rays)
+        in the scene of key key_k under band band_k, and the pixel resolves as render_composed's.  The live scene is not used and
+        need not be built.
+        samples: an int (sample_pattern), an [A, 2] array of offsets, or a SHUTTER_SAMPLE_DTYPE record array, which is passed
+        straight through (keys, lens_samples, bands and paired must then be left alone; shutter_samples makes one).  keys: an int K
+        crosses the positions with keys 0 .. K-1; with paired=True an [S] array, one key per position.  None is refused: there is
+        no implicit key.  bands: None for band 0; an int B crosses with bands 0 .. B-1; with paired=True an [S] array.  With ints,
+        sample (a * K + j) * B + b is position a, key j, band b, and A * K * B <= 64.  The other arguments, the outputs and
+        device=True as render_composed; not a dispatch either.  The camera and the lens disk must lie outside every instance of
+        every key used."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        if w < 0 or h < 0:
+            raise ValueError("render_shutter: negative size")
+        if isinstance(samples, np.ndarray) and samples.dtype == _capi.SHUTTER_SAMPLE_DTYPE:
+            if keys is not None or lens_samples is not None or bands is not None or paired:
+                raise ValueError("render_shutter: a record array of samples carries its own keys, lens offsets and bands")
+            rec = np.ascontiguousarray(samples).reshape(-1)
+        else:
+            if keys is None:
+                raise ValueError("render_shutter: keys is required (an int K, or with paired=True one key per sample): there is no implicit key")
+            offp, n = _sample_offsets(samples, "render_shutter: samples must be an int, an [S, 2] array or a SHUTTER_SAMPLE_DTYPE array")
+            pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
+            if paired:
+                kidx = np.ascontiguousarray(keys, np.int64).reshape(-1)
+                bidx = np.zeros(len(pos), np.int64) if bands is None else np.ascontiguousarray(bands, np.int64).reshape(-1)
+                if isinstance(keys, (int, np.integer)) or len(kidx) != len(pos) or len(bidx) != len(pos) or (kidx < 0).any() or (bidx < 0).any():
+                    raise ValueError("render_shutter: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample")
+                rec = np.zeros(len(pos), _capi.SHUTTER_SAMPLE_DTYPE)
+                rec["offset"], rec["key"], rec["band"] = pos, kidx, bidx
+                if lens_samples is not None:
+                    loff = np.ascontiguousarray(lens_samples, np.float32)
+                    if loff.shape != (len(rec), 2) or len(rec) == 0:
+                        raise ValueError("render_shutter: lens_samples must be an [S, 2] array with one row per sample")
+                    rec["lens_offset"] = loff
+                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
+                    rec["lens_offset"] = lens_pattern(len(rec))
+            else:
+                if not isinstance(keys, (int, np.integer)) or keys < 1 or not (bands is None or (isinstance(bands, (int, np.integer)) and bands >= 1)):
+                    raise ValueError("render_shutter: keys must be an int >= 1 and bands None or an int >= 1, or both arrays with paired=True")
+                rec = shutter_samples(pos, int(keys), bands, lens_samples)
+        recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
+        lp = C.byref(lens) if lens is not None else None
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_shutter_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter_device")
+        else:
+            self._ck(self._L.rr_render_shutter(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter")
         return _result(outs)
 
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):

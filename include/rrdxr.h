@@ -655,6 +655,71 @@ int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, c
                              const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
                              void* d_rgba8, void* d_n_rays);
 
+/* ---- opaque hit groups: lit, mirror and emissive instances with shadow rays (additive; the ABI version stays 3) -------------------
+ * hitgroup_flags & 0xffffff selects a row per instance, as DXR's InstanceContributionToHitGroupIndex selects a ClosestHit shader.
+ * The four calls below are their _nested twins -- the same arguments, rays, sample offsets, resolve, tone mapping, RGBA8, culling of
+ * background blocks, alignment rules and state: not dispatches, on the context's stream, params->ior ignored -- with a second hit
+ * group: an instance whose row of the SURFACE table is RR_SURFACE_OPAQUE is a surface lit by a small set of directional and point
+ * lights through shadow rays, with an emission term and an optional mirror child.
+ *
+ * Tables.  Surface row r belongs with material row r.  Instance rows at or beyond the surface table's length are glass, and so are
+ * all rows while no surface table is set.  rr_set_materials neither reads nor clears the surface table.  An opaque row still needs
+ * a material row; its ior and sigma_a are never read.  The context owns a device copy of the surface table, next to the material
+ * table, and a host copy of the lights, which travel by value with every launch (one in flight keeps the set it was launched with).
+ * Both setters wait for the context's stream, as rr_set_materials does, and only the four calls below read what they set.
+ *   rr_set_surfaces: n == 0 clears.  kind a known value; every float finite; albedo and specular >= 0 (emission may be negative).
+ *   rr_set_lights:   n <= RR_MAX_LIGHTS; ambient NULL = (0, 0, 0), else three finite floats.  kind a known value; v and radiance
+ *                    finite (a negative radiance is allowed); a directional v is not (0, 0, 0) and is used AS GIVEN -- normalise it;
+ *                    shadow_mask <= 0xff.
+ * A refused table (RR_ERR_INVALID_ARGUMENT) leaves the one in force.
+ *
+ * The contract.  One rounding per written operation, fmaf only where written, dot is the shader's dot3.  Everything in the nested
+ * calls' contract stands, step 1 included: absorption over t in the medium CROSSED happens before anything else, so an opaque olive
+ * inside a tinted liquid is dimmed correctly.  After step 1, a hit with count < max_refract on row m whose surface kind is
+ * RR_SURFACE_OPAQUE does this instead of steps 2-5:
+ *   a. L is unchanged.  X = fmaf(t, D, O).  N is the shading normal, Nf = front ? N : -N, front the HitKind as before.
+ *   b. E = ambient.  Then for each light in table order:
+ *        directional: Ld = v, far = tmax_secondary, g = 1.
+ *        point:       d = v - X per component, d2 = dot(d, d), far = sqrtf(d2), Ld = d / far per component, g = 1.0f / d2.
+ *        cs = dot(Nf, Ld).  If !(cs > 0) the light adds nothing AND NO RAY IS TRACED.  Otherwise one shadow ray:
+ *        TraceRay(X, Ld, [tmin_secondary, far], cull flags 0, ACCEPT_FIRST_HIT_AND_END_SEARCH, InstanceInclusionMask = shadow_mask).
+ *        It counts as one ray in n_rays, whether or not any instance passes the mask.  Any accepted hit occludes, glass instances
+ *        included; to let glass cast no shadow, give it an InstanceMask bit that the light's shadow_mask lacks.  If unoccluded:
+ *        f = cs * g and E.ch = fmaf(radiance.ch, f, E.ch).
+ *   c. col.ch = fmaf(albedo.ch, E.ch, emission.ch).  Then acc.ch = fmaf(w.ch, col.ch, acc.ch).
+ *   d. If any specular.ch != 0: one child (X, normalize(ReflectRay(D, Nf)), w.ch * specular.ch, L, count + 1) on the secondary
+ *      interval.  It is the continuing ray; nothing is parked.  It is NOT gated by max_reflect -- a mirror is the main path -- count
+ *      alone bounds it, so the tree stays bounded as before.  Otherwise the branch ends and a parked ray is taken up, as after a Miss.
+ * A scene without a top level shades its one instance (mask 1, row of instance 0) the same way; its shadow ray passes if
+ * shadow_mask & 1.
+ *
+ * Reduction: with no surface table, or with every row glass, the four calls equal the _nested calls byte for byte in colours, RGBA8
+ * and counts.  The lights are then never read.
+ * Not covered: transparent shadows; area lights or environment lighting of opaque surfaces; textures; opaque rows in
+ * rr_render_composed / rr_render_shutter, the dispatch kernels and the _materials calls (all of which ignore the surface table).
+ *
+ * State and rows as the nested calls: RR_ERR_STATE without a built TLAS or without a material table; RR_ERR_INVALID_ARGUMENT when an
+ * instance's row is >= the material table's length or > RR_NESTED_MAX_MATERIAL. */
+#define RR_SURFACE_GLASS  0u      /* the row of rr_set_materials decides everything: rr_shade_rays_nested's ClosestHit */
+#define RR_SURFACE_OPAQUE 1u
+typedef struct rr_surface { uint32_t kind; float albedo[3]; float emission[3]; float specular[3]; uint32_t pad[2]; } rr_surface;  /* 48 bytes */
+#define RR_LIGHT_DIRECTIONAL 0u   /* v: unit direction TOWARDS the light */
+#define RR_LIGHT_POINT       1u   /* v: position */
+#define RR_MAX_LIGHTS 8
+typedef struct rr_light { float v[3]; uint32_t kind; float radiance[3]; uint32_t shadow_mask; } rr_light;                          /* 32 bytes */
+int  rr_set_surfaces(rr_context* ctx, const rr_surface* rows, uint32_t n);
+int  rr_set_lights(rr_context* ctx, const rr_light* lights, uint32_t n, const float ambient[3]);
+int  rr_shade_rays_surfaces(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f,
+                            uint8_t* rgba8, uint32_t* n_rays);
+int  rr_shade_rays_surfaces_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f,
+                                   void* d_rgba8, void* d_n_rays);
+int  rr_render_surfaces(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                        const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8,
+                        uint32_t* n_rays);
+int  rr_render_surfaces_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                               const rr_dispatch_params* params, const float* offsets, uint32_t n_samples, void* d_rgba32f,
+                               void* d_rgba8, void* d_n_rays);
+
 /* ---- composed frames: a lens and dispersion on the nested-media tree (present from ABI version 3) ---------------------------------
  * One frame call that takes the primary rays of rr_render_lens, the ray tree of rr_render_nested and the weighted resolve of
  * rr_render_spectral, with dispersion per material instead of per frame: the glass of water with an ice cube, photographed with

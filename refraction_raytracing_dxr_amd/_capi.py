@@ -64,6 +64,13 @@ assert COMPOSED_SAMPLE_DTYPE.itemsize == 32
 # rr_shutter_sample: one sample of render_shutter -- a composed sample and the scene key it is traced in
 SHUTTER_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("key", "<u4"), ("pad", "<u4", 2)])
 assert SHUTTER_SAMPLE_DTYPE.itemsize == 32
+# rr_surface: one row of the surface table (set_surfaces) -- what an instance of material row r is; rr_light: one light (set_lights)
+SURFACE_GLASS, SURFACE_OPAQUE = 0, 1     # RR_SURFACE_*
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1    # RR_LIGHT_*: v is the unit direction TOWARDS the light, or its position
+MAX_LIGHTS = 8                           # RR_MAX_LIGHTS
+SURFACE_DTYPE = np.dtype([("kind", "<u4"), ("albedo", "<f4", 3), ("emission", "<f4", 3), ("specular", "<f4", 3), ("pad", "<u4", 2)])
+LIGHT_DTYPE = np.dtype([("v", "<f4", 3), ("kind", "<u4"), ("radiance", "<f4", 3), ("shadow_mask", "<u4")])
+assert SURFACE_DTYPE.itemsize == 48 and LIGHT_DTYPE.itemsize == 32
 MAX_SCENE_KEYS = 16                      # RR_MAX_SCENE_KEYS: scene keys a context holds (capture_scene_key)
 ALL_SCENE_KEYS = 0xFFFFFFFF              # RR_ALL_SCENE_KEYS: release_scene_key's "every key"
 
@@ -201,6 +208,13 @@ SYMBOLS = {
     "rr_shade_rays_nested_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
     "rr_render_nested": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
     "rr_render_nested_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_set_surfaces": (C.c_int, [_P, _P, C.c_uint32]),
+    "rr_set_lights": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "rr_shade_rays_surfaces": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_shade_rays_surfaces_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(DispatchParams), _P, _P, _P]),
+    "rr_render_surfaces": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P, _P]),
+    "rr_render_surfaces_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32, _P, _P,
+                                            _P]),
     "rr_set_material_bands": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "rr_render_composed": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
                                      C.POINTER(Lens), _P, _P, _P]),

@@ -172,6 +172,77 @@ int drawFrameNested(int spp)
     return RR_OK;
 }
 
+int setFloorAndLights(const float albedo[3], float specular, const rr_light* lights, int n_lights)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (g_mats.empty()) return fail(RR_ERR_STATE, "setFloorAndLights: setMaterials first");
+    if (!albedo || n_lights < 0 || n_lights > RR_MAX_LIGHTS || (n_lights && !lights))
+        return fail(RR_ERR_INVALID_ARGUMENT, "setFloorAndLights: need an albedo and at most 8 lights");
+    // The floor needs no file: these are the 36 vertices Mesh::load gives for the shipped assets/cube.obj, in its order -- triangle
+    // k / 3 of two passes over the faces -x, -z, +x, +z, -y, +y, flat normals whose zero components are negative zeros as the OBJ
+    // writes them ("-0.0000").  The order and the zeros' signs only matter to a comparison bit for bit with a frame of cube.obj
+    // under the same transform (tests/test_gpu_surfaces.py's rrdemo test): if the asset is ever re-exported, regenerate this table
+    // from the loader's output or that test's floor differs in ties on shared edges and in the signs of zero direction components
+    static const float P[36][3] = {
+        { -1, 1, 1 }, { -1, -1, -1 }, { -1, -1, 1 }, { -1, 1, -1 }, { 1, -1, -1 }, { -1, -1, -1 }, { 1, 1, -1 }, { 1, -1, 1 }, { 1, -1, -1 },
+        { 1, 1, 1 }, { -1, -1, 1 }, { 1, -1, 1 }, { 1, -1, -1 }, { -1, -1, 1 }, { -1, -1, -1 }, { -1, 1, -1 }, { 1, 1, 1 }, { 1, 1, -1 },
+        { -1, 1, 1 }, { -1, 1, -1 }, { -1, -1, -1 }, { -1, 1, -1 }, { 1, 1, -1 }, { 1, -1, -1 }, { 1, 1, -1 }, { 1, 1, 1 }, { 1, -1, 1 },
+        { 1, 1, 1 }, { -1, 1, 1 }, { -1, -1, 1 }, { 1, -1, -1 }, { 1, -1, 1 }, { -1, -1, 1 }, { -1, 1, -1 }, { -1, 1, 1 }, { 1, 1, 1 } };
+    static const int axis[6] = { 0, 2, 0, 2, 1, 1 };
+    static const float sign[6] = { -1, -1, 1, 1, -1, 1 };
+    Mesh floor;
+    for (int k = 0; k < 36; ++k) {
+        Vertex v;
+        std::memset(&v, 0, sizeof v);
+        const int f = (k / 3) % 6;
+        for (int c = 0; c < 3; ++c) { v.position[c] = P[k][c]; v.norm[c] = c == axis[f] ? sign[f] : -0.0f; }
+        floor.verts.push_back(v);
+        floor.indices.push_back((uint32_t)k);
+    }
+    int rc = floor.upload(g_ctx);
+    if (rc != RR_OK) return fail(rc, "Mesh::upload (floor)");
+    if ((rc = rr_build_blas(g_ctx, floor.mesh_id)) != RR_OK) return fail(rc, "rr_build_blas (floor)");
+    float ymin = 3.0e38f;
+    for (uint32_t i : cubeMesh.indices) ymin = cubeMesh.verts[i].position[1] < ymin ? cubeMesh.verts[i].position[1] : ymin;
+    rr_instance_desc inst[2];
+    std::memset(inst, 0, sizeof inst);
+    inst[0].transform[0] = inst[0].transform[5] = inst[0].transform[10] = 1.0f;
+    inst[0].instance_id_mask = 1u << 24;
+    inst[0].blas = cubeMesh.raytracingGeometry().mesh_id;
+    inst[1].transform[0] = 4.0f; inst[1].transform[5] = 0.1f; inst[1].transform[10] = 4.0f;
+    inst[1].transform[7] = ymin - 0.15f;
+    inst[1].instance_id_mask = 1u | (1u << 24);
+    inst[1].hitgroup_flags = (uint32_t)g_mats.size();           // the row appended below
+    inst[1].blas = floor.mesh_id;
+    if ((rc = rr_build_tlas(g_ctx, inst, 2)) != RR_OK) return fail(rc, "rr_build_tlas");
+    std::vector<rr_material> mats = g_mats;
+    mats.push_back(rr_material{ 1.0f, { 0.0f, 0.0f, 0.0f } });  // never read: the row is opaque
+    if ((rc = rr_set_materials(g_ctx, mats.data(), (uint32_t)mats.size())) != RR_OK) return fail(rc, "rr_set_materials");
+    std::vector<rr_surface> surf(mats.size());
+    std::memset(surf.data(), 0, surf.size() * sizeof(rr_surface));
+    rr_surface& s = surf.back();
+    s.kind = RR_SURFACE_OPAQUE;
+    for (int c = 0; c < 3; ++c) { s.albedo[c] = albedo[c]; s.specular[c] = specular; }
+    if ((rc = rr_set_surfaces(g_ctx, surf.data(), (uint32_t)surf.size())) != RR_OK) return fail(rc, "rr_set_surfaces");
+    static const float ambient[3] = { 0.05f, 0.05f, 0.05f };
+    if ((rc = rr_set_lights(g_ctx, lights, (uint32_t)n_lights, ambient)) != RR_OK) return fail(rc, "rr_set_lights");
+    return RR_OK;
+}
+
+int drawFrameSurfaces(int spp)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (spp <= 0) return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameSurfaces: spp must be 1, 2, 4, 8 or 16");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    g_angle += g_opt.angle_step;
+    if ((rc = rr_render_surfaces(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, nullptr, (uint32_t)spp, nullptr,
+                                 g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_surfaces");
+    return RR_OK;
+}
+
 // the band set of the composed and shutter frames: every row's index spread by Cauchy's law through its own value; the weights are
 // the same for every row
 static int setBandSet(int n_bands, float abbe)

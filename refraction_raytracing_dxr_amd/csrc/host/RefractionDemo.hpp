@@ -42,6 +42,12 @@ int setMaterials(const rr_material* mats, int n);
 int drawFrameMaterials(int spp);
 // drawFrameMaterials with the nested-media ray tree (rr_render_nested): instances may sit inside, or overlap, other instances
 int drawFrameNested(int spp);
+// A lit table under the mesh (after setMaterials): an opaque floor -- cube.obj's twelve triangles scaled to (4, 0.1, 4), its top 0.05
+// below the mesh's lowest vertex -- as a second instance made of a material row and an opaque surface row appended to the table
+// (albedo, and specular in every channel), lit by n_lights lights and an ambient term of 0.05.  The scene gets a top level.
+// drawFrameSurfaces is drawFrameNested shaded with them (rr_render_surfaces)
+int setFloorAndLights(const float albedo[3], float specular, const rr_light* lights, int n_lights);
+int drawFrameSurfaces(int spp);
 // drawFrameNested composed with a lens and dispersion per material (rr_render_composed): the spp built-in positions crossed with
 // n_bands bands, sample a * n_bands + b being position a in band b, each sample with the lens point of rr_host_lens_pattern(spp *
 // n_bands); lens may be null (a pinhole).  The band set (rr_set_material_bands) gives every row of the table of setMaterials the

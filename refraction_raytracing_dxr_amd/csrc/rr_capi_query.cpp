@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_surfaces, rr_set_lights, rr_shade_rays_surfaces*, rr_render_surfaces*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -322,6 +322,30 @@ int nested_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, 
     const FrameArgs f = frame_args(ctx, q);
     if (hipError_t e = launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
                                             f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.who, e);
+    return RR_OK;
+}
+
+// shade_nested_impl with the surface table and the lights (p: after check_nested)
+int shade_surfaces_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+{
+    if (int r = check_shading_params(ctx, who, p)) return r;
+    SceneDev sc;
+    fill_scene(ctx, sc);
+    const DispatchDev a = shading_args(p);
+    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
+    if (hipError_t e = launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n,
+                                                  out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, who, e);
+    return RR_OK;
+}
+
+// nested_impl with the surface table and the lights (q.params: after check_nested)
+int surfaces_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+{
+    const FrameArgs f = frame_args(ctx, q);
+    if (hipError_t e = launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx),
+                                              q.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.who, e);
     return RR_OK;
 }
@@ -901,6 +925,134 @@ int rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, co
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_nested_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return nested_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_set_surfaces(rr_context* ctx, const rr_surface* rows, uint32_t n)
+{
+    if (int r = use_device(ctx)) return r;
+    if (n == 0) { ctx->n_surfs = 0; return RR_OK; }
+    if (!rows) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_surfaces: null table");
+    if (n > 0x1000000u) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_surfaces: a hit-group index has 24 bits, so at most 16 777 216 rows");
+    std::vector<SurfDev> dev(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const rr_surface& s = rows[i];
+        if (s.kind != RR_SURFACE_GLASS && s.kind != RR_SURFACE_OPAQUE) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_surfaces: unknown surface kind");
+        SurfDev& o = dev[i];
+        memset(&o, 0, sizeof o);
+        o.kind = s.kind;
+        for (int ch = 0; ch < 3; ++ch) {
+            if (!std::isfinite(s.albedo[ch]) || !(s.albedo[ch] >= 0.0f) || !std::isfinite(s.specular[ch]) || !(s.specular[ch] >= 0.0f))
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_surfaces: every albedo and specular must be finite and >= 0");
+            if (!std::isfinite(s.emission[ch])) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_surfaces: every emission must be finite");
+            o.albedo[ch] = s.albedo[ch]; o.emission[ch] = s.emission[ch]; o.specular[ch] = s.specular[ch];
+        }
+    }
+    // as rr_set_materials: the table in force stays until the new one is whole, and the copy is ordered behind what is in flight
+    if (n > ctx->d_surfs.size()) {
+        ctx->n_surfs = 0;
+        if (int r = ctx->d_surfs.grow(ctx, n)) return r;
+    }
+    RR_HIP(hipMemcpyAsync(ctx->d_surfs.get(), dev.data(), (size_t)n * sizeof(SurfDev), hipMemcpyHostToDevice, ctx->stream));
+    RR_HIP(hipStreamSynchronize(ctx->stream));   // (dev goes away with this call)
+    ctx->n_surfs = n;
+    return RR_OK;
+}
+
+int rr_set_lights(rr_context* ctx, const rr_light* lights, uint32_t n, const float ambient[3])
+{
+    if (int r = use_device(ctx)) return r;
+    if (n > RR_MAX_LIGHTS) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: need n <= RR_MAX_LIGHTS (8)");
+    if (n && !lights) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: null lights");
+    LightsDev t;
+    memset(&t, 0, sizeof t);
+    for (uint32_t i = 0; i < n; ++i) {
+        const rr_light& l = lights[i];
+        if (l.kind != RR_LIGHT_DIRECTIONAL && l.kind != RR_LIGHT_POINT) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: unknown light kind");
+        if (l.shadow_mask > 0xffu) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: an instance mask has 8 bits, so shadow_mask <= 0xff");
+        for (int ch = 0; ch < 3; ++ch) {
+            if (!std::isfinite(l.v[ch]) || !std::isfinite(l.radiance[ch]))
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: every direction, position and radiance must be finite");
+            t.l[i].v[ch] = l.v[ch]; t.l[i].radiance[ch] = l.radiance[ch];
+        }
+        if (l.kind == RR_LIGHT_DIRECTIONAL && l.v[0] == 0.0f && l.v[1] == 0.0f && l.v[2] == 0.0f)
+            return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: a directional light needs a direction that is not zero");
+        t.l[i].kind = l.kind; t.l[i].shadow_mask = l.shadow_mask;
+    }
+    for (int ch = 0; ch < 3; ++ch) {
+        if (ambient && !std::isfinite(ambient[ch])) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_lights: the ambient term must be finite");
+        t.ambient[ch] = ambient ? ambient[ch] : 0.0f;
+    }
+    t.n = n;
+    // the set travels by value with every launch: those in flight hold their own copy.  Waiting keeps the setters alike
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->lights = t;
+    return RR_OK;
+}
+
+int rr_shade_rays_surfaces(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
+                           uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_surfaces: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_shade_rays_surfaces", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces: need rgba32f or rgba8");
+    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces: null rays");
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_surfaces_impl(ctx, "rr_shade_rays_surfaces", ctx->d_rays.get(), n, p, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_shade_rays_surfaces_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
+                                  void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_surfaces_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_shade_rays_surfaces_device", p)) return r;
+    if (n == 0) return RR_OK;
+    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces_device: need d_rgba32f or d_rgba8");
+    const char* const align = "rr_shade_rays_surfaces_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
+    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
+    return shade_surfaces_impl(ctx, "rr_shade_rays_surfaces_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
+                               { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_render_surfaces(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                       const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_surfaces: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_render_surfaces", p)) return r;
+    const SamplesReq q = { "rr_render_surfaces", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = surfaces_impl(ctx, q, off, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_surfaces_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                              const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_surfaces_device: build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (int r = check_nested(ctx, "rr_render_surfaces_device", p)) return r;
+    const SamplesReq q = { "rr_render_surfaces_device", width, height, constants, &p, offsets, n_samples };
+    SampleOffsets off;
+    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_surfaces_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return surfaces_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_render_composed(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,

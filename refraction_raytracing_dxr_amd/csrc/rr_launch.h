@@ -90,6 +90,16 @@ hipError_t launch_shade_rays_nested(const SceneDev& sc, const DispatchDev& a, co
 hipError_t launch_render_nested(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
                                 uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
                                 bool stack16, hipStream_t s);
+// ---- rr_render_surfaces.hip: opaque hit groups (rr_shade_rays_surfaces[_device], rr_render_surfaces[_device]): launch_shade_rays_nested
+// and launch_render_nested with the ray tree of rr_render_surfaces.h -- an instance whose row of the surface table is opaque is lit
+// by `lights` through shadow rays, emits and may continue as a mirror.  surfs: the context's table in device memory, n_surfs rows
+// (0: every row is glass, surfs may be null); rows at or beyond n_surfs are glass.  lights travels by value to the kernel
+hipError_t launch_shade_rays_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfDev* surfs, uint32_t n_surfs,
+                                      const LightsDev& lights, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
+                                      uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+hipError_t launch_render_surfaces(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
+                                  const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t mat0, uint32_t n_samples, float4* f32,
+                                  uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
 // ---- rr_render_composed.hip: composed frames (rr_render_composed[_device]): launch_render_nested with launch_render_lens' primary
 // rays (off, loff, lens; a.hx0..hy1 the lens rectangle, or the pinhole's when lens.pinhole) and launch_render_spectral's resolve.
 // Sample k is shaded under the table band_mats + b_k * n_rows (the context's band set: the bands' tables one behind the other,

@@ -154,6 +154,26 @@ struct alignas(32) MatDev {
 };
 static_assert(sizeof(MatDev) == 32, "MatDev must be 32 B");
 
+// One row of the surface table (rr_set_surfaces) as the surface kernels read it (rr_render_surfaces.h): rr_surface's layout.  A lane
+// fetches kind at every ClosestHit on a row the table covers, and the rest only when the row is opaque.
+struct alignas(16) SurfDev {
+    uint32_t kind;            // RR_SURFACE_GLASS / RR_SURFACE_OPAQUE
+    float albedo[3], emission[3], specular[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(SurfDev) == 48, "SurfDev must be 48 B");
+constexpr uint32_t SURFACE_OPAQUE = 1u, LIGHT_POINT = 1u, MAX_LIGHTS = 8u;
+
+// The lights and the ambient term (rr_set_lights) as the surface kernels take them: BY VALUE, as a kernel argument, the same for
+// every lane -- the rows arrive through scalar loads and the light loop's trip count n is wave-uniform.  Rows are rr_light's layout.
+struct LightDev { float v[3]; uint32_t kind; float radiance[3]; uint32_t shadow_mask; };
+struct LightsDev {
+    LightDev l[MAX_LIGHTS];
+    float ambient[3];
+    uint32_t n;
+};
+static_assert(sizeof(LightDev) == 32 && sizeof(LightsDev) == 8 * 32 + 16, "LightsDev must be 8 rows and four words");
+
 // exp(x) for x <= 0 (Beer-Lambert: x = -(sigma * t)), the one definition host and device share, in fp32 with every fused
 // operation written as fmaf (Cephes' expf: x = k ln 2 + r with ln 2 split in two, a degree-5 polynomial in r, 2^k from the exponent
 // bits).  Exactly 1 for +0 and -0; 0 from -87 down (and for a NaN); k >= -126 above the cut, so 2^k is a normal number.

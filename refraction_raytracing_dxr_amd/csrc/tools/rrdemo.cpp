@@ -9,10 +9,13 @@
 //          [--dispersion BANDS[:ABBE]]                             (with --spp N, default 1: N positions x BANDS bands of the Abbe number, default 30)
 //          [--materials "IOR:R,G,B;IOR:R,G,B;..."]                 (with --spp N, default 1: a material table, absorption per unit length; instance i is made of row i modulo the rows)
 //          [--nested]                                              (with --materials: the nested-media ray tree, rr_render_nested)
+//          [--floor R,G,B[:S]]                                     (with --nested --materials: an opaque floor of that albedo under the mesh, with specular S in every channel; rr_render_surfaces)
+//          [--light x,y,z:R,G,B | --light @x,y,z:R,G,B]            (with --nested --materials, up to 8 times: a directional light towards (x, y, z), or with @ a point light at (x, y, z), of that radiance)
 //          [--compose]                                             (with --spp N and --materials: --lens, --dispersion and --nested together, rr_render_composed; the Abbe number applies to every row)
 //          [--shutter K:DT]                                        (with --compose: every frame over K scene keys spread over DT radians of the orbit, rr_render_shutter; N x K x BANDS <= 64)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -78,6 +81,9 @@ int main(int argc, char** argv)
     float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f, shutter_dt = 0.0f;
     bool have_lens = false, pump = false, stream = false, nested = false, compose = false;
     std::vector<rr_material> materials;
+    std::vector<rr_light> lights;
+    bool have_floor = false;
+    float floor_albedo[3] = { 0.0f, 0.0f, 0.0f }, floor_specular = 0.0f;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
         auto arg = [&](const char* name) { return !strcmp(argv[i], name) && i + 1 < argc; };
@@ -121,6 +127,33 @@ int main(int argc, char** argv)
             }
             if (!ok || materials.empty()) { fprintf(stderr, "--materials takes IOR:R,G,B rows separated by ';', IOR > 0, R, G, B >= 0\n"); return 2; }
         }
+        else if (arg("--floor")) {
+            int used = 0;
+            const char* q = argv[++i];
+            bool ok = sscanf(q, "%f,%f,%f%n", &floor_albedo[0], &floor_albedo[1], &floor_albedo[2], &used) == 3 && (q[used] == ':' || q[used] == 0);
+            if (ok && q[used] == ':') { int more = 0; ok = sscanf(q + used + 1, "%f%n", &floor_specular, &more) == 1 && q[used + 1 + more] == 0; }
+            if (!ok || !(floor_albedo[0] >= 0.0f) || !(floor_albedo[1] >= 0.0f) || !(floor_albedo[2] >= 0.0f) || !(floor_specular >= 0.0f)) { fprintf(stderr, "--floor takes R,G,B[:S], all >= 0\n"); return 2; }
+            have_floor = true;
+        }
+        else if (arg("--light")) {
+            const char* q = argv[++i];
+            const bool point = q[0] == '@';
+            double v[3];
+            rr_light l;
+            int used = 0;
+            memset(&l, 0, sizeof l);
+            if (sscanf(q + (point ? 1 : 0), "%lf,%lf,%lf:%f,%f,%f%n", &v[0], &v[1], &v[2], &l.radiance[0], &l.radiance[1], &l.radiance[2], &used) != 6 || q[(point ? 1 : 0) + used] != 0) { fprintf(stderr, "--light takes x,y,z:R,G,B, or @x,y,z:R,G,B for a point light\n"); return 2; }
+            const double xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];       // one operation per statement: nothing to fuse
+            const double xy = xx + yy;
+            const double sum = xy + zz;
+            const double len = sqrt(sum);
+            if (!point && !(len > 0.0 && std::isfinite(len))) { fprintf(stderr, "--light: a direction must not be zero\n"); return 2; }
+            for (int c = 0; c < 3; ++c) l.v[c] = (float)(point ? v[c] : v[c] / len);      // a direction is normalised in double, then rounded
+            l.kind = point ? RR_LIGHT_POINT : RR_LIGHT_DIRECTIONAL;
+            l.shadow_mask = 0xffu;
+            if (lights.size() == RR_MAX_LIGHTS) { fprintf(stderr, "--light: at most 8 lights\n"); return 2; }
+            lights.push_back(l);
+        }
         else if (arg("--device")) opt.device = atoi(argv[++i]);
         else if (arg("--gpus")) gpus = atoi(argv[++i]);
         else if (arg("--frames-per-gather")) fpg = atoi(argv[++i]);
@@ -130,7 +163,7 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested]] [--compose [--shutter K:DT]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]...]] [--compose [--shutter K:DT]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (compose) {          // the frames that refuse each other below, in one call: a lens and dispersion on the nested-media tree
@@ -154,6 +187,10 @@ int main(int argc, char** argv)
         if (!spp) spp = 1;
     }
     if (nested && materials.empty()) { fprintf(stderr, "--nested needs --materials\n"); return 2; }
+    const bool surfaces = have_floor || !lights.empty();
+    if (surfaces && (!nested || materials.empty())) { fprintf(stderr, "--floor and --light need --nested --materials\n"); return 2; }
+    if (surfaces && (compose || n_keys || base || have_lens || n_bands)) { fprintf(stderr, "--floor and --light render with the nested tree alone: they cannot be combined with --compose, --shutter, --adaptive, --lens or --dispersion\n"); return 2; }
+    if (!lights.empty() && !have_floor) { fprintf(stderr, "--light needs --floor: glass is not lit by lights\n"); return 2; }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
         unsigned char id[128];
@@ -196,6 +233,10 @@ int main(int argc, char** argv)
     if (rc != RR_OK) { fprintf(stderr, "initialize failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
     if (!materials.empty() && (rc = RefractionDemo::setMaterials(materials.data(), (int)materials.size())) != RR_OK) {
         fprintf(stderr, "setMaterials failed (%d): %s\n", rc, RefractionDemo::lastError());
+        return 1;
+    }
+    if (have_floor && (rc = RefractionDemo::setFloorAndLights(floor_albedo, floor_specular, lights.data(), (int)lights.size())) != RR_OK) {
+        fprintf(stderr, "setFloorAndLights failed (%d): %s\n", rc, RefractionDemo::lastError());
         return 1;
     }
     auto t0 = std::chrono::steady_clock::now();
@@ -251,7 +292,7 @@ int main(int argc, char** argv)
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
         const rr_lens lens = { lens_radius, lens_focus };
-        rc = n_keys ? RefractionDemo::drawFrameShutter(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = n_keys ? RefractionDemo::drawFrameShutter(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : have_floor ? RefractionDemo::drawFrameSurfaces(spp) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -278,6 +319,9 @@ int main(int argc, char** argv)
     else if (frames && n_bands)
         printf("%d frames of %dx%d at %d samples per pixel x %d bands of Abbe number %g in %.3f s (%.1f fps incl. readback)\n", frames, opt.width,
                opt.height, spp, n_bands, abbe, s, frames / s);
+    else if (frames && have_floor)
+        printf("%d frames of %dx%d at %d samples per pixel with %d materials (nested media) on a floor under %d lights in %.3f s (%.1f fps incl. readback)\n", frames,
+               opt.width, opt.height, spp, (int)materials.size(), (int)lights.size(), s, frames / s);
     else if (frames && !materials.empty())
         printf("%d frames of %dx%d at %d samples per pixel with %d materials%s in %.3f s (%.1f fps incl. readback)\n", frames, opt.width, opt.height, spp,
                (int)materials.size(), nested ? " (nested media)" : "", s, frames / s);

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, BAND_DTYPE, HIT_DTYPE, INSTANCE_DTYPE, MATERIAL_DTYPE, NODE_DTYPE, RAY_DTYPE,
+from ._capi import (DISPATCH_COLLECT_STATS, DISPATCH_FLOAT_OUTPUT, DISPATCH_KEEP_COUNTERS, DISPATCH_TIME_KERNEL, BAND_DTYPE, HIT_DTYPE, INSTANCE_DTYPE, LIGHT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE, RAY_DTYPE, SURFACE_DTYPE,
                     TRI_DTYPE, VERTEX_DTYPE, DispatchParams, Lens, RRError, SceneConstants, Stats)
 
 FOV_Y = float(np.float32(52.0 / 180.0 * 3.1415))     # RefractionDemo.cpp:559
@@ -197,6 +197,38 @@ def make_instances(transforms=None, meshes=None, masks=None, flags=None, materia
         inst["hitgroup_flags"][i] = (((flags[i] if flags is not None else 0) & 0xff) << 24) | ((int(materials[i]) if materials is not None else 0) & 0xffffff)
         inst["blas"][i] = meshes[i] if meshes is not None else 0
     return inst
+
+
+def glass():
+    """A row of the surface table (Renderer.set_surfaces) that leaves everything to the material row: SURFACE_GLASS"""
+    return np.zeros((), SURFACE_DTYPE)
+
+
+def opaque(albedo, emission=(0, 0, 0), specular=(0, 0, 0)):
+    """A row of the surface table for an opaque surface: albedo times what the lights and the ambient term send, plus emission, plus
+    -- where specular is not (0, 0, 0) -- a mirror child weighted by specular.  RGB triples; albedo and specular >= 0."""
+    r = np.zeros((), SURFACE_DTYPE)
+    r["kind"], r["albedo"], r["emission"], r["specular"] = _capi.SURFACE_OPAQUE, albedo, emission, specular
+    return r
+
+
+def directional_light(towards, radiance, shadow_mask=0xff):
+    """A LIGHT_DTYPE row: a light infinitely far away in direction `towards` (normalised here, in float64, then rounded), with an RGB
+    radiance.  Its shadow rays see the instances whose mask meets shadow_mask."""
+    d = np.asarray(towards, np.float64)
+    n = float(np.sqrt((d * d).sum()))
+    if not np.isfinite(n) or n == 0.0:
+        raise ValueError("directional_light: need a finite direction that is not zero")
+    r = np.zeros((), LIGHT_DTYPE)
+    r["v"], r["kind"], r["radiance"], r["shadow_mask"] = d / n, _capi.LIGHT_DIRECTIONAL, radiance, shadow_mask
+    return r
+
+
+def point_light(position, radiance, shadow_mask=0xff):
+    """A LIGHT_DTYPE row: a point light at `position` whose contribution falls with the square of the distance"""
+    r = np.zeros((), LIGHT_DTYPE)
+    r["v"], r["kind"], r["radiance"], r["shadow_mask"] = position, _capi.LIGHT_POINT, radiance, shadow_mask
+    return r
 
 
 def pack_rays(origin, dir, tmin, tmax, flags=0, instance_mask=0xff):
@@ -754,6 +786,60 @@ class Renderer:
             self._ck(self._L.rr_render_nested_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested_device")
         else:
             self._ck(self._L.rr_render_nested(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested")
+        return _result(outs)
+
+    def set_surfaces(self, table):
+        """The surface table (rr_set_surfaces): a SURFACE_DTYPE array or a list of glass() / opaque(...) rows.  Row r says what an
+        instance of material row r is; rows at or beyond the table's length are glass, and None or an empty table makes every row
+        glass.  Copied; takes effect on the next shade_rays_surfaces / render_surfaces without a rebuild.  set_materials leaves it
+        alone, and only those two calls read it."""
+        t = np.zeros(0, SURFACE_DTYPE) if table is None else np.ascontiguousarray(table, SURFACE_DTYPE).reshape(-1)
+        self._ck(self._L.rr_set_surfaces(self._h, t.ctypes.data if len(t) else None, len(t)), "rr_set_surfaces")
+
+    def set_lights(self, lights=None, ambient=None):
+        """The lights of the opaque surfaces (rr_set_lights): a LIGHT_DTYPE array or a list of directional_light(...) /
+        point_light(...) rows, MAX_LIGHTS at most, and an RGB ambient term (None: 0).  Copied."""
+        t = np.zeros(0, LIGHT_DTYPE) if lights is None else np.ascontiguousarray(lights, LIGHT_DTYPE).reshape(-1)
+        amb = None if ambient is None else np.ascontiguousarray(ambient, np.float32).reshape(3)
+        self._ck(self._L.rr_set_lights(self._h, t.ctypes.data if len(t) else None, len(t), None if amb is None else amb.ctypes.data), "rr_set_lights")
+
+    def shade_rays_surfaces(self, rays, params=None, rgba8=False, ray_counts=False):
+        """shade_rays_nested with opaque hit groups (rr_shade_rays_surfaces): the same rays, material table, outputs and stream
+        order.  A hit on an instance whose row of the surface table is opaque is, after the absorption of the medium crossed, lit by
+        every light it faces and whose shadow ray -- first hit, instances selected by the light's shadow_mask, counted in the ray
+        counts -- finds nothing, adds albedo * (ambient + sum) + emission, and continues as a mirror where specular is not zero.
+        Without a surface table, or with every row glass, this is shade_rays_nested byte for byte."""
+        p = params if params is not None else default_params()
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            t = rays
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("shade_rays_surfaces: the tensor must live on GPU %d" % self.device)
+            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError("shade_rays_surfaces: need a contiguous [n, 12] int32 or float32 tensor")
+            n = t.shape[0]
+            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
+            self._ck(self._L.rr_shade_rays_surfaces_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
+                     "rr_shade_rays_surfaces_device")
+        else:
+            rays = np.ascontiguousarray(rays, RAY_DTYPE)
+            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
+            self._ck(self._L.rr_shade_rays_surfaces(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_surfaces")
+        return _result(outs)
+
+    def render_surfaces(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
+        """render_nested with the ray tree of shade_rays_surfaces (rr_render_surfaces): the same arguments, samples, resolve and
+        outputs, every sample shaded as shade_rays_surfaces shades camera_rays(camera, width, height, *offset_s)."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "render_surfaces: samples must be an int or an [S, 2] array")
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("render_surfaces: negative size")
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_surfaces_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_surfaces_device")
+        else:
+            self._ck(self._L.rr_render_surfaces(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_surfaces")
         return _result(outs)
 
     def set_material_bands(self, iors, weights=None):

@@ -8,8 +8,11 @@ import subprocess
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 HAVE_OBJDUMP = os.path.exists(OBJDUMP)
 
-# every (STACK, PEND, TLAS, E) the ladder of the ray-tree kernels (for_tree_variant, csrc/rr_choice.h) can launch -- k_shade_rays,
-# k_render_samples, k_adaptive_base and k_adaptive_refine: launch_render_fused's ladder without its 22-entry rung
+# every (STACK, PEND, TLAS, E) the ladder of the ray-tree kernels (for_tree_variant, csrc/rr_choice.h) can launch:
+# launch_render_fused's ladder without its 22-entry rung.  Fourteen templates are built as these 20 -- k_shade_rays,
+# k_render_samples, k_adaptive_base, k_adaptive_refine, k_render_lens, k_render_spectral, k_shade_rays_mat, k_render_materials,
+# k_shade_rays_nested, k_render_nested, k_render_composed, k_render_shutter, k_shade_rays_surfaces and k_render_surfaces; tree_matrix.py
+# reaches each of the 20 with a scene
 LAUNCHABLE = [(30, 2, True, "unsigned short"), (39, 2, True, "unsigned short"), (39, 2, False, "unsigned short"),
               (39, 8, False, "unsigned short")] + \
              [(s, 2, t, "unsigned int") for s in (19, 26, 31, 39, 64) for t in (False, True)] + \

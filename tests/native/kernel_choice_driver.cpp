@@ -5,6 +5,7 @@
 //   fused <scene facts as pick> <depth reflect> <dbg_kernel dbg_stack tlas32>   -> stack pend stack16
 //   tree <single stack pend stack16>                         -> STACK PEND TLAS bits: the ray-tree kernels' instantiation
 //                                                               (for_tree_variant), bits = 16 or 32 per stack entry
+//   variant <as fused>                                       -> `tree` of what `fused` answers: the instantiation a ray-tree call launches
 //   key <W H refract reflect depth>                          -> choice_key
 //   new                                                      -> (a fresh class) ok
 //   due <key share no_cull>        -> find + measure_due: due choice seen
@@ -72,6 +73,16 @@ int main()
             in >> single >> v.stack >> v.pend >> stack16;
             v.stack16 = stack16 != 0;
             for_tree_variant(single != 0, v, [](auto t) {
+                using T = decltype(t);
+                return printf("%d %d %d %d\n", T::stack, T::pend, T::tlas ? 1 : 0, (int)(8 * sizeof(typename T::entry)));
+            });
+        } else if (cmd == "variant") {
+            const SceneFacts s = read_scene(in);
+            uint32_t depth;
+            int reflect;
+            in >> depth >> reflect;
+            const DebugFacts d = read_debug(in);
+            for_tree_variant(s.single_identity, fused_variant(s, depth, reflect, d), [](auto t) {
                 using T = decltype(t);
                 return printf("%d %d %d %d\n", T::stack, T::pend, T::tlas ? 1 : 0, (int)(8 * sizeof(typename T::entry)));
             });

@@ -670,7 +670,8 @@ int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, c
  *   rr_set_surfaces: n == 0 clears.  kind a known value; every float finite; albedo and specular >= 0 (emission may be negative).
  *   rr_set_lights:   n <= RR_MAX_LIGHTS; ambient NULL = (0, 0, 0), else three finite floats.  kind a known value; v and radiance
  *                    finite (a negative radiance is allowed); a directional v is not (0, 0, 0) and is used AS GIVEN -- normalise it;
- *                    shadow_mask <= 0xff.
+ *                    shadow_mask <= 0xff.  It also clears the shape table of rr_set_light_shapes (below), whose rows belong with
+ *                    the lights they were set for; none of the four calls here reads that table.
  * A refused table (RR_ERR_INVALID_ARGUMENT) leaves the one in force.
  *
  * The contract.  One rounding per written operation, fmaf only where written, dot is the shader's dot3.  Everything in the nested
@@ -695,8 +696,9 @@ int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, c
  *
  * Reduction: with no surface table, or with every row glass, the four calls equal the _nested calls byte for byte in colours, RGBA8
  * and counts.  The lights are then never read.
- * Not covered: transparent shadows; area lights or environment lighting of opaque surfaces; textures; opaque rows in
- * rr_render_composed / rr_render_shutter, the dispatch kernels and the _materials calls (all of which ignore the surface table).
+ * Not covered: transparent shadows; area lights or environment lighting of opaque surfaces in these four calls; textures; opaque
+ * rows in rr_render_composed / rr_render_shutter, the dispatch kernels and the _materials calls (all of which ignore the surface
+ * table).  Opaque rows through a lens, over scene keys and under lights with an area are rr_render_lit's, below.
  *
  * State and rows as the nested calls: RR_ERR_STATE without a built TLAS or without a material table; RR_ERR_INVALID_ARGUMENT when an
  * instance's row is >= the material table's length or > RR_NESTED_MAX_MATERIAL. */
@@ -816,6 +818,52 @@ int  rr_render_shutter(rr_context* ctx, uint32_t width, uint32_t height, const r
 int  rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
                               const rr_dispatch_params* params, const rr_shutter_sample* samples, uint32_t n_samples,
                               const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
+/* ---- lit shutter frames: opaque surfaces, lights and soft shadows per sample (additive; the ABI version stays 3) -------------------
+ * rr_render_shutter's frame over rr_shade_rays_surfaces' hit groups: the lit scene through the lens, with motion blur, dispersion
+ * and -- one more per-sample entry -- a point on every light, so that the fold over the samples which integrates the aperture and
+ * the shutter integrates the lights' areas too.  No random numbers: every sample is stated by its record.
+ *
+ * Shapes.  rr_set_light_shapes gives light i of the set in force (rr_set_lights) the two edge vectors ex, ey of row i.  n == 0
+ * clears the table; any other n must equal the number of lights in force.  RR_ERR_INVALID_ARGUMENT: another n, a NULL table with
+ * n > 0, an ex or ey that is not finite, a non-zero pad; a refused table leaves the one in force.  rr_set_lights clears the table.
+ * The call waits for the context's stream, as rr_set_lights does; the table travels by value with every launch.  Only the two
+ * render calls below read it.
+ *
+ * Moved lights.  rr_host_moved_lights(lights, shapes, n, lu, lv, out) states the only new arithmetic, in fp32:
+ *   out[i].v[c] = fmaf(lv, shapes[i].ey[c], fmaf(lu, shapes[i].ex[c], lights[i].v[c]))        each fmaf rounded once
+ * and copies everything else of row i.  With shapes == NULL the rows are copied unchanged (a -0 in v stays -0).  Both light kinds
+ * are moved alike; a moved directional v is used AS GIVEN, as rr_set_lights has it.  Needs no context; out may be lights.
+ * RR_ERR_INVALID_ARGUMENT for a NULL lights or out with n > 0.
+ *
+ * The frame.  rr_render_lit[_device] takes rr_render_shutter[_device]'s arguments with rr_lit_sample records: a shutter sample whose
+ * pad has a meaning, the light offset (lu, lv), each in [-1, 1].  Sample k is shaded as rr_shade_rays_surfaces shades the rays of
+ * rr_host_lens_rays for sample k (without a lens: rr_host_camera_rays) in the scene of key samples[k].key, under the band table
+ * samples[k].band, the surface table and ambient term in force, and the lights
+ *   rr_host_moved_lights(lights in force, shape table in force or NULL, n, light_offset_k[0], light_offset_k[1]).
+ * The pixel resolves as rr_render_shutter's, ((w_0 * c_0 + w_1 * c_1) + ...) / n_samples with every operation rounded once; shadow
+ * rays count in n_rays.  Outputs, tone mapping, device pointers, alignment, culling of background blocks (a culled block is one Miss
+ * per sample and looks at no table and no light) and RR_DISPATCH_DEBUG_NO_CULL as rr_render_shutter.  Nothing is allocated, copied
+ * or waited for by the _device variant.
+ * Refused: everything rr_render_shutter refuses, with the same codes (its pad check has nothing left to look at); and with
+ * RR_ERR_INVALID_ARGUMENT a light offset outside [-1, 1], NaN included, whether or not a shape table is set; a sample for which a
+ * moved v is not finite, or for which a moved directional light has v == (0, 0, 0).
+ * Reductions, byte for byte in colours, RGBA8 and counts: with no surface table, or with every row glass, rr_render_shutter on the
+ * same records; with one key that is a capture of the live scene, no lens, no band set and no shape table (or one of zeros),
+ * rr_render_surfaces on the samples' positions.
+ * Stated limits: a shaped light is a rectangle of point emitters -- there is no cosine at the light and no normalisation by its
+ * area; the caller's radiance is per sample, and the / n_samples of the resolve averages it.  Any accepted hit still occludes.
+ * Not covered: a camera per key, textures, environment lighting of opaque surfaces, transparent shadows. */
+typedef struct rr_light_shape { float ex[3]; float ey[3]; uint32_t pad[2]; } rr_light_shape;                                        /* 32 bytes */
+typedef struct rr_lit_sample { float offset[2]; float lens_offset[2]; uint32_t band; uint32_t key; float light_offset[2]; } rr_lit_sample; /* 32 bytes */
+int  rr_set_light_shapes(rr_context* ctx, const rr_light_shape* shapes, uint32_t n);
+int  rr_host_moved_lights(const rr_light* lights, const rr_light_shape* shapes, uint32_t n, float lu, float lv, rr_light* out);
+int  rr_render_lit(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                   const rr_dispatch_params* params, const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens,
+                   float* rgba32f, uint8_t* rgba8, uint32_t* n_rays);
+int  rr_render_lit_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
+                          const rr_dispatch_params* params, const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens,
+                          void* d_rgba32f, void* d_rgba8, void* d_n_rays);
 
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel

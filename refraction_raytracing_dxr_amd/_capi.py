@@ -71,6 +71,11 @@ MAX_LIGHTS = 8                           # RR_MAX_LIGHTS
 SURFACE_DTYPE = np.dtype([("kind", "<u4"), ("albedo", "<f4", 3), ("emission", "<f4", 3), ("specular", "<f4", 3), ("pad", "<u4", 2)])
 LIGHT_DTYPE = np.dtype([("v", "<f4", 3), ("kind", "<u4"), ("radiance", "<f4", 3), ("shadow_mask", "<u4")])
 assert SURFACE_DTYPE.itemsize == 48 and LIGHT_DTYPE.itemsize == 32
+# rr_light_shape: the two edges light i moves along (set_light_shapes); rr_lit_sample: one sample of render_lit -- a shutter sample
+# whose pad is the light offset
+LIGHT_SHAPE_DTYPE = np.dtype([("ex", "<f4", 3), ("ey", "<f4", 3), ("pad", "<u4", 2)])
+LIT_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("key", "<u4"), ("light_offset", "<f4", 2)])
+assert LIGHT_SHAPE_DTYPE.itemsize == 32 and LIT_SAMPLE_DTYPE.itemsize == 32 and LIT_SAMPLE_DTYPE.fields["light_offset"][1] == 24
 MAX_SCENE_KEYS = 16                      # RR_MAX_SCENE_KEYS: scene keys a context holds (capture_scene_key)
 ALL_SCENE_KEYS = 0xFFFFFFFF              # RR_ALL_SCENE_KEYS: release_scene_key's "every key"
 
@@ -227,6 +232,12 @@ SYMBOLS = {
                                     C.POINTER(Lens), _P, _P, _P]),
     "rr_render_shutter_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
                                            C.POINTER(Lens), _P, _P, _P]),
+    "rr_set_light_shapes": (C.c_int, [_P, _P, C.c_uint32]),
+    "rr_host_moved_lights": (C.c_int, [_P, _P, C.c_uint32, C.c_float, C.c_float, _P]),
+    "rr_render_lit": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                C.POINTER(Lens), _P, _P, _P]),
+    "rr_render_lit_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
+                                       C.POINTER(Lens), _P, _P, _P]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

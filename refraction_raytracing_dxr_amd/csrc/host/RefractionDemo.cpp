@@ -19,6 +19,9 @@ std::string g_err;
 void* g_comm = nullptr;                      // RCCL communicator of the sharded form
 int g_rank = 0, g_world = 1;
 std::vector<rr_material> g_mats;             // the table of setMaterials: drawFrameComposed derives its band set from it
+std::vector<rr_material> g_table;            // the table in force where it is not g_mats: setFloorAndLights appends the floor's row
+std::vector<rr_instance_desc> g_floor_inst;  // the two instances of setFloorAndLights: drawFrameLit turns them per key
+std::vector<rr_light> g_lights;              // the lights of setFloorAndLights: setLightSoftness shapes the point lights among them
 bool g_shutter_tlas = false;                 // drawFrameShutter built the top level it updates per key
 
 int fail(int code, const char* what)
@@ -141,6 +144,7 @@ int setMaterials(const rr_material* mats, int n)
     const int rc = rr_set_materials(g_ctx, mats, (uint32_t)n);
     if (rc != RR_OK) return fail(rc, "rr_set_materials");
     g_mats.assign(mats, mats + n);
+    g_table.clear();
     return RR_OK;
 }
 
@@ -226,7 +230,22 @@ int setFloorAndLights(const float albedo[3], float specular, const rr_light* lig
     if ((rc = rr_set_surfaces(g_ctx, surf.data(), (uint32_t)surf.size())) != RR_OK) return fail(rc, "rr_set_surfaces");
     static const float ambient[3] = { 0.05f, 0.05f, 0.05f };
     if ((rc = rr_set_lights(g_ctx, lights, (uint32_t)n_lights, ambient)) != RR_OK) return fail(rc, "rr_set_lights");
+    g_table = mats;
+    g_floor_inst.assign(inst, inst + 2);
+    g_lights.assign(lights, lights + n_lights);
     return RR_OK;
+}
+
+int setLightSoftness(float half_edge)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (!(half_edge >= 0.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "setLightSoftness: need a half-edge >= 0");
+    std::vector<rr_light_shape> shapes(g_lights.size());
+    std::memset(shapes.data(), 0, shapes.size() * sizeof(rr_light_shape));
+    for (size_t i = 0; i < g_lights.size(); ++i)
+        if (g_lights[i].kind == RR_LIGHT_POINT) { shapes[i].ex[0] = half_edge; shapes[i].ey[2] = half_edge; }
+    const int rc = rr_set_light_shapes(g_ctx, shapes.data(), (uint32_t)shapes.size());
+    return rc != RR_OK ? fail(rc, "rr_set_light_shapes") : RR_OK;
 }
 
 int drawFrameSurfaces(int spp)
@@ -247,12 +266,13 @@ int drawFrameSurfaces(int spp)
 // the same for every row
 static int setBandSet(int n_bands, float abbe)
 {
-    const int rows = (int)g_mats.size();
+    const std::vector<rr_material>& table = g_table.empty() ? g_mats : g_table;
+    const int rows = (int)table.size();
     int rc;
     rr_band one[RR_MAX_SAMPLES];
     std::vector<float> iors((size_t)n_bands * rows), weights((size_t)n_bands * 3);
     for (int r = 0; r < rows; ++r) {
-        if ((rc = rr_host_spectral_bands((uint32_t)n_bands, g_mats[r].ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
+        if ((rc = rr_host_spectral_bands((uint32_t)n_bands, table[r].ior, abbe, one)) != RR_OK) return fail(rc, "rr_host_spectral_bands");
         for (int b = 0; b < n_bands; ++b) {
             iors[(size_t)b * rows + r] = one[b].ior;
             for (int ch = 0; ch < 3; ++ch) weights[(size_t)b * 3 + ch] = one[b].weight[ch];
@@ -343,6 +363,84 @@ int drawFrameShutter(int spp, const rr_lens* lens, int n_bands, float abbe, int 
         return fail(rc, "rr_render_shutter");
     printf("shutter frame: %d positions x %d keys over %g rad x %d bands (Abbe number %g) of %d materials, %s, nested media\n", spp, n_keys, dt, n_bands,
            abbe, rows, lens && lens->radius > 0.0f ? "thin lens" : "pinhole");
+    return RR_OK;
+}
+
+// the built-in light offsets: rr.light_pattern of the Python layer -- point k of n is (2 (k + 0.5) / n - 1, 2 (phi2(k) + 0.5 / m) - 1),
+// phi2 the base-2 radical inverse, m the smallest power of two >= n, in double, rounded once
+static void lightPattern(int n, float* out)
+{
+    int m = 1;
+    while (m < n) m *= 2;
+    for (int k = 0; k < n; ++k) {
+        double phi = 0.0, f = 0.5;
+        for (int i = k; i; i >>= 1) { phi += f * (double)(i & 1); f *= 0.5; }
+        out[2 * k] = (float)(2.0 * (k + 0.5) / n - 1.0);
+        out[2 * k + 1] = (float)(2.0 * (phi + 0.5 / m) - 1.0);
+    }
+}
+
+int drawFrameLit(int spp, const rr_lens* lens, int n_bands, float abbe, int n_keys, float dt)
+{
+    if (!g_ctx) return fail(RR_ERR_STATE, "initialize first");
+    if (g_mats.empty()) return fail(RR_ERR_STATE, "drawFrameLit: setMaterials first");
+    if (n_bands < 1) n_bands = 1;
+    const int keys = n_keys < 1 ? 1 : n_keys;
+    if (spp <= 0 || keys > RR_MAX_SCENE_KEYS || spp * (long long)keys * n_bands > RR_MAX_SAMPLES)
+        return fail(RR_ERR_INVALID_ARGUMENT, "drawFrameLit: spp must be 1, 2, 4, 8 or 16, keys at most 16 and spp * keys * bands at most 64");
+    rr_scene_constants sc;
+    int rc = rr_host_camera_orbit(g_angle, g_opt.fov_y, g_opt.aspect, g_opt.zn, g_opt.zf, &sc);
+    if (rc != RR_OK) return fail(rc, "rr_host_camera_orbit");
+    const int n = spp * keys * n_bands;
+    float pos[2 * RR_MAX_SAMPLES], lpos[2 * RR_MAX_SAMPLES], gpos[2 * RR_MAX_SAMPLES];
+    if ((rc = rr_host_sample_pattern((uint32_t)spp, pos)) != RR_OK) return fail(rc, "rr_host_sample_pattern");
+    if ((rc = rr_host_lens_pattern((uint32_t)n, lpos)) != RR_OK) return fail(rc, "rr_host_lens_pattern");
+    lightPattern(spp, gpos);
+    if ((rc = setBandSet(n_bands, abbe)) != RR_OK) return rc;
+    if (n_keys < 1) {                                           // no shutter: the frame's scene as it stands is key 0
+        if ((rc = rr_capture_scene_key(g_ctx, 0)) != RR_OK) return fail(rc, "rr_capture_scene_key");
+    } else {
+        // drawFrameShutter's keys with everything that stands in the scene turned: the mesh and, where there is one, the floor.  The
+        // lights stay where they are, like the environment map
+        std::vector<rr_instance_desc> base = g_floor_inst;
+        if (base.empty()) {
+            rr_instance_desc one;
+            std::memset(&one, 0, sizeof one);
+            one.transform[0] = one.transform[5] = one.transform[10] = 1.0f;
+            one.instance_id_mask = 1u << 24;
+            one.hitgroup_flags = RR_INSTANCE_FLAG_TRIANGLE_CULL_DISABLE << 24;
+            one.blas = cubeMesh.raytracingGeometry().mesh_id;
+            base.push_back(one);
+        }
+        for (int j = 0; j < n_keys; ++j) {
+            const float d = n_keys > 1 ? dt * (float)j / (float)(n_keys - 1) : 0.0f, c = std::cos(d), s = std::sin(d);
+            std::vector<rr_instance_desc> inst = base;
+            for (size_t i = 0; i < inst.size(); ++i)
+                for (int col = 0; col < 4; ++col) {             // rows 0 and 2 of R_y(d) * [A | t]
+                    const float a0 = base[i].transform[col], a2 = base[i].transform[8 + col];
+                    inst[i].transform[col] = c * a0 + s * a2;
+                    inst[i].transform[8 + col] = c * a2 - s * a0;
+                }
+            if ((rc = rr_build_tlas(g_ctx, inst.data(), (uint32_t)inst.size())) != RR_OK) return fail(rc, "rr_build_tlas");
+            if ((rc = rr_capture_scene_key(g_ctx, (uint32_t)j)) != RR_OK) return fail(rc, "rr_capture_scene_key");
+        }
+    }
+    g_angle += g_opt.angle_step;
+    rr_lit_sample samples[RR_MAX_SAMPLES];
+    memset(samples, 0, sizeof samples);
+    for (int k = 0; k < n; ++k) {                               // sample (a * keys + j) * n_bands + b: position a, key j, band b, lens point k, light point a
+        const int a = k / (keys * n_bands);
+        samples[k].offset[0] = pos[2 * a]; samples[k].offset[1] = pos[2 * a + 1];
+        samples[k].lens_offset[0] = lpos[2 * k]; samples[k].lens_offset[1] = lpos[2 * k + 1];
+        samples[k].light_offset[0] = gpos[2 * a]; samples[k].light_offset[1] = gpos[2 * a + 1];
+        samples[k].key = (uint32_t)(k / n_bands % keys);
+        samples[k].band = (uint32_t)(k % n_bands);
+    }
+    if ((rc = rr_render_lit(g_ctx, (uint32_t)g_opt.width, (uint32_t)g_opt.height, &sc, &g_opt.dispatch, samples, (uint32_t)n, lens, nullptr,
+                            g_back.data(), nullptr)) != RR_OK)
+        return fail(rc, "rr_render_lit");
+    printf("lit frame: %d positions x %d keys over %g rad x %d bands (Abbe number %g) of %d materials under %d lights, %s\n", spp, keys, n_keys < 1 ? 0.0f : dt,
+           n_bands, abbe, (int)g_mats.size(), (int)g_lights.size(), lens && lens->radius > 0.0f ? "thin lens" : "pinhole");
     return RR_OK;
 }
 
@@ -488,6 +586,9 @@ void shutdown()
         rr_destroy(g_ctx); g_ctx = nullptr;
     }
     g_mats.clear();
+    g_table.clear();
+    g_floor_inst.clear();
+    g_lights.clear();
 }
 
 } // namespace RefractionDemo

@@ -60,6 +60,12 @@ int drawFrameComposed(int spp, const rr_lens* lens, int n_bands, float abbe);
 // so key j holds the mesh turned by the opposite angle about y under the frame's one camera; the environment map does not turn with
 // it.  From the first call on the scene has a top level (one instance, updated per key).  Prints one line that names the frame
 int drawFrameShutter(int spp, const rr_lens* lens, int n_bands, float abbe, int n_keys, float dt);
+// drawFrameShutter over the opaque hit groups (rr_render_lit): the floor and lights of setFloorAndLights, if any, through the lens;
+// n_keys < 1: no shutter, the frame's scene is captured as key 0.  With keys the mesh and the floor turn together, the lights stay.
+// Position a of the spp takes point a of the built-in light pattern; setLightSoftness(S) makes every point light a square of
+// half-edge S in the xz-plane (rr_set_light_shapes), 0 a point again
+int setLightSoftness(float half_edge);
+int drawFrameLit(int spp, const rr_lens* lens, int n_bands, float abbe, int n_keys, float dt);
 // drawFrameSamples with base samples for every pixel and the rest of the spp only where the base samples show contrast above
 // threshold (rr_render_adaptive); refined (may be null) receives the number of pixels that took all spp samples
 int drawFrameAdaptive(int base, int spp, float threshold, uint64_t* refined);

@@ -1,4 +1,4 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_surfaces, rr_set_lights, rr_shade_rays_surfaces*, rr_render_surfaces*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_env_lookup.
+// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_surfaces, rr_set_lights, rr_shade_rays_surfaces*, rr_render_surfaces*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_set_light_shapes, rr_host_moved_lights, rr_render_lit*, rr_env_lookup.
 // A host variant stages its arrays through the context's scratch around the launch its device variant makes.
 #include "rr_context.h"
 
@@ -448,11 +448,11 @@ int check_shutter(rr_context* ctx, ShutterReq& q, rr_dispatch_params& p, bool ha
     return RR_OK;
 }
 
-// launches a checked shutter frame: out holds device pointers.  As composed_impl: nothing allocated, copied or waited for -- the
-// key records are on the device since their capture.  The rectangle is that of the union of the used keys' boxes; the kernel
-// variant comes from fused_variant over the used keys' facts merged: the deepest stack need, the largest mesh and pools (16-bit
-// stack entries only where every key's references fit them)
-int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, const ShadeOut& out)
+// what a shutter frame's launch takes from the keys it uses.  The rectangle is that of the union of the used keys' boxes; the
+// kernel variant comes from fused_variant over the used keys' facts merged: the deepest stack need, the largest mesh and pools
+// (16-bit stack entries only where every key's references fit them)
+struct ShutterFrame { FrameArgs f; bool single_identity; };
+ShutterFrame shutter_frame(rr_context* ctx, const ShutterReq& q, const ShutterTables& t)
 {
     float box[6] = { 3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f };
     SceneFacts sf = { false, 0, 0, 0, 0, false };
@@ -466,13 +466,81 @@ int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, c
         sf.pool_nodes = std::max(sf.pool_nodes, sk.facts.pool_nodes);
         sf.pool_refs = std::max(sf.pool_refs, sk.facts.pool_refs);
     }
-    const FrameArgs f = frame_args_of(ctx, q.c.s, q.c.lens, box, sf);
+    return { frame_args_of(ctx, q.c.s, q.c.lens, box, sf), sf.single_identity };
+}
+
+// launches a checked shutter frame: out holds device pointers.  As composed_impl: nothing allocated, copied or waited for -- the
+// key records are on the device since their capture
+int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, const ShadeOut& out)
+{
+    const ShutterFrame m = shutter_frame(ctx, q, t);
+    const FrameArgs& f = m.f;
     const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
     const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
-    if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), sf.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, mats,
+    if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), m.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, mats,
                                              ctx->n_mats, weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out.f32, out.rgba8,
                                              out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.c.s.who, e);
+    return RR_OK;
+}
+
+// a light's v, one component, moved by a sample's light offset (lu, lv) over its shape: the arithmetic rr_host_moved_lights states
+// and k_render_lit does (rr_render_lit.h), each fmaf rounded once
+inline float moved_v(float v, float ex, float ey, float lu, float lv) { return std::fmaf(lv, ey, std::fmaf(lu, ex, v)); }
+
+// a lit frame: a shutter frame over the surface tree whose samples each carry a light offset.  rec: the samples as shutter records
+// (what check_shutter reads), lgt: the light offsets as the kernel takes them
+struct LitReq { ShutterReq s; const rr_lit_sample* samples; };
+struct LitTables { ShutterTables s; SampleOffsets lgt; rr_shutter_sample rec[RR_MAX_SAMPLES]; };
+
+// what both variants of rr_render_lit refuse before they look at their outputs' memory: what rr_render_shutter refuses, then the
+// light offsets (whether or not a shape table is set), then per sample the lights as rr_host_moved_lights moves them; fills the tables
+int check_lit(rr_context* ctx, LitReq& q, rr_dispatch_params& p, bool have_colour, LitTables& t)
+{
+    const std::string w(q.s.c.s.who);
+    const uint32_t n = q.s.c.s.n_samples;
+    if (q.samples && n >= 1 && n <= RR_MAX_SAMPLES) {           // (otherwise check_shutter refuses, in its own order)
+        for (uint32_t k = 0; k < n; ++k) {
+            const rr_lit_sample& s = q.samples[k];
+            t.rec[k] = rr_shutter_sample{ { s.offset[0], s.offset[1] }, { s.lens_offset[0], s.lens_offset[1] }, s.band, s.key, { 0u, 0u } };
+        }
+        q.s.samples = t.rec;
+    }
+    if (int r = check_shutter(ctx, q.s, p, have_colour, t.s)) return r;
+    memset(&t.lgt, 0, sizeof t.lgt);
+    const LightsDev& L = ctx->lights;
+    const LightShapesDev& S = ctx->light_shapes;
+    for (uint32_t k = 0; k < n; ++k) {
+        const rr_lit_sample& s = q.samples[k];
+        for (int i = 0; i < 2; ++i) {
+            if (!(s.light_offset[i] >= -1.0f && s.light_offset[i] <= 1.0f))     // (NaN fails both comparisons)
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": light offsets must lie in [-1, 1]").c_str());
+            t.lgt.v[2 * k + i] = s.light_offset[i];
+        }
+        for (uint32_t i = 0; i < L.n; ++i) {
+            float v[3];                                         // (rr_host_moved_lights' arithmetic, moved_v)
+            for (int ch = 0; ch < 3; ++ch) v[ch] = S.on ? moved_v(L.l[i].v[ch], S.s[i].ex[ch], S.s[i].ey[ch], s.light_offset[0], s.light_offset[1]) : L.l[i].v[ch];
+            if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]))
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a light moved by a sample's offset has a position or direction that is not finite").c_str());
+            if (L.l[i].kind == RR_LIGHT_DIRECTIONAL && v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f)
+                return fail(ctx, RR_ERR_INVALID_ARGUMENT, (w + ": a directional light moved by a sample's offset has the direction zero").c_str());
+        }
+    }
+    return RR_OK;
+}
+
+// launches a checked lit frame: out holds device pointers.  As shutter_impl, whose merge of the used keys' facts this is: nothing
+// allocated, copied or waited for -- the surface table is on the device, the lights and their shapes travel by value
+int lit_impl(rr_context* ctx, const LitReq& q, const LitTables& t, const ShadeOut& out)
+{
+    const ShutterFrame m = shutter_frame(ctx, q.s, t.s);
+    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
+    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
+    if (hipError_t e = launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
+                                         t.s.key, mats, ctx->n_mats, weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
+                                         ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out.f32, out.rgba8, out.n_rays, m.f.v.stack,
+                                         m.f.v.pend, m.f.v.stack16, ctx->stream))
+        return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
     return RR_OK;
 }
 } // namespace
@@ -986,6 +1054,7 @@ int rr_set_lights(rr_context* ctx, const rr_light* lights, uint32_t n, const flo
     // the set travels by value with every launch: those in flight hold their own copy.  Waiting keeps the setters alike
     RR_HIP(hipStreamSynchronize(ctx->stream));
     ctx->lights = t;
+    ctx->light_shapes = LightShapesDev{};                       // (row i belonged with the old light i)
     return RR_OK;
 }
 
@@ -1111,6 +1180,69 @@ int rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, c
     if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
                                     "rr_render_shutter_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
     return shutter_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+}
+
+int rr_set_light_shapes(rr_context* ctx, const rr_light_shape* shapes, uint32_t n)
+{
+    if (int r = use_device(ctx)) return r;
+    LightShapesDev t;
+    memset(&t, 0, sizeof t);
+    if (n) {
+        if (!shapes) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_light_shapes: null shapes");
+        if (n != ctx->lights.n) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_light_shapes: need one shape per light in force (rr_set_lights), or n == 0");
+        for (uint32_t i = 0; i < n; ++i) {
+            const rr_light_shape& s = shapes[i];
+            if (s.pad[0] || s.pad[1]) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_light_shapes: a shape's pad must be zero");
+            for (int ch = 0; ch < 3; ++ch) {
+                if (!std::isfinite(s.ex[ch]) || !std::isfinite(s.ey[ch])) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_light_shapes: every ex and ey must be finite");
+                t.s[i].ex[ch] = s.ex[ch]; t.s[i].ey[ch] = s.ey[ch];
+            }
+        }
+        t.on = 1u;
+    }
+    // as the lights: the table travels by value with every launch, and waiting keeps the setters alike
+    RR_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->light_shapes = t;
+    return RR_OK;
+}
+
+int rr_host_moved_lights(const rr_light* lights, const rr_light_shape* shapes, uint32_t n, float lu, float lv, rr_light* out)
+{
+    if (n && (!lights || !out)) return RR_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n; ++i) {
+        rr_light m = lights[i];
+        if (shapes) for (int ch = 0; ch < 3; ++ch) m.v[ch] = moved_v(m.v[ch], shapes[i].ex[ch], shapes[i].ey[ch], lu, lv);
+        out[i] = m;
+    }
+    return RR_OK;
+}
+
+int rr_render_lit(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                  const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    LitReq q = { { { { "rr_render_lit", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, nullptr }, samples };
+    LitTables t;
+    if (int r = check_lit(ctx, q, p, rgba32f || rgba8, t)) return r;
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
+    if (int r = lit_impl(ctx, q, t, out)) return r;
+    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+}
+
+int rr_render_lit_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
+                         const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
+{
+    if (int r = use_device(ctx)) return r;
+    rr_dispatch_params p = params_or_default(params);
+    LitReq q = { { { { "rr_render_lit_device", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, nullptr }, samples };
+    LitTables t;
+    if (int r = check_lit(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
+    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
+                                    "rr_render_lit_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+    return lit_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -258,10 +258,13 @@ struct rr_context {
     DevBuf<MatDev>     d_mats;
     uint32_t n_mats = 0, max_material = 0;
     // the surface table (rr_set_surfaces): n_surfs rows at the head of d_surfs, 0 = none set (every row is glass); and the lights
-    // with the ambient term (rr_set_lights), which the surface kernels take by value.  Only the rr_*_surfaces calls read them
+    // with the ambient term (rr_set_lights), which the surface kernels take by value.  Only the rr_*_surfaces calls and
+    // rr_render_lit read them.  light_shapes: the shape table (rr_set_light_shapes), row i with light i, on == 0 while none is set;
+    // rr_set_lights clears it, and only rr_render_lit reads it
     DevBuf<SurfDev>    d_surfs;
     uint32_t n_surfs = 0;
     LightsDev lights = {};
+    LightShapesDev light_shapes = {};
     // the band set of rr_render_composed (rr_set_material_bands): n_bands copies of the table in force, each with a column of
     // indices of its own, one behind the other at the head of d_band_mats, and three weights per band at the head of d_band_w;
     // n_bands == 0: none set, the one band is d_mats itself with the weights of d_band_one (1, 1, 1; made with the first table).

@@ -131,6 +131,16 @@ hipError_t launch_render_shutter(const KeyDev* keys, bool single_identity, const
                                  const MatDev* band_mats, uint32_t n_rows, const float* band_w, const float4* env, int32_t env_w, int32_t env_h,
                                  uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
                                  hipStream_t s);
+// ---- rr_render_lit.hip: lit shutter frames (rr_render_lit[_device]): launch_render_shutter over the ray tree of
+// launch_render_surfaces, with the lights per sample.  surfs, n_surfs, lights: as launch_render_surfaces.  shapes: per light the two
+// edges its position (or direction) moves along, by value; lgt: per sample the light offset (lu, lv), laid out as off -- sample k is
+// lit by light i at fmaf(lv_k, ey_i, fmaf(lu_k, ex_i, v_i)) per component, or at v_i where shapes.on == 0 (rr_render_lit.h).  That
+// every moved v is finite and no moved direction is zero the host checks
+hipError_t launch_render_lit(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
+                             const SampleOffsets& loff, const SampleOffsets& lgt, const LensDev& lens, const SampleBands& band, const SampleKeys& key,
+                             const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs, uint32_t n_surfs,
+                             const LightsDev& lights, const LightShapesDev& shapes, const float4* env, int32_t env_w, int32_t env_h,
+                             uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

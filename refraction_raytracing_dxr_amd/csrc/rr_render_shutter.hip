@@ -22,19 +22,6 @@ static_assert(sizeof(SampleKeys) == 64, "SampleKeys: one byte per sample, four t
 static_assert(sizeof(DispatchDev) + sizeof(CamDev) + 2 * sizeof(SampleOffsets) + sizeof(LensDev) + sizeof(SampleBands) + sizeof(SampleKeys) +
               7 * sizeof(uint32_t) + 7 * sizeof(void*) + 64 <= 4096, "k_render_shutter: the kernel arguments do not fit the kernarg segment");
 
-// A pointer read from a record in memory is a generic pointer to the compiler, which the tree would dereference with flat_load --
-// through the aperture check and both memory counters, the LDS stacks' among them -- where k_render_composed, whose pointers are
-// kernel arguments and known to be global, uses global_load with a scalar base.  The record's pointers are hipMalloc'ed device
-// memory: in_global says so, by way of the global address space and back.  The empty statement between the two casts keeps the
-// pair from being folded away before the address spaces are inferred; it holds the pointer in scalar registers, where it is anyway
-// (the record has a scalar address), and a pointer the build does not use is dropped with it.
-template <class T> __device__ __forceinline__ const T* in_global(const T* p)
-{
-    const __attribute__((address_space(1))) T* g = (const __attribute__((address_space(1))) T*)p;
-    asm("" : "+s"(g));
-    return (const T*)g;
-}
-
 // Arguments as k_render_composed, with keys / key in place of sc / mat0 (a.hx0..hy1: the rectangle of the union of the used keys'
 // bounds) and the context's environment map beside them.  key: per sample the key it is traced in, a byte each, four to a word.
 template <int STACK, int PEND, bool TLAS, class E>

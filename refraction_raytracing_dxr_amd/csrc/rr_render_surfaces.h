@@ -33,8 +33,9 @@
 // The traversal stack is free while a hit is being shaded, so a shadow ray walks on the same LDS column.  The light rows sit in the
 // kernel-argument segment (LightsDev, rr_types.h) and every loop over them has a wave-uniform index, so they arrive through scalar
 // loads; the surface row differs per lane and comes through vector loads, as mats does.
-// Not covered: transparent shadows, area lights or environment lighting of opaque surfaces, textures, opaque rows in the composed and
-// shutter frames, the dispatch kernels and the _materials calls.
+// Not covered: transparent shadows, environment lighting of opaque surfaces, textures, opaque rows in the composed and shutter
+// frames, the dispatch kernels and the _materials calls.  (Opaque rows over scene keys, through a lens and under lights with an
+// area: rr_render_lit.h.)
 #pragma once
 #include "rr_render_nested.h"
 

@@ -174,6 +174,17 @@ struct LightsDev {
 };
 static_assert(sizeof(LightDev) == 32 && sizeof(LightsDev) == 8 * 32 + 16, "LightsDev must be 8 rows and four words");
 
+// The shapes of the lights (rr_set_light_shapes) as the lit kernels take them, by value beside LightsDev: row i spans light i's
+// rectangle, and a sample's light offset (lu, lv) moves the light's v to fmaf(lv, ey, fmaf(lu, ex, v)) per component.  on == 0: no
+// table is set and v is used as it is (rr_host_moved_lights states the same on the host)
+struct LightShapeDev { float ex[3], ey[3]; };
+struct LightShapesDev {
+    LightShapeDev s[MAX_LIGHTS];
+    uint32_t on;
+    uint32_t pad[3];
+};
+static_assert(sizeof(LightShapesDev) == 8 * 24 + 16, "LightShapesDev must be 8 rows of (ex, ey) and four words");
+
 // exp(x) for x <= 0 (Beer-Lambert: x = -(sigma * t)), the one definition host and device share, in fp32 with every fused
 // operation written as fmaf (Cephes' expf: x = k ln 2 + r with ln 2 split in two, a degree-5 polynomial in r, 2^k from the exponent
 // bits).  Exactly 1 for +0 and -0; 0 from -87 down (and for a NaN); k >= -126 above the cut, so 2^k is a normal number.

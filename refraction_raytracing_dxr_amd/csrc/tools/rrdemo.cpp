@@ -13,6 +13,7 @@
 //          [--light x,y,z:R,G,B | --light @x,y,z:R,G,B]            (with --nested --materials, up to 8 times: a directional light towards (x, y, z), or with @ a point light at (x, y, z), of that radiance)
 //          [--compose]                                             (with --spp N and --materials: --lens, --dispersion and --nested together, rr_render_composed; the Abbe number applies to every row)
 //          [--shutter K:DT]                                        (with --compose: every frame over K scene keys spread over DT radians of the orbit, rr_render_shutter; N x K x BANDS <= 64)
+//          [--lit [--soft S]]                                      (with --compose, with or without --shutter: --floor and --light through the lens, rr_render_lit; every point light a square of half-edge S in the xz-plane)
 //          [--gpus N [--frames-per-gather F]]                      (one process per GPU: tiles, one RCCL gather per F frames)
 #include <chrono>
 #include <cmath>
@@ -79,7 +80,8 @@ int main(int argc, char** argv)
     RefractionDemo::Options opt;
     int frames = 1, fpd = 1, in_flight = 2, gpus = 0, rank = -1, fpg = 16, spp = 0, base = 0, n_bands = 0, n_keys = 0;
     float threshold = 0.0f, lens_radius = 0.0f, lens_focus = 0.0f, abbe = 30.0f, shutter_dt = 0.0f;
-    bool have_lens = false, pump = false, stream = false, nested = false, compose = false;
+    bool have_lens = false, pump = false, stream = false, nested = false, compose = false, lit = false, have_soft = false;
+    float soft = 0.0f;
     std::vector<rr_material> materials;
     std::vector<rr_light> lights;
     bool have_floor = false;
@@ -95,6 +97,12 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--stream")) stream = true;
         else if (!strcmp(argv[i], "--nested")) nested = true;
         else if (!strcmp(argv[i], "--compose")) compose = true;
+        else if (!strcmp(argv[i], "--lit")) lit = true;
+        else if (arg("--soft")) {
+            int used = 0;
+            if (sscanf(argv[++i], "%f%n", &soft, &used) != 1 || argv[i][used] != 0 || !(soft >= 0.0f) || !std::isfinite(soft)) { fprintf(stderr, "--soft takes S, a finite half-edge >= 0\n"); return 2; }
+            have_soft = true;
+        }
         else if (arg("--frames-per-dispatch")) fpd = atoi(argv[++i]);
         else if (arg("--in-flight")) in_flight = atoi(argv[++i]);
         else if (arg("--spp")) {
@@ -163,7 +171,7 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]...]] [--compose [--shutter K:DT]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]...]] [--compose [--shutter K:DT] [--lit [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]... [--soft S]]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (compose) {          // the frames that refuse each other below, in one call: a lens and dispersion on the nested-media tree
@@ -188,8 +196,10 @@ int main(int argc, char** argv)
     }
     if (nested && materials.empty()) { fprintf(stderr, "--nested needs --materials\n"); return 2; }
     const bool surfaces = have_floor || !lights.empty();
-    if (surfaces && (!nested || materials.empty())) { fprintf(stderr, "--floor and --light need --nested --materials\n"); return 2; }
-    if (surfaces && (compose || n_keys || base || have_lens || n_bands)) { fprintf(stderr, "--floor and --light render with the nested tree alone: they cannot be combined with --compose, --shutter, --adaptive, --lens or --dispersion\n"); return 2; }
+    if (lit && !compose) { fprintf(stderr, "--lit needs --compose\n"); return 2; }
+    if (have_soft && !lit) { fprintf(stderr, "--soft S needs --lit\n"); return 2; }
+    if (surfaces && !lit && (!nested || materials.empty())) { fprintf(stderr, "--floor and --light need --nested --materials\n"); return 2; }
+    if (surfaces && !lit && (compose || n_keys || base || have_lens || n_bands)) { fprintf(stderr, "--floor and --light render with the nested tree alone: they cannot be combined with --compose, --shutter, --adaptive, --lens or --dispersion\n"); return 2; }
     if (!lights.empty() && !have_floor) { fprintf(stderr, "--light needs --floor: glass is not lit by lights\n"); return 2; }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
@@ -237,6 +247,10 @@ int main(int argc, char** argv)
     }
     if (have_floor && (rc = RefractionDemo::setFloorAndLights(floor_albedo, floor_specular, lights.data(), (int)lights.size())) != RR_OK) {
         fprintf(stderr, "setFloorAndLights failed (%d): %s\n", rc, RefractionDemo::lastError());
+        return 1;
+    }
+    if (have_soft && (rc = RefractionDemo::setLightSoftness(soft)) != RR_OK) {
+        fprintf(stderr, "setLightSoftness failed (%d): %s\n", rc, RefractionDemo::lastError());
         return 1;
     }
     auto t0 = std::chrono::steady_clock::now();
@@ -292,7 +306,7 @@ int main(int argc, char** argv)
     for (int k = 0; k < frames; ++k) {
         uint64_t n_ref = 0;
         const rr_lens lens = { lens_radius, lens_focus };
-        rc = n_keys ? RefractionDemo::drawFrameShutter(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : have_floor ? RefractionDemo::drawFrameSurfaces(spp) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
+        rc = lit ? RefractionDemo::drawFrameLit(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : n_keys ? RefractionDemo::drawFrameShutter(spp, have_lens ? &lens : nullptr, n_bands, abbe, n_keys, shutter_dt) : compose ? RefractionDemo::drawFrameComposed(spp, have_lens ? &lens : nullptr, n_bands, abbe) : have_floor ? RefractionDemo::drawFrameSurfaces(spp) : nested ? RefractionDemo::drawFrameNested(spp) : !materials.empty() ? RefractionDemo::drawFrameMaterials(spp) : base ? RefractionDemo::drawFrameAdaptive(base, spp, threshold, &n_ref) : n_bands ? RefractionDemo::drawFrameSpectral(spp, n_bands, abbe) : have_lens ? RefractionDemo::drawFrameLens(spp, lens_radius, lens_focus) : spp ? RefractionDemo::drawFrameSamples(spp) : RefractionDemo::drawFrame();
         refined += n_ref;
         if (rc != RR_OK) { fprintf(stderr, "drawFrame failed (%d): %s\n", rc, RefractionDemo::lastError()); return 1; }
         if (!out.empty()) {
@@ -307,7 +321,10 @@ int main(int argc, char** argv)
         }
     }
     double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (frames && n_keys)
+    if (frames && lit)
+        printf("%d lit frames of %dx%d at %d samples per pixel x %d keys x %d bands with %d materials under %d lights in %.3f s (%.1f fps incl. key captures and readback)\n",
+               frames, opt.width, opt.height, spp, n_keys ? n_keys : 1, n_bands ? n_bands : 1, (int)materials.size(), (int)lights.size(), s, frames / s);
+    else if (frames && n_keys)
         printf("%d shutter frames of %dx%d at %d samples per pixel x %d keys x %d bands with %d materials in %.3f s (%.1f fps incl. key captures and readback)\n", frames,
                opt.width, opt.height, spp, n_keys, n_bands ? n_bands : 1, (int)materials.size(), s, frames / s);
     else if (frames && compose)

@@ -183,6 +183,72 @@ def shutter_samples(positions, keys, bands=None, lens_offsets=None):
     return rec
 
 
+def light_pattern(n):
+    """-> float32 [n, 2]: the built-in light offsets of render_lit for n = 1..64 positions, each in [-1, 1], in units of a light's
+    edges.  Deterministic, a Hammersley set centred in its cells: point k is (2 * (k + 0.5) / n - 1, 2 * (phi2(k) + 0.5 / m) - 1) with
+    phi2 the base-2 radical inverse and m the smallest power of two >= n, computed in float64 and rounded once; n == 1 gives (0, 0)."""
+    n = int(n)
+    if not 1 <= n <= _capi.MAX_SAMPLES:
+        raise ValueError("light_pattern: need 1 <= n <= %d" % _capi.MAX_SAMPLES)
+    m = 1
+    while m < n:
+        m *= 2
+    k = np.arange(n)
+    phi = np.zeros(n, np.float64)
+    f, i = 0.5, k.copy()
+    while i.any():
+        phi += f * (i & 1)
+        i >>= 1
+        f *= 0.5
+    return np.stack([2.0 * (k + 0.5) / n - 1.0, 2.0 * (phi + 0.5 / m) - 1.0], axis=1).astype(np.float32)
+
+
+def light_shape(ex, ey):
+    """A LIGHT_SHAPE_DTYPE row (Renderer.set_light_shapes): the two edge vectors a light's position (or direction) moves along; a
+    sample with light offset (lu, lv) sees the light at v + lu * ex + lv * ey (moved_lights has the arithmetic)."""
+    r = np.zeros((), _capi.LIGHT_SHAPE_DTYPE)
+    r["ex"], r["ey"] = ex, ey
+    return r
+
+
+def moved_lights(lights, shapes, lu, lv):
+    """-> LIGHT_DTYPE [n]: the lights one sample of render_lit is lit by (rr_host_moved_lights): row i with
+    v = fmaf(lv, shapes[i].ey, fmaf(lu, shapes[i].ex, v)) per component in fp32, everything else copied.  shapes None: the rows
+    unchanged.  Otherwise one LIGHT_SHAPE_DTYPE row per light."""
+    t = np.ascontiguousarray(lights, LIGHT_DTYPE).reshape(-1)
+    out = np.zeros(len(t), LIGHT_DTYPE)
+    sp = None
+    if shapes is not None:
+        s = np.ascontiguousarray(shapes, _capi.LIGHT_SHAPE_DTYPE).reshape(-1)
+        if len(s) != len(t):
+            raise ValueError("moved_lights: need one shape per light")
+        sp = s.ctypes.data if len(s) else None
+    rc = _capi.lib().rr_host_moved_lights(t.ctypes.data if len(t) else None, sp, len(t), float(np.float32(lu)), float(np.float32(lv)),
+                                          out.ctypes.data if len(t) else None)
+    if rc:
+        raise RRError(rc, "rr_host_moved_lights")
+    return out
+
+
+def lit_samples(positions, keys, bands=None, lens_offsets=None, light_offsets=None):
+    """The crossed sample records of render_lit -> LIT_SAMPLE_DTYPE [A * K * B]: shutter_samples(positions, keys, bands, lens_offsets)
+    with a light offset per POSITION -- every sample of position a, whatever its key and band, has light_offsets[a].  light_offsets:
+    None for light_pattern(A), or an [A, 2] array in [-1, 1]."""
+    src = shutter_samples(positions, keys, bands, lens_offsets)
+    n_pos = int(positions) if isinstance(positions, (int, np.integer)) else len(positions)
+    if light_offsets is None:
+        lo = light_pattern(n_pos)
+    else:
+        lo = np.ascontiguousarray(light_offsets, np.float32)
+        if lo.shape != (n_pos, 2):
+            raise ValueError("lit_samples: light_offsets must be an [A, 2] array with one row per position")
+    rec = np.zeros(len(src), _capi.LIT_SAMPLE_DTYPE)
+    for f in ("offset", "lens_offset", "band", "key"):
+        rec[f] = src[f]
+    rec["light_offset"] = np.repeat(lo, len(src) // n_pos, axis=0)
+    return rec
+
+
 def make_instances(transforms=None, meshes=None, masks=None, flags=None, materials=None):
     """64-byte instance records (RefractionDemo.cpp:324-334 fills exactly one: identity, mask 1, flags 0).  materials: per instance
     the row of the material table (Renderer.set_materials) it is made of -- DXR's InstanceContributionToHitGroupIndex, the low 24
@@ -791,14 +857,15 @@ class Renderer:
     def set_surfaces(self, table):
         """The surface table (rr_set_surfaces): a SURFACE_DTYPE array or a list of glass() / opaque(...) rows.  Row r says what an
         instance of material row r is; rows at or beyond the table's length are glass, and None or an empty table makes every row
-        glass.  Copied; takes effect on the next shade_rays_surfaces / render_surfaces without a rebuild.  set_materials leaves it
-        alone, and only those two calls read it."""
+        glass.  Copied; takes effect on the next shade_rays_surfaces / render_surfaces / render_lit without a rebuild.  set_materials
+        leaves it alone, and only those three calls read it."""
         t = np.zeros(0, SURFACE_DTYPE) if table is None else np.ascontiguousarray(table, SURFACE_DTYPE).reshape(-1)
         self._ck(self._L.rr_set_surfaces(self._h, t.ctypes.data if len(t) else None, len(t)), "rr_set_surfaces")
 
     def set_lights(self, lights=None, ambient=None):
         """The lights of the opaque surfaces (rr_set_lights): a LIGHT_DTYPE array or a list of directional_light(...) /
-        point_light(...) rows, MAX_LIGHTS at most, and an RGB ambient term (None: 0).  Copied."""
+        point_light(...) rows, MAX_LIGHTS at most, and an RGB ambient term (None: 0).  Copied.  Clears the shape table of
+        set_light_shapes, whose rows belong with the lights they were set for."""
         t = np.zeros(0, LIGHT_DTYPE) if lights is None else np.ascontiguousarray(lights, LIGHT_DTYPE).reshape(-1)
         amb = None if ambient is None else np.ascontiguousarray(ambient, np.float32).reshape(3)
         self._ck(self._L.rr_set_lights(self._h, t.ctypes.data if len(t) else None, len(t), None if amb is None else amb.ctypes.data), "rr_set_lights")
@@ -989,6 +1056,70 @@ class Renderer:
             self._ck(self._L.rr_render_shutter_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter_device")
         else:
             self._ck(self._L.rr_render_shutter(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter")
+        return _result(outs)
+
+    def set_light_shapes(self, shapes=None):
+        """The shapes of the lights (rr_set_light_shapes): a LIGHT_SHAPE_DTYPE array or a list of light_shape(ex, ey) rows, one per
+        light in force, row i with light i; None or an empty table clears it.  Copied; takes effect on the next render_lit without a
+        rebuild.  set_lights clears it, and only render_lit reads it."""
+        t = np.zeros(0, _capi.LIGHT_SHAPE_DTYPE) if shapes is None else np.ascontiguousarray(shapes, _capi.LIGHT_SHAPE_DTYPE).reshape(-1)
+        self._ck(self._L.rr_set_light_shapes(self._h, t.ctypes.data if len(t) else None, len(t)), "rr_set_light_shapes")
+
+    def render_lit(self, width, height, camera, samples=4, keys=None, lens=None, lens_samples=None, bands=None, light_samples=None, paired=False,
+                   params=None, rgba8=False, ray_counts=False, device=False):
+        """Lit shutter frame (rr_render_lit): render_shutter over the ray tree of shade_rays_surfaces, with a point on every light per
+        sample -- the lit scene through the lens, with motion blur, dispersion and soft shadows.  Sample k is shaded as
+        shade_rays_surfaces shades lens_rays(...) (no lens: camera_rays) in the scene of key key_k under band band_k, the surface table
+        and ambient term in force and the lights moved_lights(lights, shapes, *light_offset_k); the pixel resolves as render_shutter's.
+        samples, keys, lens, lens_samples, bands and paired as render_shutter; a LIT_SAMPLE_DTYPE record array is passed straight
+        through (lit_samples makes one).  light_samples: None for light_pattern(A), one offset per position, or an [A, 2] array in
+        [-1, 1] (with paired=True a position is a sample).  A shaped light is a rectangle of point emitters: no cosine at the light and
+        no normalisation by its area.  The outputs and device=True as render_shutter; not a dispatch either."""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        if w < 0 or h < 0:
+            raise ValueError("render_lit: negative size")
+        if isinstance(samples, np.ndarray) and samples.dtype == _capi.LIT_SAMPLE_DTYPE:
+            if keys is not None or lens_samples is not None or bands is not None or light_samples is not None or paired:
+                raise ValueError("render_lit: a record array of samples carries its own keys, lens offsets, bands and light offsets")
+            rec = np.ascontiguousarray(samples).reshape(-1)
+        else:
+            if keys is None:
+                raise ValueError("render_lit: keys is required (an int K, or with paired=True one key per sample): there is no implicit key")
+            offp, n = _sample_offsets(samples, "render_lit: samples must be an int, an [S, 2] array or a LIT_SAMPLE_DTYPE array")
+            pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
+            if paired:
+                kidx = np.ascontiguousarray(keys, np.int64).reshape(-1)
+                bidx = np.zeros(len(pos), np.int64) if bands is None else np.ascontiguousarray(bands, np.int64).reshape(-1)
+                if isinstance(keys, (int, np.integer)) or len(kidx) != len(pos) or len(bidx) != len(pos) or (kidx < 0).any() or (bidx < 0).any():
+                    raise ValueError("render_lit: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample")
+                rec = np.zeros(len(pos), _capi.LIT_SAMPLE_DTYPE)
+                rec["offset"], rec["key"], rec["band"] = pos, kidx, bidx
+                if lens_samples is not None:
+                    loff = np.ascontiguousarray(lens_samples, np.float32)
+                    if loff.shape != (len(rec), 2) or len(rec) == 0:
+                        raise ValueError("render_lit: lens_samples must be an [S, 2] array with one row per sample")
+                    rec["lens_offset"] = loff
+                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
+                    rec["lens_offset"] = lens_pattern(len(rec))
+                if light_samples is not None:
+                    lo = np.ascontiguousarray(light_samples, np.float32)
+                    if lo.shape != (len(rec), 2) or len(rec) == 0:
+                        raise ValueError("render_lit: light_samples must be an [S, 2] array with one row per sample")
+                    rec["light_offset"] = lo
+                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
+                    rec["light_offset"] = light_pattern(len(rec))
+            else:
+                if not isinstance(keys, (int, np.integer)) or keys < 1 or not (bands is None or (isinstance(bands, (int, np.integer)) and bands >= 1)):
+                    raise ValueError("render_lit: keys must be an int >= 1 and bands None or an int >= 1, or both arrays with paired=True")
+                rec = lit_samples(pos, int(keys), bands, lens_samples, light_samples)
+        recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
+        lp = C.byref(lens) if lens is not None else None
+        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
+        if device:
+            self._ck(self._L.rr_render_lit_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_lit_device")
+        else:
+            self._ck(self._L.rr_render_lit(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_lit")
         return _result(outs)
 
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):

@@ -1,5 +1,13 @@
-// rr_capi_query.cpp -- rays of the caller's: rr_trace_rays, rr_query_rays*, rr_query_rays_multi*, rr_shade_rays*, rr_render_samples*, rr_render_adaptive*, rr_render_lens*, rr_render_spectral*, rr_set_materials, rr_shade_rays_materials*, rr_render_materials*, rr_shade_rays_nested*, rr_render_nested*, rr_set_surfaces, rr_set_lights, rr_shade_rays_surfaces*, rr_render_surfaces*, rr_set_material_bands, rr_render_composed*, rr_render_shutter*, rr_set_light_shapes, rr_host_moved_lights, rr_render_lit*, rr_env_lookup.
-// A host variant stages its arrays through the context's scratch around the launch its device variant makes.
+// rr_capi_query.cpp -- rays of the caller's: the hit queries (rr_trace_rays, rr_query_rays*), the table setters, rr_env_lookup, and
+// the ray-tree entry points, which come in host / _device pairs of two families, each behind one shell:
+//   rays_shell   rr_shade_rays, _materials, _nested, _surfaces: the caller's rays.  Refuses, in this order: no TLAS; what the
+//                family's table check refuses; (n == 0 returns); no colour output; the ray pointer (null; _device: or misaligned);
+//                _device: misaligned outputs; then, behind the staging of a host call, what check_shading_params refuses.
+//   frame_shell  rr_render_samples, _adaptive, _lens, _spectral, _materials, _nested, _surfaces, _composed, _shutter, _lit: a W x H
+//                frame.  Refuses: no TLAS where the pair asks that before its own check (the three table pairs); what the pair's
+//                check refuses (check_samples and its kin, which hold the no-colour-output refusal); _device: misaligned outputs.
+// A host variant stages its arrays through the context's scratch around the launch its device variant makes; a _device variant
+// returns from its shell before any of that, so it allocates, copies and waits for nothing.
 #include "rr_context.h"
 
 namespace {
@@ -64,27 +72,94 @@ int fetch(rr_context* ctx, size_t n, float* rgba32f, uint8_t* rgba8, uint32_t* n
     return RR_OK;
 }
 
+// The outputs as an entry point takes them: host arrays, or with `device` device pointers; any may be null (not wanted).  n_taken
+// is rr_render_adaptive's second count array, of which the shells look at the alignment alone.
+struct CallerOut { void* f32; void* rgba8; void* n_rays; bool device; void* n_taken = nullptr; };
+
+// a refusal in the entry point's name (the text is put together only here, where a call fails)
+int refuse(rr_context* ctx, int code, const char* who, const char* what) { return fail(ctx, code, (std::string(who) + what).c_str()); }
+
 // what the _device variants refuse of their output pointers (null passes: not wanted), with the entry point's own message
-int check_out_alignment(rr_context* ctx, const void* d_rgba32f, const void* d_rgba8, const void* d_n_rays, const void* d_n_taken, const char* what)
+int check_out_alignment(rr_context* ctx, const CallerOut& o, const char* who, const char* what)
 {
-    const bool ok = ((uintptr_t)d_rgba32f & 15u) == 0 && (((uintptr_t)d_rgba8 | (uintptr_t)d_n_rays | (uintptr_t)d_n_taken) & 3u) == 0;
-    return ok ? RR_OK : fail(ctx, RR_ERR_INVALID_ARGUMENT, what);
+    const bool ok = ((uintptr_t)o.f32 & 15u) == 0 && (((uintptr_t)o.rgba8 | (uintptr_t)o.n_rays | (uintptr_t)o.n_taken) & 3u) == 0;
+    return ok ? RR_OK : refuse(ctx, RR_ERR_INVALID_ARGUMENT, who, what);
 }
+
+// a _device variant's outputs as the launch takes them
+ShadeOut device_out(const CallerOut& o) { return { static_cast<float4*>(o.f32), static_cast<uint32_t*>(o.rgba8), static_cast<uint32_t*>(o.n_rays) }; }
+
+// The frame shell (the header comment has the order of its refusals).  who: the entry point's name; tlas_first: the pair refuses
+// a missing TLAS before its own check; check(have_colour) is that check, launch(out) the launch of the checked frame, whose
+// `out` holds device pointers.  A _device call returns from the first branch: nothing staged, copied or waited for.
+template <class Check, class Launch>
+int frame_shell(rr_context* ctx, const char* who, uint32_t width, uint32_t height, const CallerOut& o, bool tlas_first, Check check, Launch launch)
+{
+    if (int r = use_device(ctx)) return r;
+    if (tlas_first && !ctx->tlas_built) return refuse(ctx, RR_ERR_STATE, who, ": build the BLAS and TLAS first");
+    if (int r = check(o.f32 || o.rgba8)) return r;
+    if (o.device) {
+        if (int r = check_out_alignment(ctx, o, who, ": need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
+        return launch(device_out(o));
+    }
+    const size_t n = (size_t)width * height;
+    ShadeOut out;
+    if (int r = stage(ctx, n, o.f32, o.rgba8, o.n_rays, out)) return r;
+    if (int r = launch(out)) return r;
+    return fetch(ctx, n, static_cast<float*>(o.f32), static_cast<uint8_t*>(o.rgba8), static_cast<uint32_t*>(o.n_rays));
+}
+
+// One tree of the rays family: the name check_shading_params refuses under (null: the entry point's own), what the family asks
+// of the scene's tables (null: nothing; p is the caller's parameters, whose ior a table check replaces), and the launch.
+struct RayTree {
+    const char* params_name;
+    int (*check_tables)(rr_context* ctx, const char* who, rr_dispatch_params& p);
+    hipError_t (*launch)(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v);
+};
 
 // checks a radiance query's parameters and launches it: d_rays is a device pointer.  Touches nothing of
 // the context but its error text: no counters, no frame, no kernel choice.
-int shade_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+int shade_impl(rr_context* ctx, const char* who, const RayTree& tree, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
 {
-    if (int r = check_shading_params(ctx, "shade_rays", p)) return r;
+    if (int r = check_shading_params(ctx, tree.params_name ? tree.params_name : who, p)) return r;
     SceneDev sc;
     fill_scene(ctx, sc);
     const DispatchDev a = shading_args(p);
     // the kernel of a launch of many slices: a batch of rays is that, not a frame that ends on its longest wave
     const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
-    if (hipError_t e = launch_shade_rays(sc, a, d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, who, e);
+    if (hipError_t e = tree.launch(ctx, sc, a, d_rays, n, out, v)) return fail(ctx, RR_ERR_DEVICE, who, e);
     return RR_OK;
 }
+
+// The rays shell (the header comment has the order of its refusals): rays and o hold host arrays, or with o.device device pointers
+int rays_shell(rr_context* ctx, const char* who, const RayTree& tree, const void* rays, uint32_t n, const rr_dispatch_params* params, const CallerOut& o)
+{
+    if (int r = use_device(ctx)) return r;
+    if (!ctx->tlas_built) return refuse(ctx, RR_ERR_STATE, who, ": build the BLAS and TLAS first");
+    rr_dispatch_params p = params_or_default(params);
+    if (tree.check_tables) if (int r = tree.check_tables(ctx, who, p)) return r;
+    if (n == 0) return RR_OK;
+    if (!o.f32 && !o.rgba8) return refuse(ctx, RR_ERR_INVALID_ARGUMENT, who, o.device ? ": need d_rgba32f or d_rgba8" : ": need rgba32f or rgba8");
+    if (o.device) {
+        const char* const align = ": need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
+        if (!rays || ((uintptr_t)rays & 15u) != 0) return refuse(ctx, RR_ERR_INVALID_ARGUMENT, who, align);
+        if (int r = check_out_alignment(ctx, o, who, align)) return r;
+        return shade_impl(ctx, who, tree, static_cast<const rr_ray_dev*>(rays), n, p, device_out(o));
+    }
+    if (!rays) return refuse(ctx, RR_ERR_INVALID_ARGUMENT, who, ": null rays");
+    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
+    ShadeOut out;
+    if (int r = stage(ctx, n, o.f32, o.rgba8, o.n_rays, out)) return r;
+    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
+    if (int r = shade_impl(ctx, who, tree, ctx->d_rays.get(), n, p, out)) return r;
+    return fetch(ctx, n, static_cast<float*>(o.f32), static_cast<uint8_t*>(o.rgba8), static_cast<uint32_t*>(o.n_rays));
+}
+
+hipError_t shade_plain(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
+{
+    return launch_shade_rays(sc, a, d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream);
+}
+const RayTree kShadeRays = { "shade_rays", nullptr, shade_plain };
 
 // a supersampled frame as its two entry points take it (pointers of the caller's: host memory)
 struct SamplesReq {
@@ -148,15 +223,36 @@ FrameArgs frame_args(rr_context* ctx, const SamplesReq& q, const rr_lens* lens =
     return f;
 }
 
-// launches a checked supersampled frame: out holds device pointers.  Like shade_impl it touches nothing of the context but its
-// error text, and it allocates and copies nothing: constants and offsets travel as kernel arguments.
-int samples_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+// One tree of the supersampled frames that differ in nothing else (samples, materials, nested, surfaces): what the pair asks of
+// the scene's tables before check_samples (null: nothing, and no TLAS refusal of its own), and the launch.
+struct FrameTree {
+    int (*check_tables)(rr_context* ctx, const char* who, rr_dispatch_params& p);
+    hipError_t (*launch)(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out);
+};
+
+// Both variants of such a frame, through the frame shell.  The launch touches nothing of the context but its error text, and it
+// allocates and copies nothing: constants and offsets travel as kernel arguments.  With a table check q.params becomes its result.
+int samples_pair(rr_context* ctx, SamplesReq q, const FrameTree& tree, const CallerOut& o)
 {
-    const FrameArgs f = frame_args(ctx, q);
-    if (hipError_t e = launch_render_samples(f.sc, f.a, f.cam, off, q.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, q.who, e);
-    return RR_OK;
+    rr_dispatch_params p = params_or_default(q.params);
+    if (tree.check_tables) q.params = &p;
+    SampleOffsets off;
+    return frame_shell(ctx, q.who, q.width, q.height, o, tree.check_tables != nullptr,
+                       [&](bool have_colour) {
+                           if (tree.check_tables) if (int r = tree.check_tables(ctx, q.who, p)) return r;
+                           return check_samples(ctx, q, have_colour, off);
+                       },
+                       [&](const ShadeOut& out) {
+                           if (hipError_t e = tree.launch(ctx, frame_args(ctx, q), off, q.n_samples, out)) return fail(ctx, RR_ERR_DEVICE, q.who, e);
+                           return (int)RR_OK;
+                       });
 }
+
+hipError_t frame_plain(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
+{
+    return launch_render_samples(f.sc, f.a, f.cam, off, n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream);
+}
+const FrameTree kSamples = { nullptr, frame_plain };
 
 // an adaptive frame: a supersampled frame of n_samples = n_max samples, of which every pixel takes the first n_base
 struct AdaptiveReq { SamplesReq s; uint32_t n_base; float threshold; };
@@ -181,6 +277,38 @@ int adaptive_impl(rr_context* ctx, const AdaptiveReq& q, const SampleOffsets& of
                                               f.v.stack, f.v.pend, f.v.stack16, (uint32_t)ctx->dbg_refine_groups, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
+}
+
+// Both variants of rr_render_adaptive, through the frame shell: what the pair has beyond the three outputs sits in the launch
+// step, where it stood between the shell's steps before.  _device (o.n_taken, workspace: device pointers): the workspace refusal
+// behind the shell's alignment refusal, then the launch.  Host (o.n_taken, n_refined: the caller's): between the staging and the
+// fetch, the growth of the context's n_taken and workspace buffers, the launch and the copies the fetch then waits for.
+int adaptive_pair(rr_context* ctx, const AdaptiveReq& q, const CallerOut& o, void* d_workspace, uint64_t workspace_bytes, uint64_t* n_refined)
+{
+    const uint32_t width = q.s.width, height = q.s.height;
+    uint32_t* const n_taken = static_cast<uint32_t*>(o.n_taken);
+    SampleOffsets off;
+    uint32_t total = 0;
+    const int rc = frame_shell(ctx, q.s.who, width, height, o, false,
+        [&](bool have_colour) { return check_adaptive(ctx, q, have_colour, off); },
+        [&](const ShadeOut& out) {
+            if (o.device) {
+                if (!d_workspace || ((uintptr_t)d_workspace & 15u) != 0 || workspace_bytes < rr_host_adaptive_workspace_bytes(width, height))
+                    return refuse(ctx, RR_ERR_INVALID_ARGUMENT, q.s.who, ": need a 16-byte aligned workspace of at least rr_host_adaptive_workspace_bytes(width, height) bytes");
+                return adaptive_impl(ctx, q, off, out, n_taken, AdaptiveWorkspace(d_workspace, width, height));
+            }
+            const size_t n = (size_t)width * height;
+            const size_t ws_units = (size_t)(rr_host_adaptive_workspace_bytes(width, height) / 16u);
+            if (n_taken && n > ctx->d_adaptive_taken.size()) if (int r = ctx->d_adaptive_taken.grow(ctx, n)) return r;
+            if (ws_units > ctx->d_adaptive_ws.size()) if (int r = ctx->d_adaptive_ws.grow(ctx, ws_units)) return r;
+            const AdaptiveWorkspace ws(ctx->d_adaptive_ws.get(), width, height);
+            if (int r = adaptive_impl(ctx, q, off, out, n_taken ? ctx->d_adaptive_taken.get() : nullptr, ws)) return r;
+            if (n_taken) RR_HIP(hipMemcpyAsync(n_taken, ctx->d_adaptive_taken.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (n_refined) RR_HIP(hipMemcpyAsync(&total, ws.total, 4, hipMemcpyDeviceToHost, ctx->stream));
+            return (int)RR_OK;
+        });
+    if (rc == RR_OK && n_refined) *n_refined = total;
+    return rc;
 }
 
 // a thin-lens frame: a supersampled frame with a lens and one lens offset per sample
@@ -208,7 +336,7 @@ int check_lens(rr_context* ctx, const LensReq& q, bool have_colour, SampleOffset
     return RR_OK;
 }
 
-// launches a checked thin-lens frame: out holds device pointers.  As samples_impl: nothing of the context but its error text,
+// launches a checked thin-lens frame: out holds device pointers.  As samples_pair's launch: nothing of the context but its error text,
 // nothing allocated or copied.
 int lens_impl(rr_context* ctx, const LensReq& q, const SampleOffsets& off, const SampleOffsets& loff, const LensDev& lens, const ShadeOut& out)
 {
@@ -217,6 +345,16 @@ int lens_impl(rr_context* ctx, const LensReq& q, const SampleOffsets& off, const
                                           f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
+}
+
+// both variants of rr_render_lens, through the frame shell
+int lens_pair(rr_context* ctx, const LensReq& q, const CallerOut& o)
+{
+    SampleOffsets off, loff;
+    LensDev ld;
+    return frame_shell(ctx, q.s.who, q.s.width, q.s.height, o, false,
+                       [&](bool have_colour) { return check_lens(ctx, q, have_colour, off, loff, ld); },
+                       [&](const ShadeOut& out) { return lens_impl(ctx, q, off, loff, ld, out); });
 }
 
 // a spectral frame: a supersampled frame with one band (index of refraction, channel weights) per sample
@@ -243,7 +381,7 @@ int check_spectral(rr_context* ctx, const SpectralReq& q, bool have_colour, Samp
     return RR_OK;
 }
 
-// launches a checked spectral frame: out holds device pointers.  As samples_impl: nothing of the context but its error text,
+// launches a checked spectral frame: out holds device pointers.  As samples_pair's launch: nothing of the context but its error text,
 // nothing allocated or copied.
 int spectral_impl(rr_context* ctx, const SpectralReq& q, const SampleOffsets& off, const BandTable& bands, const ShadeOut& out)
 {
@@ -252,6 +390,16 @@ int spectral_impl(rr_context* ctx, const SpectralReq& q, const SampleOffsets& of
                                               f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
+}
+
+// both variants of rr_render_spectral, through the frame shell
+int spectral_pair(rr_context* ctx, const SpectralReq& q, const CallerOut& o)
+{
+    SampleOffsets off;
+    BandTable bt;
+    return frame_shell(ctx, q.s.who, q.s.width, q.s.height, o, false,
+                       [&](bool have_colour) { return check_spectral(ctx, q, have_colour, off, bt); },
+                       [&](const ShadeOut& out) { return spectral_impl(ctx, q, off, bt, out); });
 }
 
 // What both material calls need beside their scalar twins' checks: a table, and every instance of the scene inside it.  The index
@@ -269,29 +417,19 @@ int check_materials(rr_context* ctx, const char* who, rr_dispatch_params& p)
 // the hit-group index of instance 0, which the kernels take as an argument where the scene skips the top level
 uint32_t inst0_material(const rr_context* ctx) { return ctx->inst_host.empty() ? 0u : ctx->inst_host[0].hitgroup_flags & 0xffffffu; }
 
-// shade_impl with the material table (p: after check_materials)
-int shade_mat_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+// the ray tree with the material table (p: after check_materials), on caller rays and as a frame
+hipError_t shade_mat(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    if (int r = check_shading_params(ctx, "shade_rays_materials", p)) return r;
-    SceneDev sc;
-    fill_scene(ctx, sc);
-    const DispatchDev a = shading_args(p);
-    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
-    if (hipError_t e = launch_shade_rays_mat(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend,
-                                             v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, who, e);
-    return RR_OK;
+    return launch_shade_rays_mat(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16,
+                                 ctx->stream);
 }
-
-// samples_impl with the material table (q.params: after check_materials)
-int materials_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+hipError_t frame_mat(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    const FrameArgs f = frame_args(ctx, q);
-    if (hipError_t e = launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
-                                               f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, q.who, e);
-    return RR_OK;
+    return launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack,
+                                   f.v.pend, f.v.stack16, ctx->stream);
 }
+const RayTree kShadeMaterials = { "shade_rays_materials", check_materials, shade_mat };
+const FrameTree kMaterials = { check_materials, frame_mat };
 
 // What the nested calls need beside check_materials: a list entry is one byte holding row + 1, so no instance's row above 254
 int check_nested(rr_context* ctx, const char* who, rr_dispatch_params& p)
@@ -302,53 +440,34 @@ int check_nested(rr_context* ctx, const char* who, rr_dispatch_params& p)
     return RR_OK;
 }
 
-// shade_mat_impl with the nested tree (p: after check_nested)
-int shade_nested_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+// the material trees with the nested tree (p: after check_nested)
+hipError_t shade_nested(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    if (int r = check_shading_params(ctx, "shade_rays_nested", p)) return r;
-    SceneDev sc;
-    fill_scene(ctx, sc);
-    const DispatchDev a = shading_args(p);
-    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
-    if (hipError_t e = launch_shade_rays_nested(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend,
-                                                v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, who, e);
-    return RR_OK;
+    return launch_shade_rays_nested(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16,
+                                    ctx->stream);
 }
+hipError_t frame_nested(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
+{
+    return launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack,
+                                f.v.pend, f.v.stack16, ctx->stream);
+}
+const RayTree kShadeNested = { "shade_rays_nested", check_nested, shade_nested };
+const FrameTree kNested = { check_nested, frame_nested };
 
-// materials_impl with the nested tree (q.params: after check_nested)
-int nested_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
+// the nested trees with the surface table and the lights (p: after check_nested).  On caller rays check_shading_params refuses
+// under the entry point's own name, unlike its three siblings.
+hipError_t shade_surfaces(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    const FrameArgs f = frame_args(ctx, q);
-    if (hipError_t e = launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), q.n_samples, out.f32, out.rgba8, out.n_rays,
-                                            f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, q.who, e);
-    return RR_OK;
+    return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n, out.f32,
+                                      out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream);
 }
-
-// shade_nested_impl with the surface table and the lights (p: after check_nested)
-int shade_surfaces_impl(rr_context* ctx, const char* who, const rr_ray_dev* d_rays, uint32_t n, const rr_dispatch_params& p, const ShadeOut& out)
+hipError_t frame_surfaces(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    if (int r = check_shading_params(ctx, who, p)) return r;
-    SceneDev sc;
-    fill_scene(ctx, sc);
-    const DispatchDev a = shading_args(p);
-    const FusedVariant v = fused_variant(scene_facts(ctx), 64u, p.max_reflect, ctx->dbg);
-    if (hipError_t e = launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n,
-                                                  out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, who, e);
-    return RR_OK;
+    return launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), n_samples,
+                                  out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream);
 }
-
-// nested_impl with the surface table and the lights (q.params: after check_nested)
-int surfaces_impl(rr_context* ctx, const SamplesReq& q, const SampleOffsets& off, const ShadeOut& out)
-{
-    const FrameArgs f = frame_args(ctx, q);
-    if (hipError_t e = launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx),
-                                              q.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, q.who, e);
-    return RR_OK;
-}
+const RayTree kShadeSurfaces = { nullptr, check_nested, shade_surfaces };
+const FrameTree kSurfaces = { check_nested, frame_surfaces };
 
 // a composed frame: a nested frame whose samples each have a lens offset and a band of the context's band set; lens may be null
 // (a pinhole).  s.offsets is not the caller's: check_composed points it at the sub-pixel positions it takes from the samples
@@ -393,17 +512,34 @@ int check_composed(rr_context* ctx, ComposedReq& q, rr_dispatch_params& p, bool 
     return check_composed_args(ctx, q, have_colour, t, true);
 }
 
-// launches a checked composed frame: out holds device pointers.  As nested_impl: nothing of the context but its error text,
+// the band set in force on the device, or the material table and the weights 1 in its place
+struct BandSet { const MatDev* mats; const float* weights; };
+BandSet band_set(const rr_context* ctx)
+{
+    return ctx->n_bands ? BandSet{ ctx->d_band_mats.get(), ctx->d_band_w.get() } : BandSet{ ctx->d_mats.get(), ctx->d_band_one.get() };
+}
+
+// launches a checked composed frame: out holds device pointers.  As a nested frame: nothing of the context but its error text,
 // nothing allocated, copied or waited for -- the band set, or the table in force and the weights 1 in its place, is on the device
 int composed_impl(rr_context* ctx, const ComposedReq& q, const ComposedTables& t, const ShadeOut& out)
 {
     const FrameArgs f = frame_args(ctx, q.s, q.lens);
-    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
-    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
-    if (hipError_t e = launch_render_composed(f.sc, f.a, f.cam, t.off, t.loff, t.lens, t.band, mats, ctx->n_mats, weights, inst0_material(ctx),
+    const BandSet b = band_set(ctx);
+    if (hipError_t e = launch_render_composed(f.sc, f.a, f.cam, t.off, t.loff, t.lens, t.band, b.mats, ctx->n_mats, b.weights, inst0_material(ctx),
                                               q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
+}
+
+// both variants of rr_render_composed, through the frame shell (q.s.params: the caller's; the checks see their own copy)
+int composed_pair(rr_context* ctx, ComposedReq q, const CallerOut& o)
+{
+    rr_dispatch_params p = params_or_default(q.s.params);
+    q.s.params = &p;
+    ComposedTables t;
+    return frame_shell(ctx, q.s.who, q.s.width, q.s.height, o, false,
+                       [&](bool have_colour) { return check_composed(ctx, q, p, have_colour, t); },
+                       [&](const ShadeOut& out) { return composed_impl(ctx, q, t, out); });
 }
 
 // a shutter frame: a composed frame whose samples each name a captured scene key.  c: the samples as composed records (what
@@ -475,13 +611,23 @@ int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, c
 {
     const ShutterFrame m = shutter_frame(ctx, q, t);
     const FrameArgs& f = m.f;
-    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
-    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
-    if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), m.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, mats,
-                                             ctx->n_mats, weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out.f32, out.rgba8,
+    const BandSet b = band_set(ctx);
+    if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), m.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, b.mats,
+                                             ctx->n_mats, b.weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out.f32, out.rgba8,
                                              out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.c.s.who, e);
     return RR_OK;
+}
+
+// both variants of rr_render_shutter, through the frame shell (params as composed_pair)
+int shutter_pair(rr_context* ctx, ShutterReq q, const CallerOut& o)
+{
+    rr_dispatch_params p = params_or_default(q.c.s.params);
+    q.c.s.params = &p;
+    ShutterTables t;
+    return frame_shell(ctx, q.c.s.who, q.c.s.width, q.c.s.height, o, false,
+                       [&](bool have_colour) { return check_shutter(ctx, q, p, have_colour, t); },
+                       [&](const ShadeOut& out) { return shutter_impl(ctx, q, t, out); });
 }
 
 // a light's v, one component, moved by a sample's light offset (lu, lv) over its shape: the arithmetic rr_host_moved_lights states
@@ -534,14 +680,25 @@ int check_lit(rr_context* ctx, LitReq& q, rr_dispatch_params& p, bool have_colou
 int lit_impl(rr_context* ctx, const LitReq& q, const LitTables& t, const ShadeOut& out)
 {
     const ShutterFrame m = shutter_frame(ctx, q.s, t.s);
-    const MatDev* const mats = ctx->n_bands ? ctx->d_band_mats.get() : ctx->d_mats.get();
-    const float* const weights = ctx->n_bands ? ctx->d_band_w.get() : ctx->d_band_one.get();
+    const BandSet b = band_set(ctx);
     if (hipError_t e = launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
-                                         t.s.key, mats, ctx->n_mats, weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
+                                         t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
                                          ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out.f32, out.rgba8, out.n_rays, m.f.v.stack,
                                          m.f.v.pend, m.f.v.stack16, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
     return RR_OK;
+}
+
+// both variants of rr_render_lit, through the frame shell (params as composed_pair)
+int lit_pair(rr_context* ctx, LitReq q, const CallerOut& o)
+{
+    SamplesReq& s = q.s.c.s;
+    rr_dispatch_params p = params_or_default(s.params);
+    s.params = &p;
+    LitTables t;
+    return frame_shell(ctx, s.who, s.width, s.height, o, false,
+                       [&](bool have_colour) { return check_lit(ctx, q, p, have_colour, t); },
+                       [&](const ShadeOut& out) { return lit_impl(ctx, q, t, out); });
 }
 } // namespace
 
@@ -626,57 +783,26 @@ int rr_query_rays_multi_device(rr_context* ctx, const void* d_rays, uint32_t n, 
 int rr_shade_rays(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
                   uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays: build the BLAS and TLAS first");
-    if (n == 0) return RR_OK;
-    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: need rgba32f or rgba8");
-    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays: null rays");
-    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    if (int r = shade_impl(ctx, "rr_shade_rays", ctx->d_rays.get(), n, params_or_default(params), out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return rays_shell(ctx, "rr_shade_rays", kShadeRays, rays, n, params, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_shade_rays_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
                          void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_device: build the BLAS and TLAS first");
-    if (n == 0) return RR_OK;
-    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: need d_rgba32f or d_rgba8");
-    const char* const align = "rr_shade_rays_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
-    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
-    return shade_impl(ctx, "rr_shade_rays_device", static_cast<const rr_ray_dev*>(d_rays), n, params_or_default(params),
-                      { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return rays_shell(ctx, "rr_shade_rays_device", kShadeRays, d_rays, n, params, { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_samples(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                       const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const SamplesReq q = { "rr_render_samples", width, height, constants, params, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = samples_impl(ctx, q, off, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return samples_pair(ctx, { "rr_render_samples", width, height, constants, params, offsets, n_samples }, kSamples, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_samples_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                              const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const SamplesReq q = { "rr_render_samples_device", width, height, constants, params, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_samples_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return samples_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return samples_pair(ctx, { "rr_render_samples_device", width, height, constants, params, offsets, n_samples }, kSamples,
+                        { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 uint64_t rr_host_adaptive_workspace_bytes(uint32_t width, uint32_t height)
@@ -689,99 +815,45 @@ int rr_render_adaptive(rr_context* ctx, uint32_t width, uint32_t height, const r
                        const float* offsets, uint32_t n_base, uint32_t n_max, float threshold, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays,
                        uint32_t* n_taken, uint64_t* n_refined)
 {
-    if (int r = use_device(ctx)) return r;
-    const AdaptiveReq q = { { "rr_render_adaptive", width, height, constants, params, offsets, n_max }, n_base, threshold };
-    SampleOffsets off;
-    if (int r = check_adaptive(ctx, q, rgba32f || rgba8, off)) return r;
-    const size_t n = (size_t)width * height;
-    const size_t ws_units = (size_t)(rr_host_adaptive_workspace_bytes(width, height) / 16u);
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (n_taken && n > ctx->d_adaptive_taken.size()) if (int r = ctx->d_adaptive_taken.grow(ctx, n)) return r;
-    if (ws_units > ctx->d_adaptive_ws.size()) if (int r = ctx->d_adaptive_ws.grow(ctx, ws_units)) return r;
-    const AdaptiveWorkspace ws(ctx->d_adaptive_ws.get(), width, height);
-    if (int r = adaptive_impl(ctx, q, off, out, n_taken ? ctx->d_adaptive_taken.get() : nullptr, ws)) return r;
-    if (n_taken) RR_HIP(hipMemcpyAsync(n_taken, ctx->d_adaptive_taken.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    uint32_t total = 0;
-    if (n_refined) RR_HIP(hipMemcpyAsync(&total, ws.total, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int r = fetch(ctx, n, rgba32f, rgba8, n_rays)) return r;
-    if (n_refined) *n_refined = total;
-    return RR_OK;
+    return adaptive_pair(ctx, { { "rr_render_adaptive", width, height, constants, params, offsets, n_max }, n_base, threshold },
+                         { rgba32f, rgba8, n_rays, false, n_taken }, nullptr, 0, n_refined);
 }
 
 int rr_render_adaptive_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                               const float* offsets, uint32_t n_base, uint32_t n_max, float threshold, void* d_rgba32f, void* d_rgba8, void* d_n_rays,
                               void* d_n_taken, void* d_workspace, uint64_t workspace_bytes)
 {
-    if (int r = use_device(ctx)) return r;
-    const AdaptiveReq q = { { "rr_render_adaptive_device", width, height, constants, params, offsets, n_max }, n_base, threshold };
-    SampleOffsets off;
-    if (int r = check_adaptive(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, d_n_taken,
-                                    "rr_render_adaptive_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    if (!d_workspace || ((uintptr_t)d_workspace & 15u) != 0 || workspace_bytes < rr_host_adaptive_workspace_bytes(width, height))
-        return fail(ctx, RR_ERR_INVALID_ARGUMENT,
-                    "rr_render_adaptive_device: need a 16-byte aligned workspace of at least rr_host_adaptive_workspace_bytes(width, height) bytes");
-    return adaptive_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) },
-                         static_cast<uint32_t*>(d_n_taken), AdaptiveWorkspace(d_workspace, width, height));
+    return adaptive_pair(ctx, { { "rr_render_adaptive_device", width, height, constants, params, offsets, n_max }, n_base, threshold },
+                         { d_rgba32f, d_rgba8, d_n_rays, true, d_n_taken }, d_workspace, workspace_bytes, nullptr);
 }
 
 int rr_render_lens(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                    const float* offsets, const float* lens_offsets, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8,
                    uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const LensReq q = { { "rr_render_lens", width, height, constants, params, offsets, n_samples }, lens_offsets, lens };
-    SampleOffsets off, loff;
-    LensDev ld;
-    if (int r = check_lens(ctx, q, rgba32f || rgba8, off, loff, ld)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = lens_impl(ctx, q, off, loff, ld, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return lens_pair(ctx, { { "rr_render_lens", width, height, constants, params, offsets, n_samples }, lens_offsets, lens },
+                     { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_lens_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                           const float* offsets, const float* lens_offsets, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
                           void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const LensReq q = { { "rr_render_lens_device", width, height, constants, params, offsets, n_samples }, lens_offsets, lens };
-    SampleOffsets off, loff;
-    LensDev ld;
-    if (int r = check_lens(ctx, q, d_rgba32f || d_rgba8, off, loff, ld)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_lens_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return lens_impl(ctx, q, off, loff, ld, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return lens_pair(ctx, { { "rr_render_lens_device", width, height, constants, params, offsets, n_samples }, lens_offsets, lens },
+                     { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_spectral(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                        const float* offsets, const rr_band* bands, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const SpectralReq q = { { "rr_render_spectral", width, height, constants, params, offsets, n_samples }, bands };
-    SampleOffsets off;
-    BandTable bt;
-    if (int r = check_spectral(ctx, q, rgba32f || rgba8, off, bt)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = spectral_impl(ctx, q, off, bt, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return spectral_pair(ctx, { { "rr_render_spectral", width, height, constants, params, offsets, n_samples }, bands }, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_spectral_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                               const float* offsets, const rr_band* bands, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    const SpectralReq q = { { "rr_render_spectral_device", width, height, constants, params, offsets, n_samples }, bands };
-    SampleOffsets off;
-    BandTable bt;
-    if (int r = check_spectral(ctx, q, d_rgba32f || d_rgba8, off, bt)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_spectral_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return spectral_impl(ctx, q, off, bt, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return spectral_pair(ctx, { { "rr_render_spectral_device", width, height, constants, params, offsets, n_samples }, bands },
+                         { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 float rr_host_expf_neg(float x) { return rr_expf_neg(x); }
@@ -866,133 +938,51 @@ int rr_set_material_bands(rr_context* ctx, const float* iors, const float* weigh
 int rr_shade_rays_materials(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
                             uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_materials: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_materials(ctx, "rr_shade_rays_materials", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials: need rgba32f or rgba8");
-    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials: null rays");
-    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    if (int r = shade_mat_impl(ctx, "rr_shade_rays_materials", ctx->d_rays.get(), n, p, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return rays_shell(ctx, "rr_shade_rays_materials", kShadeMaterials, rays, n, params, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_shade_rays_materials_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
                                    void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_materials_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_materials(ctx, "rr_shade_rays_materials_device", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_materials_device: need d_rgba32f or d_rgba8");
-    const char* const align = "rr_shade_rays_materials_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
-    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
-    return shade_mat_impl(ctx, "rr_shade_rays_materials_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
-                          { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return rays_shell(ctx, "rr_shade_rays_materials_device", kShadeMaterials, d_rays, n, params, { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_materials(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                         const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_materials: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_materials(ctx, "rr_render_materials", p)) return r;
-    const SamplesReq q = { "rr_render_materials", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = materials_impl(ctx, q, off, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return samples_pair(ctx, { "rr_render_materials", width, height, constants, params, offsets, n_samples }, kMaterials, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_materials_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                                const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_materials_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_materials(ctx, "rr_render_materials_device", p)) return r;
-    const SamplesReq q = { "rr_render_materials_device", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_materials_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return materials_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return samples_pair(ctx, { "rr_render_materials_device", width, height, constants, params, offsets, n_samples }, kMaterials,
+                        { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_shade_rays_nested(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
                          uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_nested: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_shade_rays_nested", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested: need rgba32f or rgba8");
-    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested: null rays");
-    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    if (int r = shade_nested_impl(ctx, "rr_shade_rays_nested", ctx->d_rays.get(), n, p, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return rays_shell(ctx, "rr_shade_rays_nested", kShadeNested, rays, n, params, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_shade_rays_nested_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
                                 void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_nested_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_shade_rays_nested_device", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_nested_device: need d_rgba32f or d_rgba8");
-    const char* const align = "rr_shade_rays_nested_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
-    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
-    return shade_nested_impl(ctx, "rr_shade_rays_nested_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
-                             { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return rays_shell(ctx, "rr_shade_rays_nested_device", kShadeNested, d_rays, n, params, { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_nested(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                      const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_nested: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_render_nested", p)) return r;
-    const SamplesReq q = { "rr_render_nested", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = nested_impl(ctx, q, off, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return samples_pair(ctx, { "rr_render_nested", width, height, constants, params, offsets, n_samples }, kNested, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                             const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_nested_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_render_nested_device", p)) return r;
-    const SamplesReq q = { "rr_render_nested_device", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_nested_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return nested_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return samples_pair(ctx, { "rr_render_nested_device", width, height, constants, params, offsets, n_samples }, kNested,
+                        { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_set_surfaces(rr_context* ctx, const rr_surface* rows, uint32_t n)
@@ -1061,125 +1051,56 @@ int rr_set_lights(rr_context* ctx, const rr_light* lights, uint32_t n, const flo
 int rr_shade_rays_surfaces(rr_context* ctx, const rr_ray* rays, uint32_t n, const rr_dispatch_params* params, float* rgba32f, uint8_t* rgba8,
                            uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_surfaces: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_shade_rays_surfaces", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!rgba32f && !rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces: need rgba32f or rgba8");
-    if (!rays) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces: null rays");
-    if (n > ctx->d_rays.size()) if (int r = ctx->d_rays.grow(ctx, n)) return r;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    RR_HIP(hipMemcpyAsync(ctx->d_rays.get(), rays, (size_t)n * sizeof(rr_ray_dev), hipMemcpyHostToDevice, ctx->stream));
-    if (int r = shade_surfaces_impl(ctx, "rr_shade_rays_surfaces", ctx->d_rays.get(), n, p, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return rays_shell(ctx, "rr_shade_rays_surfaces", kShadeSurfaces, rays, n, params, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_shade_rays_surfaces_device(rr_context* ctx, const void* d_rays, uint32_t n, const rr_dispatch_params* params, void* d_rgba32f, void* d_rgba8,
                                   void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_shade_rays_surfaces_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_shade_rays_surfaces_device", p)) return r;
-    if (n == 0) return RR_OK;
-    if (!d_rgba32f && !d_rgba8) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_surfaces_device: need d_rgba32f or d_rgba8");
-    const char* const align = "rr_shade_rays_surfaces_device: need 16-byte aligned ray and float pointers and 4-byte aligned rgba8 and count pointers";
-    if (!d_rays || ((uintptr_t)d_rays & 15u) != 0) return fail(ctx, RR_ERR_INVALID_ARGUMENT, align);
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr, align)) return r;
-    return shade_surfaces_impl(ctx, "rr_shade_rays_surfaces_device", static_cast<const rr_ray_dev*>(d_rays), n, p,
-                               { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return rays_shell(ctx, "rr_shade_rays_surfaces_device", kShadeSurfaces, d_rays, n, params, { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_surfaces(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                        const float* offsets, uint32_t n_samples, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_surfaces: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_render_surfaces", p)) return r;
-    const SamplesReq q = { "rr_render_surfaces", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, rgba32f || rgba8, off)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = surfaces_impl(ctx, q, off, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return samples_pair(ctx, { "rr_render_surfaces", width, height, constants, params, offsets, n_samples }, kSurfaces, { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_surfaces_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                               const float* offsets, uint32_t n_samples, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    if (!ctx->tlas_built) return fail(ctx, RR_ERR_STATE, "rr_render_surfaces_device: build the BLAS and TLAS first");
-    rr_dispatch_params p = params_or_default(params);
-    if (int r = check_nested(ctx, "rr_render_surfaces_device", p)) return r;
-    const SamplesReq q = { "rr_render_surfaces_device", width, height, constants, &p, offsets, n_samples };
-    SampleOffsets off;
-    if (int r = check_samples(ctx, q, d_rgba32f || d_rgba8, off)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_surfaces_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return surfaces_impl(ctx, q, off, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return samples_pair(ctx, { "rr_render_surfaces_device", width, height, constants, params, offsets, n_samples }, kSurfaces,
+                        { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_composed(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                        const rr_composed_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    ComposedReq q = { { "rr_render_composed", width, height, constants, &p, nullptr, n_samples }, samples, lens };
-    ComposedTables t;
-    if (int r = check_composed(ctx, q, p, rgba32f || rgba8, t)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = composed_impl(ctx, q, t, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return composed_pair(ctx, { { "rr_render_composed", width, height, constants, params, nullptr, n_samples }, samples, lens },
+                         { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_composed_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                               const rr_composed_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
                               void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    ComposedReq q = { { "rr_render_composed_device", width, height, constants, &p, nullptr, n_samples }, samples, lens };
-    ComposedTables t;
-    if (int r = check_composed(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_composed_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return composed_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return composed_pair(ctx, { { "rr_render_composed_device", width, height, constants, params, nullptr, n_samples }, samples, lens },
+                         { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_render_shutter(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                       const rr_shutter_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    ShutterReq q = { { { "rr_render_shutter", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, samples };
-    ShutterTables t;
-    if (int r = check_shutter(ctx, q, p, rgba32f || rgba8, t)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = shutter_impl(ctx, q, t, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return shutter_pair(ctx, { { { "rr_render_shutter", width, height, constants, params, nullptr, n_samples }, nullptr, lens }, samples },
+                        { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                              const rr_shutter_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8,
                              void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    ShutterReq q = { { { "rr_render_shutter_device", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, samples };
-    ShutterTables t;
-    if (int r = check_shutter(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_shutter_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return shutter_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return shutter_pair(ctx, { { { "rr_render_shutter_device", width, height, constants, params, nullptr, n_samples }, nullptr, lens }, samples },
+                        { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_set_light_shapes(rr_context* ctx, const rr_light_shape* shapes, uint32_t n)
@@ -1220,29 +1141,15 @@ int rr_host_moved_lights(const rr_light* lights, const rr_light_shape* shapes, u
 int rr_render_lit(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                   const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens, float* rgba32f, uint8_t* rgba8, uint32_t* n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    LitReq q = { { { { "rr_render_lit", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, nullptr }, samples };
-    LitTables t;
-    if (int r = check_lit(ctx, q, p, rgba32f || rgba8, t)) return r;
-    const size_t n = (size_t)width * height;
-    ShadeOut out;
-    if (int r = stage(ctx, n, rgba32f, rgba8, n_rays, out)) return r;
-    if (int r = lit_impl(ctx, q, t, out)) return r;
-    return fetch(ctx, n, rgba32f, rgba8, n_rays);
+    return lit_pair(ctx, { { { { "rr_render_lit", width, height, constants, params, nullptr, n_samples }, nullptr, lens }, nullptr }, samples },
+                    { rgba32f, rgba8, n_rays, false });
 }
 
 int rr_render_lit_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants, const rr_dispatch_params* params,
                          const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens, void* d_rgba32f, void* d_rgba8, void* d_n_rays)
 {
-    if (int r = use_device(ctx)) return r;
-    rr_dispatch_params p = params_or_default(params);
-    LitReq q = { { { { "rr_render_lit_device", width, height, constants, &p, nullptr, n_samples }, nullptr, lens }, nullptr }, samples };
-    LitTables t;
-    if (int r = check_lit(ctx, q, p, d_rgba32f || d_rgba8, t)) return r;
-    if (int r = check_out_alignment(ctx, d_rgba32f, d_rgba8, d_n_rays, nullptr,
-                                    "rr_render_lit_device: need a 16-byte aligned float pointer and 4-byte aligned rgba8 and count pointers")) return r;
-    return lit_impl(ctx, q, t, { static_cast<float4*>(d_rgba32f), static_cast<uint32_t*>(d_rgba8), static_cast<uint32_t*>(d_n_rays) });
+    return lit_pair(ctx, { { { { "rr_render_lit_device", width, height, constants, params, nullptr, n_samples }, nullptr, lens }, nullptr }, samples },
+                    { d_rgba32f, d_rgba8, d_n_rays, true });
 }
 
 int rr_env_lookup(rr_context* ctx, const float* dirs, uint32_t n, float* rgb)

@@ -361,6 +361,27 @@ def _sample_offsets(samples, complaint):
     return (off.ctypes.data_as(C.c_void_p) if off.shape[0] else None), off.shape[0]
 
 
+def _per_sample(rec, field, given, pattern, what):
+    """rec[field] of S sample records: the rows of `given`, an [S, 2] array, or with None pattern(S) where 1 <= S <= MAX_SAMPLES
+    (any other S the library refuses, so the field stays zero)"""
+    if given is not None:
+        rows = np.ascontiguousarray(given, np.float32)
+        if rows.shape != (len(rec), 2) or len(rec) == 0:
+            raise ValueError("%s must be an [S, 2] array with one row per sample" % what)
+        rec[field] = rows
+    elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
+        rec[field] = pattern(len(rec))
+
+
+def _paired_indices(n, complaint, *columns, refuse=False):
+    """paired=True: every column (indices, or None for zeros) -> int64 [n]; complains of a column of another length or with a negative
+    entry, and where the caller has seen a reason of its own (refuse)"""
+    idx = [np.zeros(n, np.int64) if c is None else np.ascontiguousarray(c, np.int64).reshape(-1) for c in columns]
+    if refuse or any(len(i) != n or (i < 0).any() for i in idx):
+        raise ValueError(complaint)
+    return idx
+
+
 class Mesh:
     """Mesh.hpp:14-25.  verts: structured array of 32-byte Vertex; indices: uint32."""
 
@@ -725,22 +746,44 @@ class Renderer:
         waiting for it (stream order as query_rays).  rgba8=True adds the R8G8B8A8_UNORM store (uint8 [n, 4]), ray_counts=True the
         TraceRay calls of each ray's tree, the primary included (uint32 [n]; torch: int32 [n]); the result is then a tuple in
         that order."""
+        return self._shade("shade_rays", rays, params, rgba8, ray_counts)
+
+    def _shade(self, name, rays, params, rgba8, ray_counts):
+        """the four shade_rays* methods: rr_<name>_device on a tensor of rays, rr_<name> on an array"""
         p = params if params is not None else default_params()
         if type(rays).__module__.startswith("torch"):
             import torch
             t = rays
             if not t.is_cuda or t.device.index != self.device:
-                raise ValueError("shade_rays: the tensor must live on GPU %d" % self.device)
+                raise ValueError("%s: the tensor must live on GPU %d" % (name, self.device))
             if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
-                raise ValueError("shade_rays: need a contiguous [n, 12] int32 or float32 tensor")
-            n = t.shape[0]
+                raise ValueError("%s: need a contiguous [n, 12] int32 or float32 tensor" % name)
+            n, fn = t.shape[0], "rr_%s_device" % name
+            rayp = C.c_void_p(t.data_ptr() if n else None)
             outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
-            self._ck(self._L.rr_shade_rays_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs), "rr_shade_rays_device")
         else:
             rays = np.ascontiguousarray(rays, RAY_DTYPE)
-            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
-            self._ck(self._L.rr_shade_rays(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays")
+            n, fn, rayp = len(rays), "rr_%s" % name, rays.ctypes.data
+            outs, ptrs = _outputs((n,), rgba8, (ray_counts,))
+        self._ck(getattr(self._L, fn)(self._h, rayp, n, C.byref(p), *ptrs), fn)
         return _result(outs)
+
+    def _frame(self, name, w, h, rgba8, counts, device, *args, tail=()):
+        """what every frame method ends in: the outputs of an h x w frame, rr_<name>_device or rr_<name> with args before their
+        pointers and tail behind them, the result"""
+        outs, ptrs = _outputs((h, w), rgba8, counts, "cuda:%d" % self.device if device else None)
+        fn = "rr_%s_device" % name if device else "rr_%s" % name
+        self._ck(getattr(self._L, fn)(self._h, w, h, *args, *ptrs, *tail), fn)
+        return _result(outs)
+
+    def _supersampled(self, name, width, height, camera, samples, params, rgba8, ray_counts, device):
+        """render_samples and the three methods that differ from it in the ray tree alone"""
+        p = params if params is not None else default_params()
+        w, h = int(width), int(height)
+        offp, n = _sample_offsets(samples, "%s: samples must be an int or an [S, 2] array" % name)
+        if n < 0 or w < 0 or h < 0:
+            raise ValueError("%s: negative size" % name)
+        return self._frame(name, w, h, rgba8, (ray_counts,), device, C.byref(camera), C.byref(p), offp, n)
 
     def render_samples(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
         """Supersampled frame (rr_render_samples): every pixel of a width x height frame takes S primary rays through S sub-pixel
@@ -755,17 +798,7 @@ class Renderer:
         ray_counts=True the TraceRay calls of the pixel's S trees (uint32 [height, width]); the result is then a tuple in that
         order.  device=False: numpy arrays, blocking.  device=True: new torch tensors on this renderer's GPU (the counts as
         int32), computed on the renderer's stream without waiting for it (stream order as query_rays)."""
-        p = params if params is not None else default_params()
-        w, h = int(width), int(height)
-        offp, n = _sample_offsets(samples, "render_samples: samples must be an int or an [S, 2] array")
-        if n < 0 or w < 0 or h < 0:
-            raise ValueError("render_samples: negative size")
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_samples_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples_device")
-        else:
-            self._ck(self._L.rr_render_samples(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_samples")
-        return _result(outs)
+        return self._supersampled("render_samples", width, height, camera, samples, params, rgba8, ray_counts, device)
 
     def set_materials(self, table):
         """The material table (rr_set_materials): a MATERIAL_DTYPE array, or rows of (ior, (sigma_r, sigma_g, sigma_b)) -- index of
@@ -781,38 +814,12 @@ class Renderer:
         tree with an RGB path weight -- ClosestHit refracts with the index of refraction of the hit instance's material, and a ray
         that crossed the glass of an instance is absorbed per channel by exp(-sigma_a * distance) before it is shaded.  params.ior is
         ignored.  A table whose rows are all (ior, (0, 0, 0)) gives shade_rays under default_params(ior=ior) byte for byte."""
-        p = params if params is not None else default_params()
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            t = rays
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError("shade_rays_materials: the tensor must live on GPU %d" % self.device)
-            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
-                raise ValueError("shade_rays_materials: need a contiguous [n, 12] int32 or float32 tensor")
-            n = t.shape[0]
-            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
-            self._ck(self._L.rr_shade_rays_materials_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
-                     "rr_shade_rays_materials_device")
-        else:
-            rays = np.ascontiguousarray(rays, RAY_DTYPE)
-            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
-            self._ck(self._L.rr_shade_rays_materials(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_materials")
-        return _result(outs)
+        return self._shade("shade_rays_materials", rays, params, rgba8, ray_counts)
 
     def render_materials(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
         """render_samples with the material table (rr_render_materials): the same arguments, samples, resolve and outputs, every
         sample shaded as shade_rays_materials shades camera_rays(camera, width, height, *offset_s).  params.ior is ignored."""
-        p = params if params is not None else default_params()
-        w, h = int(width), int(height)
-        offp, n = _sample_offsets(samples, "render_materials: samples must be an int or an [S, 2] array")
-        if n < 0 or w < 0 or h < 0:
-            raise ValueError("render_materials: negative size")
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_materials_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_materials_device")
-        else:
-            self._ck(self._L.rr_render_materials(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_materials")
-        return _result(outs)
+        return self._supersampled("render_materials", width, height, camera, samples, params, rgba8, ray_counts, device)
 
     def shade_rays_nested(self, rays, params=None, rgba8=False, ray_counts=False):
         """shade_rays_materials for instances inside, or overlapping, other instances (rr_shade_rays_nested): the same rays, table,
@@ -821,38 +828,12 @@ class Renderer:
         two different media refracts with ior_from / ior_to, a surface inside one medium is passed straight on; absorption is that of
         the medium crossed.  On closed, consistently wound, pairwise disjoint instances this is shade_rays_materials byte for byte.
         Every instance's row must be <= NESTED_MAX_MATERIAL.  params.ior is ignored."""
-        p = params if params is not None else default_params()
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            t = rays
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError("shade_rays_nested: the tensor must live on GPU %d" % self.device)
-            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
-                raise ValueError("shade_rays_nested: need a contiguous [n, 12] int32 or float32 tensor")
-            n = t.shape[0]
-            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
-            self._ck(self._L.rr_shade_rays_nested_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
-                     "rr_shade_rays_nested_device")
-        else:
-            rays = np.ascontiguousarray(rays, RAY_DTYPE)
-            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
-            self._ck(self._L.rr_shade_rays_nested(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_nested")
-        return _result(outs)
+        return self._shade("shade_rays_nested", rays, params, rgba8, ray_counts)
 
     def render_nested(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
         """render_materials with the ray tree of shade_rays_nested (rr_render_nested): the same arguments, samples, resolve and
         outputs, every sample shaded as shade_rays_nested shades camera_rays(camera, width, height, *offset_s)."""
-        p = params if params is not None else default_params()
-        w, h = int(width), int(height)
-        offp, n = _sample_offsets(samples, "render_nested: samples must be an int or an [S, 2] array")
-        if n < 0 or w < 0 or h < 0:
-            raise ValueError("render_nested: negative size")
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_nested_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested_device")
-        else:
-            self._ck(self._L.rr_render_nested(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_nested")
-        return _result(outs)
+        return self._supersampled("render_nested", width, height, camera, samples, params, rgba8, ray_counts, device)
 
     def set_surfaces(self, table):
         """The surface table (rr_set_surfaces): a SURFACE_DTYPE array or a list of glass() / opaque(...) rows.  Row r says what an
@@ -876,38 +857,12 @@ class Renderer:
         every light it faces and whose shadow ray -- first hit, instances selected by the light's shadow_mask, counted in the ray
         counts -- finds nothing, adds albedo * (ambient + sum) + emission, and continues as a mirror where specular is not zero.
         Without a surface table, or with every row glass, this is shade_rays_nested byte for byte."""
-        p = params if params is not None else default_params()
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            t = rays
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError("shade_rays_surfaces: the tensor must live on GPU %d" % self.device)
-            if t.dtype not in (torch.int32, torch.float32) or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
-                raise ValueError("shade_rays_surfaces: need a contiguous [n, 12] int32 or float32 tensor")
-            n = t.shape[0]
-            outs, ptrs = _outputs((n,), rgba8, (ray_counts,), t.device)
-            self._ck(self._L.rr_shade_rays_surfaces_device(self._h, C.c_void_p(t.data_ptr() if n else None), n, C.byref(p), *ptrs),
-                     "rr_shade_rays_surfaces_device")
-        else:
-            rays = np.ascontiguousarray(rays, RAY_DTYPE)
-            outs, ptrs = _outputs((len(rays),), rgba8, (ray_counts,))
-            self._ck(self._L.rr_shade_rays_surfaces(self._h, rays.ctypes.data, len(rays), C.byref(p), *ptrs), "rr_shade_rays_surfaces")
-        return _result(outs)
+        return self._shade("shade_rays_surfaces", rays, params, rgba8, ray_counts)
 
     def render_surfaces(self, width, height, camera, samples=4, params=None, rgba8=False, ray_counts=False, device=False):
         """render_nested with the ray tree of shade_rays_surfaces (rr_render_surfaces): the same arguments, samples, resolve and
         outputs, every sample shaded as shade_rays_surfaces shades camera_rays(camera, width, height, *offset_s)."""
-        p = params if params is not None else default_params()
-        w, h = int(width), int(height)
-        offp, n = _sample_offsets(samples, "render_surfaces: samples must be an int or an [S, 2] array")
-        if n < 0 or w < 0 or h < 0:
-            raise ValueError("render_surfaces: negative size")
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_surfaces_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_surfaces_device")
-        else:
-            self._ck(self._L.rr_render_surfaces(self._h, w, h, C.byref(camera), C.byref(p), offp, n, *ptrs), "rr_render_surfaces")
-        return _result(outs)
+        return self._supersampled("render_surfaces", width, height, camera, samples, params, rgba8, ray_counts, device)
 
     def set_material_bands(self, iors, weights=None):
         """The band set of render_composed (rr_set_material_bands): iors is a float32 [B, rows] array, row b the indices of
@@ -959,9 +914,7 @@ class Renderer:
                     raise ValueError("render_composed: paired=True needs an array of band indices")
                 idx = np.zeros(len(pos), np.uint32)
             elif paired:
-                idx = np.ascontiguousarray(bands, np.int64).reshape(-1)
-                if len(idx) != len(pos) or (idx < 0).any():
-                    raise ValueError("render_composed: paired=True needs one band index >= 0 per sample")
+                idx, = _paired_indices(len(pos), "render_composed: paired=True needs one band index >= 0 per sample", bands)
             else:
                 if not isinstance(bands, (int, np.integer)) or bands < 1:
                     raise ValueError("render_composed: bands must be None, an int >= 1 or, with paired=True, an array of indices")
@@ -971,21 +924,14 @@ class Renderer:
                 pos = np.repeat(pos, int(bands), axis=0)
             rec = np.zeros(len(pos), _capi.COMPOSED_SAMPLE_DTYPE)
             rec["offset"], rec["band"] = pos, idx
-            if lens_samples is not None:
-                loff = np.ascontiguousarray(lens_samples, np.float32)
-                if loff.shape != (len(rec), 2) or len(rec) == 0:
-                    raise ValueError("render_composed: lens_samples must be an [S, 2] array with one row per sample")
-                rec["lens_offset"] = loff
-            elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
-                rec["lens_offset"] = lens_pattern(len(rec))
+            _per_sample(rec, "lens_offset", lens_samples, lens_pattern, "render_composed: lens_samples")
+        return self._record_frame("render_composed", w, h, camera, p, rec, lens, rgba8, ray_counts, device)
+
+    def _record_frame(self, name, w, h, camera, p, rec, lens, rgba8, ray_counts, device):
+        """the call of render_composed, render_shutter and render_lit: a frame over sample records and an optional lens"""
         recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
         lp = C.byref(lens) if lens is not None else None
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_composed_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed_device")
-        else:
-            self._ck(self._L.rr_render_composed(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_composed")
-        return _result(outs)
+        return self._frame(name, w, h, rgba8, (ray_counts,), device, C.byref(camera), C.byref(p), recp, len(rec), lp)
 
     def capture_scene_key(self, key):
         """Freezes the scene a render call issued now would trace as scene key `key` (rr_capture_scene_key), 0 <= key <
@@ -1032,31 +978,17 @@ class Renderer:
             offp, n = _sample_offsets(samples, "render_shutter: samples must be an int, an [S, 2] array or a SHUTTER_SAMPLE_DTYPE array")
             pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
             if paired:
-                kidx = np.ascontiguousarray(keys, np.int64).reshape(-1)
-                bidx = np.zeros(len(pos), np.int64) if bands is None else np.ascontiguousarray(bands, np.int64).reshape(-1)
-                if isinstance(keys, (int, np.integer)) or len(kidx) != len(pos) or len(bidx) != len(pos) or (kidx < 0).any() or (bidx < 0).any():
-                    raise ValueError("render_shutter: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample")
                 rec = np.zeros(len(pos), _capi.SHUTTER_SAMPLE_DTYPE)
-                rec["offset"], rec["key"], rec["band"] = pos, kidx, bidx
-                if lens_samples is not None:
-                    loff = np.ascontiguousarray(lens_samples, np.float32)
-                    if loff.shape != (len(rec), 2) or len(rec) == 0:
-                        raise ValueError("render_shutter: lens_samples must be an [S, 2] array with one row per sample")
-                    rec["lens_offset"] = loff
-                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
-                    rec["lens_offset"] = lens_pattern(len(rec))
+                rec["offset"] = pos
+                rec["key"], rec["band"] = _paired_indices(
+                    len(pos), "render_shutter: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample", keys, bands,
+                    refuse=isinstance(keys, (int, np.integer)))
+                _per_sample(rec, "lens_offset", lens_samples, lens_pattern, "render_shutter: lens_samples")
             else:
                 if not isinstance(keys, (int, np.integer)) or keys < 1 or not (bands is None or (isinstance(bands, (int, np.integer)) and bands >= 1)):
                     raise ValueError("render_shutter: keys must be an int >= 1 and bands None or an int >= 1, or both arrays with paired=True")
                 rec = shutter_samples(pos, int(keys), bands, lens_samples)
-        recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
-        lp = C.byref(lens) if lens is not None else None
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_shutter_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter_device")
-        else:
-            self._ck(self._L.rr_render_shutter(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_shutter")
-        return _result(outs)
+        return self._record_frame("render_shutter", w, h, camera, p, rec, lens, rgba8, ray_counts, device)
 
     def set_light_shapes(self, shapes=None):
         """The shapes of the lights (rr_set_light_shapes): a LIGHT_SHAPE_DTYPE array or a list of light_shape(ex, ey) rows, one per
@@ -1089,38 +1021,18 @@ class Renderer:
             offp, n = _sample_offsets(samples, "render_lit: samples must be an int, an [S, 2] array or a LIT_SAMPLE_DTYPE array")
             pos = sample_pattern(n) if offp is None else np.ascontiguousarray(samples, np.float32)
             if paired:
-                kidx = np.ascontiguousarray(keys, np.int64).reshape(-1)
-                bidx = np.zeros(len(pos), np.int64) if bands is None else np.ascontiguousarray(bands, np.int64).reshape(-1)
-                if isinstance(keys, (int, np.integer)) or len(kidx) != len(pos) or len(bidx) != len(pos) or (kidx < 0).any() or (bidx < 0).any():
-                    raise ValueError("render_lit: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample")
                 rec = np.zeros(len(pos), _capi.LIT_SAMPLE_DTYPE)
-                rec["offset"], rec["key"], rec["band"] = pos, kidx, bidx
-                if lens_samples is not None:
-                    loff = np.ascontiguousarray(lens_samples, np.float32)
-                    if loff.shape != (len(rec), 2) or len(rec) == 0:
-                        raise ValueError("render_lit: lens_samples must be an [S, 2] array with one row per sample")
-                    rec["lens_offset"] = loff
-                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
-                    rec["lens_offset"] = lens_pattern(len(rec))
-                if light_samples is not None:
-                    lo = np.ascontiguousarray(light_samples, np.float32)
-                    if lo.shape != (len(rec), 2) or len(rec) == 0:
-                        raise ValueError("render_lit: light_samples must be an [S, 2] array with one row per sample")
-                    rec["light_offset"] = lo
-                elif 1 <= len(rec) <= _capi.MAX_SAMPLES:
-                    rec["light_offset"] = light_pattern(len(rec))
+                rec["offset"] = pos
+                rec["key"], rec["band"] = _paired_indices(
+                    len(pos), "render_lit: paired=True needs one key index >= 0 (and, if given, one band index >= 0) per sample", keys, bands,
+                    refuse=isinstance(keys, (int, np.integer)))
+                _per_sample(rec, "lens_offset", lens_samples, lens_pattern, "render_lit: lens_samples")
+                _per_sample(rec, "light_offset", light_samples, light_pattern, "render_lit: light_samples")
             else:
                 if not isinstance(keys, (int, np.integer)) or keys < 1 or not (bands is None or (isinstance(bands, (int, np.integer)) and bands >= 1)):
                     raise ValueError("render_lit: keys must be an int >= 1 and bands None or an int >= 1, or both arrays with paired=True")
                 rec = lit_samples(pos, int(keys), bands, lens_samples, light_samples)
-        recp = rec.ctypes.data_as(C.c_void_p) if len(rec) else None
-        lp = C.byref(lens) if lens is not None else None
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_lit_device(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_lit_device")
-        else:
-            self._ck(self._L.rr_render_lit(self._h, w, h, C.byref(camera), C.byref(p), recp, len(rec), lp, *ptrs), "rr_render_lit")
-        return _result(outs)
+        return self._record_frame("render_lit", w, h, camera, p, rec, lens, rgba8, ray_counts, device)
 
     def render_lens(self, width, height, camera, lens, samples=16, lens_samples=None, params=None, rgba8=False, ray_counts=False, device=False):
         """Thin-lens frame (rr_render_lens): render_samples with a lens of finite aperture -- sample s of a pixel starts at lens
@@ -1142,12 +1054,7 @@ class Renderer:
                 raise ValueError("render_lens: lens_samples must be an [S, 2] array with one row per sample")
             loffp = loff.ctypes.data_as(C.c_void_p)
         lp = C.byref(lens) if lens is not None else None
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_lens_device(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens_device")
-        else:
-            self._ck(self._L.rr_render_lens(self._h, w, h, C.byref(camera), C.byref(p), offp, loffp, n, lp, *ptrs), "rr_render_lens")
-        return _result(outs)
+        return self._frame("render_lens", w, h, rgba8, (ray_counts,), device, C.byref(camera), C.byref(p), offp, loffp, n, lp)
 
     def render_spectral(self, width, height, camera, bands=8, samples=4, params=None, abbe=30.0, paired=False, rgba8=False, ray_counts=False,
                         device=False):
@@ -1181,12 +1088,7 @@ class Renderer:
                 tab = np.ascontiguousarray(np.tile(tab, n))
                 offp, n = off.ctypes.data_as(C.c_void_p), len(off)
             bandp = tab.ctypes.data_as(C.c_void_p)
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts,), "cuda:%d" % self.device if device else None)
-        if device:
-            self._ck(self._L.rr_render_spectral_device(self._h, w, h, C.byref(camera), C.byref(p), offp, bandp, n, *ptrs), "rr_render_spectral_device")
-        else:
-            self._ck(self._L.rr_render_spectral(self._h, w, h, C.byref(camera), C.byref(p), offp, bandp, n, *ptrs), "rr_render_spectral")
-        return _result(outs)
+        return self._frame("render_spectral", w, h, rgba8, (ray_counts,), device, C.byref(camera), C.byref(p), offp, bandp, n)
 
     def render_adaptive(self, width, height, camera, samples=(4, 16), threshold=ADAPTIVE_THRESHOLD, params=None, rgba8=False, ray_counts=False,
                         sample_counts=False, device=False):
@@ -1208,7 +1110,7 @@ class Renderer:
         offp, n_max = _sample_offsets(top, "render_adaptive: samples must be (n_base, n_max) or (n_base, [S, 2] array)")
         if n_base < 0 or n_max < 0 or w < 0 or h < 0:
             raise ValueError("render_adaptive: negative size")
-        outs, ptrs = _outputs((h, w), rgba8, (ray_counts, sample_counts), "cuda:%d" % self.device if device else None)
+        args = (C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold))
         if device:
             import torch
             nbytes = int(self._L.rr_host_adaptive_workspace_bytes(w, h))
@@ -1222,13 +1124,10 @@ class Renderer:
                 if ws is not None:
                     self.wait()
                 ws = pool[key] = torch.empty((max(nbytes, 16) // 16, 4), dtype=torch.float32, device="cuda:%d" % self.device)
-            self._ck(self._L.rr_render_adaptive_device(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), *ptrs,
-                                                       C.c_void_p(ws.data_ptr()), ws.numel() * 4), "rr_render_adaptive_device")
-            return _result(outs)
+            return self._frame("render_adaptive", w, h, rgba8, (ray_counts, sample_counts), True, *args, tail=(C.c_void_p(ws.data_ptr()), ws.numel() * 4))
         n_ref = C.c_uint64(0)
-        self._ck(self._L.rr_render_adaptive(self._h, w, h, C.byref(camera), C.byref(p), offp, n_base, n_max, float(threshold), *ptrs,
-                                            C.byref(n_ref)), "rr_render_adaptive")
-        return tuple(a for a in outs if a is not None) + (int(n_ref.value),)
+        out = self._frame("render_adaptive", w, h, rgba8, (ray_counts, sample_counts), False, *args, tail=(C.byref(n_ref),))
+        return (out if isinstance(out, tuple) else (out,)) + (int(n_ref.value),)
 
     def env_lookup(self, dirs):
         """Miss (RayTracing.hlsl:127-137) on an [n,3] array of directions -> [n,3] texels."""

@@ -50,9 +50,6 @@ DispatchDev shading_args(const rr_dispatch_params& p)
     return a;
 }
 
-// a radiance query's outputs (device pointers, any may be null)
-struct ShadeOut { float4* f32; uint32_t* rgba8; uint32_t* n_rays; };
-
 // The host variants' outputs pass through the context's one staged set (rr_context.h).  stage: grows what the call wants to n
 // elements and gives the launch its device pointers.  fetch: copies back to the caller's arrays (null: not wanted) and waits.
 int stage(rr_context* ctx, size_t n, bool want_f32, bool want_rgba8, bool want_n, ShadeOut& out)
@@ -157,7 +154,7 @@ int rays_shell(rr_context* ctx, const char* who, const RayTree& tree, const void
 
 hipError_t shade_plain(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    return launch_shade_rays(sc, a, d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream);
+    return launch_shade_rays(sc, a, d_rays, n, out, v, ctx->stream);
 }
 const RayTree kShadeRays = { "shade_rays", nullptr, shade_plain };
 
@@ -250,7 +247,7 @@ int samples_pair(rr_context* ctx, SamplesReq q, const FrameTree& tree, const Cal
 
 hipError_t frame_plain(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    return launch_render_samples(f.sc, f.a, f.cam, off, n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream);
+    return launch_render_samples(f.sc, f.a, f.cam, off, n_samples, out, f.v, ctx->stream);
 }
 const FrameTree kSamples = { nullptr, frame_plain };
 
@@ -273,8 +270,8 @@ int check_adaptive(rr_context* ctx, const AdaptiveReq& q, bool have_colour, Samp
 int adaptive_impl(rr_context* ctx, const AdaptiveReq& q, const SampleOffsets& off, const ShadeOut& out, uint32_t* n_taken, const AdaptiveWorkspace& ws)
 {
     const FrameArgs f = frame_args(ctx, q.s);
-    if (hipError_t e = launch_render_adaptive(f.sc, f.a, f.cam, off, q.n_base, q.s.n_samples, q.threshold, ws, out.f32, out.rgba8, out.n_rays, n_taken,
-                                              f.v.stack, f.v.pend, f.v.stack16, (uint32_t)ctx->dbg_refine_groups, ctx->stream))
+    if (hipError_t e = launch_render_adaptive(f.sc, f.a, f.cam, off, q.n_base, q.s.n_samples, q.threshold, ws, n_taken,
+                                              (uint32_t)ctx->dbg_refine_groups, out, f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -341,8 +338,7 @@ int check_lens(rr_context* ctx, const LensReq& q, bool have_colour, SampleOffset
 int lens_impl(rr_context* ctx, const LensReq& q, const SampleOffsets& off, const SampleOffsets& loff, const LensDev& lens, const ShadeOut& out)
 {
     const FrameArgs f = frame_args(ctx, q.s, q.lens);
-    if (hipError_t e = launch_render_lens(f.sc, f.a, f.cam, off, loff, lens, q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend,
-                                          f.v.stack16, ctx->stream))
+    if (hipError_t e = launch_render_lens(f.sc, f.a, f.cam, off, loff, lens, q.s.n_samples, out, f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -386,8 +382,7 @@ int check_spectral(rr_context* ctx, const SpectralReq& q, bool have_colour, Samp
 int spectral_impl(rr_context* ctx, const SpectralReq& q, const SampleOffsets& off, const BandTable& bands, const ShadeOut& out)
 {
     const FrameArgs f = frame_args(ctx, q.s);
-    if (hipError_t e = launch_render_spectral(f.sc, f.a, f.cam, off, bands, q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend,
-                                              f.v.stack16, ctx->stream))
+    if (hipError_t e = launch_render_spectral(f.sc, f.a, f.cam, off, bands, q.s.n_samples, out, f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -420,13 +415,11 @@ uint32_t inst0_material(const rr_context* ctx) { return ctx->inst_host.empty() ?
 // the ray tree with the material table (p: after check_materials), on caller rays and as a frame
 hipError_t shade_mat(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    return launch_shade_rays_mat(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16,
-                                 ctx->stream);
+    return launch_shade_rays_mat(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out, v, ctx->stream);
 }
 hipError_t frame_mat(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    return launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack,
-                                   f.v.pend, f.v.stack16, ctx->stream);
+    return launch_render_materials(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out, f.v, ctx->stream);
 }
 const RayTree kShadeMaterials = { "shade_rays_materials", check_materials, shade_mat };
 const FrameTree kMaterials = { check_materials, frame_mat };
@@ -443,13 +436,11 @@ int check_nested(rr_context* ctx, const char* who, rr_dispatch_params& p)
 // the material trees with the nested tree (p: after check_nested)
 hipError_t shade_nested(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    return launch_shade_rays_nested(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out.f32, out.rgba8, out.n_rays, v.stack, v.pend, v.stack16,
-                                    ctx->stream);
+    return launch_shade_rays_nested(sc, a, ctx->d_mats.get(), inst0_material(ctx), d_rays, n, out, v, ctx->stream);
 }
 hipError_t frame_nested(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    return launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack,
-                                f.v.pend, f.v.stack16, ctx->stream);
+    return launch_render_nested(f.sc, f.a, f.cam, off, ctx->d_mats.get(), inst0_material(ctx), n_samples, out, f.v, ctx->stream);
 }
 const RayTree kShadeNested = { "shade_rays_nested", check_nested, shade_nested };
 const FrameTree kNested = { check_nested, frame_nested };
@@ -458,13 +449,13 @@ const FrameTree kNested = { check_nested, frame_nested };
 // under the entry point's own name, unlike its three siblings.
 hipError_t shade_surfaces(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n, out.f32,
-                                      out.rgba8, out.n_rays, v.stack, v.pend, v.stack16, ctx->stream);
+    return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n, out, v,
+                                      ctx->stream);
 }
 hipError_t frame_surfaces(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
     return launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), n_samples,
-                                  out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream);
+                                  out, f.v, ctx->stream);
 }
 const RayTree kShadeSurfaces = { nullptr, check_nested, shade_surfaces };
 const FrameTree kSurfaces = { check_nested, frame_surfaces };
@@ -526,7 +517,7 @@ int composed_impl(rr_context* ctx, const ComposedReq& q, const ComposedTables& t
     const FrameArgs f = frame_args(ctx, q.s, q.lens);
     const BandSet b = band_set(ctx);
     if (hipError_t e = launch_render_composed(f.sc, f.a, f.cam, t.off, t.loff, t.lens, t.band, b.mats, ctx->n_mats, b.weights, inst0_material(ctx),
-                                              q.s.n_samples, out.f32, out.rgba8, out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+                                              q.s.n_samples, out, f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.who, e);
     return RR_OK;
 }
@@ -613,8 +604,7 @@ int shutter_impl(rr_context* ctx, const ShutterReq& q, const ShutterTables& t, c
     const FrameArgs& f = m.f;
     const BandSet b = band_set(ctx);
     if (hipError_t e = launch_render_shutter(ctx->d_key_scenes.get(), m.single_identity, f.a, f.cam, t.c.off, t.c.loff, t.c.lens, t.c.band, t.key, b.mats,
-                                             ctx->n_mats, b.weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out.f32, out.rgba8,
-                                             out.n_rays, f.v.stack, f.v.pend, f.v.stack16, ctx->stream))
+                                             ctx->n_mats, b.weights, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.c.s.n_samples, out, f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.c.s.who, e);
     return RR_OK;
 }
@@ -683,8 +673,7 @@ int lit_impl(rr_context* ctx, const LitReq& q, const LitTables& t, const ShadeOu
     const BandSet b = band_set(ctx);
     if (hipError_t e = launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
                                          t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
-                                         ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out.f32, out.rgba8, out.n_rays, m.f.v.stack,
-                                         m.f.v.pend, m.f.v.stack16, ctx->stream))
+                                         ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream))
         return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
     return RR_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rr_types.h"
+#include "rr_choice.h"
 #include "host/rr_host_lens.h"
 
 namespace rr {
@@ -42,64 +43,80 @@ hipError_t launch_query_rays(const SceneDev& sc, const rr_ray_dev* rays, uint32_
 constexpr uint32_t RR_QUERY_MULTI_MAX_K = 16;
 hipError_t launch_query_multi(const SceneDev& sc, const rr_ray_dev* rays, uint32_t n, uint32_t k, rr_hit_dev* hits, uint32_t* counts,
                               uint32_t inst0_mask, int stack, hipStream_t s);
+// ---- the ray-tree launchers (rr_shade_rays.hip ... rr_render_adaptive.hip below) end in the same three parameters: out, the
+// rasters (or, for caller rays, arrays of n entries) to write, any of them null; v, the scene's FusedVariant (rr_choice.h), which
+// for_tree_variant (there) maps to the instantiation launched -- v.stack > 64 or v.pend > 8 is hipErrorInvalidValue; the stream
+struct ShadeOut { float4* f32; uint32_t* rgba8; uint32_t* n_rays; };
+// One launch of a ray-tree kernel template <STACK, PEND, TLAS, E>: the instantiation of FusedVariant v through the ladder, `groups`
+// workgroups of 256 lanes with that instantiation's LDS on stream s; the value is the launch's hipError_t.  (A function template
+// cannot be handed to a function, hence a macro.)
+#define RR_LAUNCH_TREE_KERNEL(kernel, single_identity, v, groups, s, ...)                                                                      \
+    for_tree_variant((single_identity), (v), [&](auto t_) {                                                                                    \
+        using T_ = decltype(t_);                                                                                                               \
+        hipLaunchKernelGGL((kernel<T_::stack, T_::pend, T_::tlas, typename T_::entry>), dim3(groups), dim3(256), T_::lds_bytes, (s), __VA_ARGS__); \
+        return hipGetLastError();                                                                                                              \
+    })
 // ---- rr_shade_rays.hip: radiance queries (rr_shade_rays[_device]): the render kernels' ray tree on caller rays.  a: the fields
-// shade_ray and store_pixel read; f32 / rgba8 / n_rays: n entries each, any of them may be null; stack, pend, stack16: the scene's
-// FusedVariant (rr_choice.h), which for_tree_variant (there) maps to the instantiation launched -- here and in the two launchers
-// below; stack > 64 or pend > 8 is hipErrorInvalidValue
-hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
-                             uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+// shade_ray and store_pixel read
+hipError_t launch_shade_rays(const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* rays, uint32_t n, const ShadeOut& out, FusedVariant v,
+                             hipStream_t s);
 // ---- rr_render_samples.hip: supersampled frames (rr_render_samples[_device]): n_samples primary rays per pixel of an a.W x a.H
 // frame through the sub-pixel positions off (pixel units), each with the ray tree of a radiance query, averaged in the kernel.
 // a: the fields shade_ray and store_pixel read, W, H, tmin_p, tmax_p and the scene's screen rectangle hx0..hy1; f32 / rgba8 /
-// n_rays: W * H rasters, any of them may be null; stack, pend, stack16: the scene's FusedVariant.  The offsets travel as a
-// kernel argument: 512 bytes
+// n_rays: W * H rasters.  The offsets travel as a kernel argument: 512 bytes
 struct SampleOffsets { static constexpr uint32_t MAX = 64; float v[2 * MAX]; };     // x0, y0, x1, y1, ...
+// What every frame launcher checks -- W, H in 1..32768, n_samples in 1..SampleOffsets::MAX, v as above: false is
+// hipErrorInvalidValue -- and the frame's raster of 8x8 blocks, four of them to a workgroup
+struct FrameBlocks { uint32_t blocks_x, n_blocks, groups; };
+inline bool frame_blocks(const DispatchDev& a, uint32_t n_samples, FusedVariant v, FrameBlocks& fb)
+{
+    if (a.W == 0 || a.H == 0 || a.W > 32768u || a.H > 32768u || n_samples == 0 || n_samples > SampleOffsets::MAX || v.stack > 64 || v.pend > 8) return false;
+    fb.blocks_x = (a.W + 7u) / 8u; fb.n_blocks = fb.blocks_x * ((a.H + 7u) / 8u);           // <= 4096 * 4096
+    fb.groups = (fb.n_blocks + 3u) / 4u;
+    return true;
+}
 hipError_t launch_render_samples(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_samples,
-                                 float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                                 const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_lens.hip: thin-lens frames (rr_render_lens[_device]): launch_render_samples with every sample's ray starting on
 // the lens (LensDev, host/rr_host_lens.h) at lens offset loff[s], in units of the radius, towards the focal-plane point of pixel
 // offset off[s]; lens.pinhole: the rays of launch_render_samples.  a.hx0..hy1: the scene's rectangle for the lens
 // (rr_host_lens_screen_rect).  Both tables and the lens travel as kernel arguments: 1056 bytes
 hipError_t launch_render_lens(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
-                              const LensDev& lens, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
-                              bool stack16, hipStream_t s);
+                              const LensDev& lens, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_spectral.hip: spectral frames (rr_render_spectral[_device]): launch_render_samples with sample k shaded with the
 // index of refraction of band k instead of a.ior / a.inv_ior, and its colour weighted per channel before the resolve's sum:
 // sum = w_0 * c_0, then sum + w_k * c_k in sample order, / n_samples.  inv_ior[k] = inv_ior_of(ior[k]) (rr_types.h), filled by the
 // host.  The band table travels as a kernel argument beside the offsets: 1280 bytes
 struct BandTable { static constexpr uint32_t MAX = SampleOffsets::MAX; float ior[MAX]; float inv_ior[MAX]; float weight[MAX][3]; };
 hipError_t launch_render_spectral(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const BandTable& bands,
-                                  uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
-                                  hipStream_t s);
+                                  uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_materials.hip: per-instance glass (rr_shade_rays_materials[_device], rr_render_materials[_device]):
 // launch_shade_rays and launch_render_samples with the ray tree of rr_render_materials.h -- an RGB path weight, the index of
 // refraction of the hit instance's material instead of a.ior / a.inv_ior, and Beer-Lambert absorption over the path inside the
 // glass.  mats: the context's table in device memory (rows of 32 bytes), which every InstDev::material of the scene indexes; mat0:
 // the index of instance 0, used where the scene skips the top level.  mats == nullptr is hipErrorInvalidValue
 hipError_t launch_shade_rays_mat(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, uint32_t mat0, const rr_ray_dev* rays, uint32_t n,
-                                 float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                                 const ShadeOut& out, FusedVariant v, hipStream_t s);
 hipError_t launch_render_materials(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
-                                   uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
-                                   bool stack16, hipStream_t s);
+                                   uint32_t mat0, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_nested.hip: nested media (rr_shade_rays_nested[_device], rr_render_nested[_device]): launch_shade_rays_mat and
 // launch_render_materials with the ray tree of rr_render_nested.h -- every ray carries the list of the media it is in, TraceRay sees
 // both faces, an interface refracts with n_from / n_to and absorption is the crossed medium's.  mats, mat0: as above, every row of
 // the scene <= NESTED_MAX_MATERIAL (the host checks)
 hipError_t launch_shade_rays_nested(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, uint32_t mat0, const rr_ray_dev* rays, uint32_t n,
-                                    float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                                    const ShadeOut& out, FusedVariant v, hipStream_t s);
 hipError_t launch_render_nested(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
-                                uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
-                                bool stack16, hipStream_t s);
+                                uint32_t mat0, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_surfaces.hip: opaque hit groups (rr_shade_rays_surfaces[_device], rr_render_surfaces[_device]): launch_shade_rays_nested
 // and launch_render_nested with the ray tree of rr_render_surfaces.h -- an instance whose row of the surface table is opaque is lit
 // by `lights` through shadow rays, emits and may continue as a mirror.  surfs: the context's table in device memory, n_surfs rows
 // (0: every row is glass, surfs may be null); rows at or beyond n_surfs are glass.  lights travels by value to the kernel
 hipError_t launch_shade_rays_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfDev* surfs, uint32_t n_surfs,
-                                      const LightsDev& lights, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, float4* f32, uint32_t* rgba8,
-                                      uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                                      const LightsDev& lights, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, const ShadeOut& out, FusedVariant v,
+                                      hipStream_t s);
 hipError_t launch_render_surfaces(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
-                                  const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t mat0, uint32_t n_samples, float4* f32,
-                                  uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                                  const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t mat0, uint32_t n_samples, const ShadeOut& out,
+                                  FusedVariant v, hipStream_t s);
 // ---- rr_render_composed.hip: composed frames (rr_render_composed[_device]): launch_render_nested with launch_render_lens' primary
 // rays (off, loff, lens; a.hx0..hy1 the lens rectangle, or the pinhole's when lens.pinhole) and launch_render_spectral's resolve.
 // Sample k is shaded under the table band_mats + b_k * n_rows (the context's band set: the bands' tables one behind the other,
@@ -112,8 +129,7 @@ struct SampleBands {
 };
 hipError_t launch_render_composed(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const SampleOffsets& loff,
                                   const LensDev& lens, const SampleBands& band, const MatDev* band_mats, uint32_t n_rows, const float* band_w,
-                                  uint32_t mat0, uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend,
-                                  bool stack16, hipStream_t s);
+                                  uint32_t mat0, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_shutter.hip: shutter frames (rr_render_shutter[_device]): launch_render_composed with the scene as one more
 // per-sample table entry.  keys: the context's RR_MAX_SCENE_KEYS records in device memory, written at rr_capture_scene_key; sample k
 // is traced in keys[key_k].sc with keys[key_k].mat0 -- every key_k captured and of the same kind (single_identity: all without a
@@ -129,8 +145,7 @@ struct SampleKeys {
 hipError_t launch_render_shutter(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
                                  const SampleOffsets& loff, const LensDev& lens, const SampleBands& band, const SampleKeys& key,
                                  const MatDev* band_mats, uint32_t n_rows, const float* band_w, const float4* env, int32_t env_w, int32_t env_h,
-                                 uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16,
-                                 hipStream_t s);
+                                 uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_lit.hip: lit shutter frames (rr_render_lit[_device]): launch_render_shutter over the ray tree of
 // launch_render_surfaces, with the lights per sample.  surfs, n_surfs, lights: as launch_render_surfaces.  shapes: per light the two
 // edges its position (or direction) moves along, by value; lgt: per sample the light offset (lu, lv), laid out as off -- sample k is
@@ -140,7 +155,7 @@ hipError_t launch_render_lit(const KeyDev* keys, bool single_identity, const Dis
                              const SampleOffsets& loff, const SampleOffsets& lgt, const LensDev& lens, const SampleBands& band, const SampleKeys& key,
                              const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs, uint32_t n_surfs,
                              const LightsDev& lights, const LightShapesDev& shapes, const float4* env, int32_t env_w, int32_t env_h,
-                             uint32_t n_samples, float4* f32, uint32_t* rgba8, uint32_t* n_rays, int stack, int pend, bool stack16, hipStream_t s);
+                             uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).
@@ -165,8 +180,8 @@ struct AdaptiveWorkspace {
     }
 };
 hipError_t launch_render_adaptive(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_base,
-                                  uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, float4* f32, uint32_t* rgba8, uint32_t* n_rays,
-                                  uint32_t* n_taken, int stack, int pend, bool stack16, uint32_t refine_groups, hipStream_t s);
+                                  uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, uint32_t* n_taken, uint32_t refine_groups, const ShadeOut& out,
+                                  FusedVariant v, hipStream_t s);
 // ---- rr_frame.hip: the screen-coordinate tables of a frame, and gathered tiles -> rasters
 hipError_t launch_screen_tables(float* out, uint32_t W, uint32_t H, hipStream_t s);
 hipError_t launch_assemble_tiles(const uint32_t* gathered, uint32_t* frame, uint32_t W, uint32_t H, uint32_t tiles_x,

@@ -186,37 +186,26 @@ __global__ __launch_bounds__(256, (ShadeWaves<STACK, TLAS, E>::value)) void k_ad
 }
 
 hipError_t launch_render_adaptive(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, uint32_t n_base,
-                                  uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, float4* f32, uint32_t* rgba8, uint32_t* n_rays,
-                                  uint32_t* n_taken, int stack, int pend, bool stack16, uint32_t refine_groups, hipStream_t s)
+                                  uint32_t n_max, float threshold, const AdaptiveWorkspace& ws, uint32_t* n_taken, uint32_t refine_groups, const ShadeOut& out,
+                                  FusedVariant v, hipStream_t s)
 {
-    if (a.W == 0 || a.H == 0 || a.W > 32768u || a.H > 32768u || n_base == 0 || n_base > n_max || n_max > SampleOffsets::MAX) return hipErrorInvalidValue;
-    if (stack > 64 || pend > 8) return hipErrorInvalidValue;
-    const uint32_t blocks_x = (a.W + 7u) / 8u, n_blocks = blocks_x * ((a.H + 7u) / 8u);         // <= 4096 * 4096
-    const uint32_t groups = (n_blocks + 3u) / 4u, worst = (uint32_t)(((size_t)a.W * a.H + 255u) / 256u);
+    FrameBlocks fb;
+    if (!frame_blocks(a, n_max, v, fb) || n_base == 0 || n_base > n_max) return hipErrorInvalidValue;
+    const uint32_t blocks_x = fb.blocks_x, n_blocks = fb.n_blocks, groups = fb.groups, worst = (uint32_t)(((size_t)a.W * a.H + 255u) / 256u);
     if (refine_groups == 0 || refine_groups > worst) refine_groups = worst;
     // both traced stages take the scene's FusedVariant through the ray-tree kernels' ladder (for_tree_variant, rr_choice.h)
     const bool si = sc.single_identity != 0u;
-    const FusedVariant v = { stack, pend, stack16 };
-    if (hipError_t e = for_tree_variant(si, v, [&](auto t) {
-            using T = decltype(t);
-            hipLaunchKernelGGL((k_adaptive_base<T::stack, T::pend, T::tlas, typename T::entry>), dim3(groups), dim3(256), T::lds_bytes, s, sc, a, cam, off,
-                               n_base, blocks_x, n_blocks, ws.rec, ws.cnt);
-            return hipGetLastError();
-        })) return e;
-    hipLaunchKernelGGL(k_adaptive_classify, dim3(groups), dim3(256), 0, s, a, n_base, n_max, threshold, blocks_x, n_blocks, ws.rec, ws.cnt, ws.masks, f32,
-                       rgba8, n_rays, n_taken);
+    if (hipError_t e = RR_LAUNCH_TREE_KERNEL(k_adaptive_base, si, v, groups, s, sc, a, cam, off, n_base, blocks_x, n_blocks, ws.rec, ws.cnt)) return e;
+    hipLaunchKernelGGL(k_adaptive_classify, dim3(groups), dim3(256), 0, s, a, n_base, n_max, threshold, blocks_x, n_blocks, ws.rec, ws.cnt, ws.masks, out.f32,
+                       out.rgba8, out.n_rays, n_taken);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(1024), 0, s, ws.masks, n_blocks, ws.base);
     if (hipError_t e = hipGetLastError()) return e;
     if (n_base == n_max) return hipSuccess;                     // no samples are left to take: classify has made every pixel final
     hipLaunchKernelGGL(k_adaptive_list, dim3(groups), dim3(256), 0, s, a.W, blocks_x, n_blocks, ws.masks, ws.base, ws.list);
     if (hipError_t e = hipGetLastError()) return e;
-    return for_tree_variant(si, v, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((k_adaptive_refine<T::stack, T::pend, T::tlas, typename T::entry>), dim3(refine_groups), dim3(256), T::lds_bytes, s, sc, a, cam,
-                           off, n_base, n_max, ws.list, ws.total, ws.rec, ws.cnt, f32, rgba8, n_rays);
-        return hipGetLastError();
-    });
+    return RR_LAUNCH_TREE_KERNEL(k_adaptive_refine, si, v, refine_groups, s, sc, a, cam, off, n_base, n_max, ws.list, ws.total, ws.rec, ws.cnt, out.f32, out.rgba8,
+                                 out.n_rays);
 }
 
 } // namespace rr

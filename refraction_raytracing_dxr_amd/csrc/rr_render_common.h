@@ -1,5 +1,5 @@
 // rr_render_common.h -- device code shared by the render kernels (rr_render_fused.hip, rr_render_paths.hip, rr_render_lds.hip,
-// rr_render_stream.hip, rr_shade_rays.hip, rr_render_samples.hip, rr_render_adaptive.hip, rr_render_lens.hip, rr_render_spectral.hip): a pixel's ray tree as the
+// rr_render_stream.hip, rr_render_adaptive.hip and, through rr_render_frame.h, the ray-tree kernels' files): a pixel's ray tree as the
 // lanes walk it (RayGen, ClosestHit / Miss, the parked reflected rays), the frame store, the counters, and the numbering of a dispatch's 8x8 pixel blocks.
 #pragma once
 #include <hip/hip_runtime.h>

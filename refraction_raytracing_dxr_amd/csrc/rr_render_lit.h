@@ -12,9 +12,11 @@
 // v_fma_f32 with scalar operands make v' in vector registers, once per light per opaque hit -- beside a shadow ray's walk, nothing.
 // No lane move, no scratch; DESIGN 5.15 has the code object's figures.
 //
-// The shadow ray has the two-site form only: a second trace_scene<..., QUERY = true> call site inside the opaque shader.
-// Reduction: with every light offset applied to a zero shape, or with no shape table, v' == v in value and the tree is
-// ray_tree_surfaces' operation for operation; with no surface table or every row glass it is ray_tree_nested's.
+// The tree is not a copy: ray_tree_surfaces_two_site (rr_render_surfaces.h) asks a callable for light row i, and this header hands it
+// moved_light where the surface kernels hand it the table's row.  So the shadow ray has the two-site form only, whichever form
+// rr_render_surfaces.hip is built with.
+// Reduction: with every light offset applied to a zero shape, or with no shape table, v' == v in value and the tree computes what
+// ray_tree_surfaces computes; with no surface table or every row glass, what ray_tree_nested computes.
 #pragma once
 #include "rr_render_surfaces.h"
 
@@ -33,56 +35,14 @@ __device__ __forceinline__ LightDev moved_light(const LightsDev& lights, const L
     return m;
 }
 
-// ray_tree_surfaces with the lights moved to (lu, lv): the shadow rays are traced where the hit is shaded
+// ray_tree_surfaces, two-site form, with the lights moved to (lu, lv)
 template <bool TLAS, class E, class PK>
 __device__ __forceinline__ f3 ray_tree_lit(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
                                            const LightsDev& lights, const LightShapesDev& shapes, float lu, float lv, uint32_t mat0,
                                            RayStateNested r, E* stk, PK& park, LaneStats& st)
 {
-    f3 acc = mk3(0.0f, 0.0f, 0.0f);
-    int np = 0;
-    for (;;) {
-        HitRecFace h;
-        trace_scene<false, TLAS, E, GlobalNodes>(sc, r.O, r.D, r.tmin, r.tmax, 0u, h, stk, st.cnt, Diag{ nullptr }, GlobalNodes{});
-        ++st.rays;
-        bool have_next = false;
-        if (!h.hit) {                                         // Miss
-            f3 e = env_lookup(sc, r.D);
-            acc.x = fmaf(r.w.x, e.x, acc.x); acc.y = fmaf(r.w.y, e.y, acc.y); acc.z = fmaf(r.w.z, e.z, acc.z);
-        } else if ((int)r.count < a.max_refract) {            // ClosestHit
-            const uint32_t row = hit_material<TLAS>(sc, h, mat0);
-            const uint32_t c = media_top(r.media);
-            if (c) absorb_crossed(mats, c, h.t, r.w);
-            const f3 X = mk3(fmaf(h.t, r.D.x, r.O.x), fmaf(h.t, r.D.y, r.O.y), fmaf(h.t, r.D.z, r.O.z));   // hlsl:88
-            if (row < sf.n && sf.rows[row].kind == SURFACE_OPAQUE) {
-                const f3 N = shading_normal<TLAS>(sc, h);
-                const f3 Nf = h.front ? N : neg3(N);
-                f3 Ev = mk3(lights.ambient[0], lights.ambient[1], lights.ambient[2]);
-                for (uint32_t i = 0; i < lights.n; ++i) {
-                    const LightDev lt = moved_light(lights, shapes, i, lu, lv);
-                    f3 Ld;
-                    float far, g;
-                    light_at(lt, a, X, Ld, far, g);
-                    const float cs = dot3(Nf, Ld);
-                    if (cs > 0.0f) {
-                        HitRecShadow hs;
-                        trace_scene<false, TLAS, E, GlobalNodes, true, HitRecShadow>(sc, X, Ld, a.tmin_s, far, 0u, hs, stk, st.cnt, Diag{ nullptr },
-                                                                                     GlobalNodes{}, TLAS ? lt.shadow_mask : (lt.shadow_mask & 1u), true);
-                        ++st.rays;
-                        if (!hs.hit) {
-                            const float f = cs * g;
-                            Ev.x = fmaf(lt.radiance[0], f, Ev.x); Ev.y = fmaf(lt.radiance[1], f, Ev.y); Ev.z = fmaf(lt.radiance[2], f, Ev.z);
-                        }
-                    }
-                }
-                have_next = opaque_end(a, sf.rows + row, Ev, Nf, X, r, acc);
-            } else {
-                have_next = glass_hit<TLAS>(sc, a, mats, h, row + 1u, X, r, np, park);
-            }
-        }
-        if (!have_next && !pop_parked(a, r, np, park)) break;
-    }
-    return acc;
+    return ray_tree_surfaces_two_site<TLAS, E>(sc, a, mats, sf, lights, [&](uint32_t i) { return moved_light(lights, shapes, i, lu, lv); }, mat0, r, stk,
+                                               park, st);
 }
 
 } // namespace rr

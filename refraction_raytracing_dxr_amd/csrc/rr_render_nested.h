@@ -182,18 +182,4 @@ __device__ __forceinline__ f3 ray_tree_nested(const SceneDev& sc, const Dispatch
     return acc;
 }
 
-// For the kernels that take the scene from a key record in memory (k_render_shutter, k_render_lit).  A pointer read from such a
-// record is a generic pointer to the compiler, which the tree would dereference with flat_load --
-// through the aperture check and both memory counters, the LDS stacks' among them -- where k_render_composed, whose pointers are
-// kernel arguments and known to be global, uses global_load with a scalar base.  The record's pointers are hipMalloc'ed device
-// memory: in_global says so, by way of the global address space and back.  The empty statement between the two casts keeps the
-// pair from being folded away before the address spaces are inferred; it holds the pointer in scalar registers, where it is anyway
-// (the record has a scalar address), and a pointer the build does not use is dropped with it.
-template <class T> __device__ __forceinline__ const T* in_global(const T* p)
-{
-    const __attribute__((address_space(1))) T* g = (const __attribute__((address_space(1))) T*)p;
-    asm("" : "+s"(g));
-    return (const T*)g;
-}
-
 } // namespace rr

@@ -30,6 +30,8 @@
 //     tree's own loop: the lane carries X, Nf, E, its light index and f = cs * g as state, and the site takes a per-lane mask (0xff
 //     for a radiance ray) and a per-lane first-hit flag.  Lanes that trace shadow rays stay converged with lanes that trace radiance
 //     rays, and there is one copy of the walk.  Its hit record, HitRecTree, skips the attributes of the hit on a shadow trip.
+// The two-site tree takes "light row i" as a callable (ray_tree_surfaces_two_site): the table's row for the surface kernels, the row
+// moved to one sample's offset for the lit frames (rr_render_lit.h), which use this form in either build.
 // The traversal stack is free while a hit is being shaded, so a shadow ray walks on the same LDS column.  The light rows sit in the
 // kernel-argument segment (LightsDev, rr_types.h) and every loop over them has a wave-uniform index, so they arrive through scalar
 // loads; the surface row differs per lane and comes through vector loads, as mats does.
@@ -165,11 +167,13 @@ __device__ __forceinline__ bool pop_parked(const DispatchDev& a, RayStateNested&
     return true;
 }
 
-#ifndef RR_SURFACES_ONE_SITE
-// ray_tree_nested with the opaque hit group, the shadow rays traced where the hit is shaded
-template <bool TLAS, class E, class PK>
-__device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
-                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st)
+// ray_tree_nested with the opaque hit group, two-site form: the shadow rays are traced where the hit is shaded.  light_row(i) is row
+// i of the lights as this tree sees it -- the table's row (a reference), or a copy of it moved for one sample (rr_render_lit.h); i is
+// wave-uniform.  lights itself gives the ambient term and the number of rows.  Built in either form's build: the lit frames use it
+template <bool TLAS, class E, class PK, class LR>
+__device__ __forceinline__ f3 ray_tree_surfaces_two_site(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
+                                                         const LightsDev& lights, LR&& light_row, uint32_t mat0, RayStateNested r, E* stk, PK& park,
+                                                         LaneStats& st)
 {
     f3 acc = mk3(0.0f, 0.0f, 0.0f);
     int np = 0;
@@ -191,7 +195,7 @@ __device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const Dispat
                 const f3 Nf = h.front ? N : neg3(N);
                 f3 Ev = mk3(lights.ambient[0], lights.ambient[1], lights.ambient[2]);
                 for (uint32_t i = 0; i < lights.n; ++i) {
-                    const LightDev& lt = lights.l[i];
+                    const LightDev& lt = light_row(i);                    // (a copy lives as long as lt)
                     f3 Ld;
                     float far, g;
                     light_at(lt, a, X, Ld, far, g);
@@ -215,6 +219,15 @@ __device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const Dispat
         if (!have_next && !pop_parked(a, r, np, park)) break;
     }
     return acc;
+}
+
+#ifndef RR_SURFACES_ONE_SITE
+// the surface kernels' tree: the lights are the table's rows
+template <bool TLAS, class E, class PK>
+__device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
+                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st)
+{
+    return ray_tree_surfaces_two_site<TLAS, E>(sc, a, mats, sf, lights, [&](uint32_t i) -> const LightDev& { return lights.l[i]; }, mat0, r, stk, park, st);
 }
 #else
 // ray_tree_nested with the opaque hit group, one trace site: a lane's trip is a radiance ray or, while it shades an opaque hit, the

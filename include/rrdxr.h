@@ -696,9 +696,11 @@ int  rr_render_nested_device(rr_context* ctx, uint32_t width, uint32_t height, c
  *
  * Reduction: with no surface table, or with every row glass, the four calls equal the _nested calls byte for byte in colours, RGBA8
  * and counts.  The lights are then never read.
- * Not covered: transparent shadows; area lights or environment lighting of opaque surfaces in these four calls; textures; opaque
- * rows in rr_render_composed / rr_render_shutter, the dispatch kernels and the _materials calls (all of which ignore the surface
- * table).  Opaque rows through a lens, over scene keys and under lights with an area are rr_render_lit's, below.
+ * Not covered: area lights or environment lighting of opaque surfaces in these four calls; textures; opaque rows in
+ * rr_render_composed / rr_render_shutter, the dispatch kernels and the _materials calls (all of which ignore the surface table).
+ * Opaque rows through a lens, over scene keys and under lights with an area are rr_render_lit's, below.  Shadow rays that pass
+ * glass and take its tint are opt-in (rr_set_shadow_steps, further below); what they leave out: Fresnel loss and bending at the
+ * interfaces a shadow ray crosses, absorption beyond its last hit, caustics.
  *
  * State and rows as the nested calls: RR_ERR_STATE without a built TLAS or without a material table; RR_ERR_INVALID_ARGUMENT when an
  * instance's row is >= the material table's length or > RR_NESTED_MAX_MATERIAL. */
@@ -852,8 +854,10 @@ int  rr_render_shutter_device(rr_context* ctx, uint32_t width, uint32_t height, 
  * same records; with one key that is a capture of the live scene, no lens, no band set and no shape table (or one of zeros),
  * rr_render_surfaces on the samples' positions.
  * Stated limits: a shaped light is a rectangle of point emitters -- there is no cosine at the light and no normalisation by its
- * area; the caller's radiance is per sample, and the / n_samples of the resolve averages it.  Any accepted hit still occludes.
- * Not covered: a camera per key, textures, environment lighting of opaque surfaces, transparent shadows. */
+ * area; the caller's radiance is per sample, and the / n_samples of the resolve averages it.  Any accepted hit still occludes,
+ * unless rr_set_shadow_steps (below) says otherwise.
+ * Not covered: a camera per key, textures, environment lighting of opaque surfaces; and of a shadow ray that passes glass:
+ * Fresnel loss and bending at the interfaces, absorption beyond its last hit, caustics. */
 typedef struct rr_light_shape { float ex[3]; float ey[3]; uint32_t pad[2]; } rr_light_shape;                                        /* 32 bytes */
 typedef struct rr_lit_sample { float offset[2]; float lens_offset[2]; uint32_t band; uint32_t key; float light_offset[2]; } rr_lit_sample; /* 32 bytes */
 int  rr_set_light_shapes(rr_context* ctx, const rr_light_shape* shapes, uint32_t n);
@@ -864,6 +868,46 @@ int  rr_render_lit(rr_context* ctx, uint32_t width, uint32_t height, const rr_sc
 int  rr_render_lit_device(rr_context* ctx, uint32_t width, uint32_t height, const rr_scene_constants* constants,
                           const rr_dispatch_params* params, const rr_lit_sample* samples, uint32_t n_samples, const rr_lens* lens,
                           void* d_rgba32f, void* d_rgba8, void* d_n_rays);
+
+/* ---- transparent shadows: shadow rays pass glass and take its tint (additive; the ABI version stays 3) ------------------------------
+ * Opt-in.  rr_set_shadow_steps(ctx, K) sets shadow_steps, 0 <= K <= RR_SHADOW_MAX_STEPS.  K = 0, the setting after rr_create,
+ * changes nothing anywhere: step b of the opaque hit group stands as written above.  With K >= 1 the shadow ray of step b is a
+ * straight WALK through the glass between the opaque hit and the light, attenuated by what it crosses and stopped only by an opaque
+ * surface -- a glass of tinted water casts a tinted shadow, not a black one and not none.  The setting is read by the four _surfaces
+ * calls and by rr_render_lit[_device], at the call; nothing else reads it, and rr_set_lights / rr_set_surfaces / rr_set_materials
+ * leave it alone.  It travels by value with every launch, so the setter waits for nothing.  K > RR_SHADOW_MAX_STEPS is
+ * RR_ERR_INVALID_ARGUMENT and the setting in force stays.  rr_get_shadow_steps reads the setting in force.
+ *
+ * The contract, with K >= 1, for a light the hit faces (cs > 0; Ld, far, g as in step b).  One rounding per written operation,
+ * fmaf only where written:
+ *   Start.  T = (1, 1, 1), Ls = L (the media list of the radiance ray at the hit), Xs = X, fs = far.
+ *   Each of up to K calls: TraceRay(Xs, Ld, [tmin_secondary, fs], cull flags 0, closest hit, InstanceInclusionMask = shadow_mask).
+ *   Each call counts one ray in n_rays.
+ *     Miss: the walk ends lit.
+ *     Hit on a row whose surface kind is opaque: the walk ends occluded; the light adds nothing.
+ *     Hit on a glass row m at t:
+ *       1. c = top(Ls).  If c is not air, T.ch = T.ch * rr_expf_neg(-(sigma_c.ch * t)): the medium CROSSED, as in the nested calls.
+ *       2. Ls = front ? push(Ls, m) : remove(Ls, m), with the nested calls' rules: a push onto a full list is dropped, removing an
+ *          absent row is a no-op.
+ *       3. Xs.ch = fmaf(t, Ld.ch, Xs.ch) and fs = fs - t.
+ *       4. If !(fs > tmin_secondary), the walk ends lit.
+ *       5. If this was the K-th call, the walk ends occluded: the cap is conservative.
+ *   Lit.  f = cs * g and E.ch = fmaf(radiance.ch, f * T.ch, E.ch).
+ * A scene without a top level walks its one instance (mask 1, row of instance 0) the same way if shadow_mask & 1; otherwise the
+ * first call misses.  In rr_render_lit the walk goes towards the light as moved for the sample, so a shaped light's soft shadow
+ * takes the glass's colour.
+ *
+ * Reductions, byte for byte in colours, RGBA8 and ray counts:
+ *   - any K equals K = 0 wherever no shadow ray's first hit is glass, since f * 1.0f == f;
+ *   - K = 1 equals K = 0 on every scene, but for a glass hit closer than tmin_secondary to the far end of its interval, which
+ *     step 4 lets through.
+ * Not modelled: Fresnel loss and bending at the interfaces -- no normal is fetched on the walk, which is straight and loses only
+ * what the media absorb; absorption beyond the last hit, for a light inside a medium; caustics.  Before this setting existed the
+ * lists above named "transparent shadows" among what is not covered; the advice given there, an InstanceMask bit the light's
+ * shadow_mask lacks, still makes glass cast no shadow at all. */
+#define RR_SHADOW_MAX_STEPS 16
+int  rr_set_shadow_steps(rr_context* ctx, uint32_t k);
+int  rr_get_shadow_steps(rr_context* ctx, uint32_t* k);
 
 /* Miss on caller-supplied ray directions (host arrays of n x 3 floats in, n x 3 floats out): the equirectangular lookup
  * of RayTracing.hlsl:127-137 in isolation -- atan2 / acos, the division by the literal 3.14159, the float-to-uint texel

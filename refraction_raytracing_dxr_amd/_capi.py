@@ -76,6 +76,7 @@ assert SURFACE_DTYPE.itemsize == 48 and LIGHT_DTYPE.itemsize == 32
 LIGHT_SHAPE_DTYPE = np.dtype([("ex", "<f4", 3), ("ey", "<f4", 3), ("pad", "<u4", 2)])
 LIT_SAMPLE_DTYPE = np.dtype([("offset", "<f4", 2), ("lens_offset", "<f4", 2), ("band", "<u4"), ("key", "<u4"), ("light_offset", "<f4", 2)])
 assert LIGHT_SHAPE_DTYPE.itemsize == 32 and LIT_SAMPLE_DTYPE.itemsize == 32 and LIT_SAMPLE_DTYPE.fields["light_offset"][1] == 24
+SHADOW_MAX_STEPS = 16                    # RR_SHADOW_MAX_STEPS: the most TraceRay calls a transparent shadow's walk may take (set_shadow_steps)
 MAX_SCENE_KEYS = 16                      # RR_MAX_SCENE_KEYS: scene keys a context holds (capture_scene_key)
 ALL_SCENE_KEYS = 0xFFFFFFFF              # RR_ALL_SCENE_KEYS: release_scene_key's "every key"
 
@@ -238,6 +239,8 @@ SYMBOLS = {
                                 C.POINTER(Lens), _P, _P, _P]),
     "rr_render_lit_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SceneConstants), C.POINTER(DispatchParams), _P, C.c_uint32,
                                        C.POINTER(Lens), _P, _P, _P]),
+    "rr_set_shadow_steps": (C.c_int, [_P, C.c_uint32]),
+    "rr_get_shadow_steps": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "rr_env_lookup": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "rr_comm_unique_id": (C.c_int, [_P]),
     "rr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -449,11 +449,17 @@ const FrameTree kNested = { check_nested, frame_nested };
 // under the entry point's own name, unlike its three siblings.
 hipError_t shade_surfaces(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
+    if (ctx->shadow_steps)                                      // transparent shadows: the walk's kernels (rr_render_shadows.hip)
+        return launch_shade_rays_shadows(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->shadow_steps, inst0_material(ctx),
+                                         d_rays, n, out, v, ctx->stream);
     return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n, out, v,
                                       ctx->stream);
 }
 hipError_t frame_surfaces(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
+    if (ctx->shadow_steps)
+        return launch_render_shadows(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->shadow_steps,
+                                     inst0_material(ctx), n_samples, out, f.v, ctx->stream);
     return launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), n_samples,
                                   out, f.v, ctx->stream);
 }
@@ -671,10 +677,14 @@ int lit_impl(rr_context* ctx, const LitReq& q, const LitTables& t, const ShadeOu
 {
     const ShutterFrame m = shutter_frame(ctx, q.s, t.s);
     const BandSet b = band_set(ctx);
-    if (hipError_t e = launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
-                                         t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
-                                         ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream))
-        return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
+    const hipError_t e = ctx->shadow_steps
+        ? launch_render_lit_shadows(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
+                                    t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
+                                    ctx->shadow_steps, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream)
+        : launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
+                            t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
+                            ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream);
+    if (e) return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
     return RR_OK;
 }
 
@@ -1034,6 +1044,24 @@ int rr_set_lights(rr_context* ctx, const rr_light* lights, uint32_t n, const flo
     RR_HIP(hipStreamSynchronize(ctx->stream));
     ctx->lights = t;
     ctx->light_shapes = LightShapesDev{};                       // (row i belonged with the old light i)
+    return RR_OK;
+}
+
+static_assert(SHADOW_MAX_STEPS == RR_SHADOW_MAX_STEPS, "the launchers' cap is the header's");
+int rr_set_shadow_steps(rr_context* ctx, uint32_t k)
+{
+    if (!ctx) return RR_ERR_INVALID_ARGUMENT;
+    if (k > RR_SHADOW_MAX_STEPS) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_set_shadow_steps: need k <= RR_SHADOW_MAX_STEPS (16)");
+    // the cap travels by value with every launch, so nothing is waited for: a launch in flight keeps the one it was given
+    ctx->shadow_steps = k;
+    return RR_OK;
+}
+
+int rr_get_shadow_steps(rr_context* ctx, uint32_t* k)
+{
+    if (!ctx) return RR_ERR_INVALID_ARGUMENT;
+    if (!k) return fail(ctx, RR_ERR_INVALID_ARGUMENT, "rr_get_shadow_steps: null k");
+    *k = ctx->shadow_steps;
     return RR_OK;
 }
 

@@ -156,6 +156,22 @@ hipError_t launch_render_lit(const KeyDev* keys, bool single_identity, const Dis
                              const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs, uint32_t n_surfs,
                              const LightsDev& lights, const LightShapesDev& shapes, const float4* env, int32_t env_w, int32_t env_h,
                              uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
+// ---- rr_render_shadows.hip: transparent shadows (rr_set_shadow_steps): launch_shade_rays_surfaces, launch_render_surfaces and
+// launch_render_lit over the ray tree of rr_render_shadows.h -- an opaque hit's shadow ray walks through glass, at most shadow_k
+// closest-hit calls, takes the tint of the media it crosses and is stopped only by an opaque row.  Arguments as the twins';
+// 1 <= shadow_k <= SHADOW_MAX_STEPS (0 is hipErrorInvalidValue: with the setting at 0 the host launches the twins)
+constexpr uint32_t SHADOW_MAX_STEPS = 16;
+hipError_t launch_shade_rays_shadows(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfDev* surfs, uint32_t n_surfs,
+                                     const LightsDev& lights, uint32_t shadow_k, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, const ShadeOut& out,
+                                     FusedVariant v, hipStream_t s);
+hipError_t launch_render_shadows(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
+                                 const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t shadow_k, uint32_t mat0, uint32_t n_samples,
+                                 const ShadeOut& out, FusedVariant v, hipStream_t s);
+hipError_t launch_render_lit_shadows(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
+                                     const SampleOffsets& loff, const SampleOffsets& lgt, const LensDev& lens, const SampleBands& band,
+                                     const SampleKeys& key, const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs,
+                                     uint32_t n_surfs, const LightsDev& lights, const LightShapesDev& shapes, uint32_t shadow_k, const float4* env,
+                                     int32_t env_w, int32_t env_h, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

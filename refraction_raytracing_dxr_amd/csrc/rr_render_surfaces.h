@@ -35,9 +35,10 @@
 // The traversal stack is free while a hit is being shaded, so a shadow ray walks on the same LDS column.  The light rows sit in the
 // kernel-argument segment (LightsDev, rr_types.h) and every loop over them has a wave-uniform index, so they arrive through scalar
 // loads; the surface row differs per lane and comes through vector loads, as mats does.
-// Not covered: transparent shadows, environment lighting of opaque surfaces, textures, opaque rows in the composed and shutter
-// frames, the dispatch kernels and the _materials calls.  (Opaque rows over scene keys, through a lens and under lights with an
-// area: rr_render_lit.h.)
+// Not covered: environment lighting of opaque surfaces, textures, opaque rows in the composed and shutter frames, the dispatch
+// kernels and the _materials calls.  (Opaque rows over scene keys, through a lens and under lights with an area: rr_render_lit.h.
+// Shadow rays that pass glass and take its tint: rr_render_shadows.h, whose walk leaves out Fresnel loss and bending at the
+// interfaces it crosses, absorption beyond its last hit, and caustics.)
 #pragma once
 #include "rr_render_nested.h"
 

@@ -11,6 +11,7 @@
 //          [--nested]                                              (with --materials: the nested-media ray tree, rr_render_nested)
 //          [--floor R,G,B[:S]]                                     (with --nested --materials: an opaque floor of that albedo under the mesh, with specular S in every channel; rr_render_surfaces)
 //          [--light x,y,z:R,G,B | --light @x,y,z:R,G,B]            (with --nested --materials, up to 8 times: a directional light towards (x, y, z), or with @ a point light at (x, y, z), of that radiance)
+//          [--transparent-shadows K]                               (with --floor and --light, 0 <= K <= 16: shadow rays pass glass in at most K steps and take its tint, rr_set_shadow_steps)
 //          [--compose]                                             (with --spp N and --materials: --lens, --dispersion and --nested together, rr_render_composed; the Abbe number applies to every row)
 //          [--shutter K:DT]                                        (with --compose: every frame over K scene keys spread over DT radians of the orbit, rr_render_shutter; N x K x BANDS <= 64)
 //          [--lit [--soft S]]                                      (with --compose, with or without --shutter: --floor and --light through the lens, rr_render_lit; every point light a square of half-edge S in the xz-plane)
@@ -86,6 +87,8 @@ int main(int argc, char** argv)
     std::vector<rr_light> lights;
     bool have_floor = false;
     float floor_albedo[3] = { 0.0f, 0.0f, 0.0f }, floor_specular = 0.0f;
+    bool have_shadow_steps = false;
+    int shadow_steps = 0;
     std::string out, idfile;
     for (int i = 1; i < argc; ++i) {
         auto arg = [&](const char* name) { return !strcmp(argv[i], name) && i + 1 < argc; };
@@ -102,6 +105,11 @@ int main(int argc, char** argv)
             int used = 0;
             if (sscanf(argv[++i], "%f%n", &soft, &used) != 1 || argv[i][used] != 0 || !(soft >= 0.0f) || !std::isfinite(soft)) { fprintf(stderr, "--soft takes S, a finite half-edge >= 0\n"); return 2; }
             have_soft = true;
+        }
+        else if (arg("--transparent-shadows")) {
+            int used = 0;
+            if (sscanf(argv[++i], "%d%n", &shadow_steps, &used) != 1 || argv[i][used] != 0 || shadow_steps < 0 || shadow_steps > RR_SHADOW_MAX_STEPS) { fprintf(stderr, "--transparent-shadows takes K, 0 <= K <= 16\n"); return 2; }
+            have_shadow_steps = true;
         }
         else if (arg("--frames-per-dispatch")) fpd = atoi(argv[++i]);
         else if (arg("--in-flight")) in_flight = atoi(argv[++i]);
@@ -171,7 +179,7 @@ int main(int argc, char** argv)
         else if (arg("--max-refract")) opt.dispatch.max_refract = atoi(argv[++i]);
         else if (arg("--max-reflect")) opt.dispatch.max_reflect = atoi(argv[++i]);
         else if (arg("--size")) { if (sscanf(argv[++i], "%dx%d", &opt.width, &opt.height) != 2) { fprintf(stderr, "bad --size\n"); return 2; } }
-        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]...]] [--compose [--shutter K:DT] [--lit [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]... [--soft S]]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rrdemo --mesh M.obj --env E.(hdr|png) [--size WxH] [--frames N] [--out f_%%03d.ppm] [--spp N [--adaptive BASE:THRESHOLD | --lens RADIUS:FOCUS]] [--dispersion BANDS[:ABBE]] [--materials IOR:R,G,B;... [--nested [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]... [--transparent-shadows K]]] [--compose [--shutter K:DT] [--lit [--floor R,G,B[:S]] [--light [@]x,y,z:R,G,B]... [--soft S]]]\n"); return 2; }
     }
     if (spp && (stream || pump || gpus > 0)) { fprintf(stderr, "--spp renders frame by frame: it cannot be combined with --stream, --pump or --gpus\n"); return 2; }
     if (compose) {          // the frames that refuse each other below, in one call: a lens and dispersion on the nested-media tree
@@ -201,6 +209,7 @@ int main(int argc, char** argv)
     if (surfaces && !lit && (!nested || materials.empty())) { fprintf(stderr, "--floor and --light need --nested --materials\n"); return 2; }
     if (surfaces && !lit && (compose || n_keys || base || have_lens || n_bands)) { fprintf(stderr, "--floor and --light render with the nested tree alone: they cannot be combined with --compose, --shutter, --adaptive, --lens or --dispersion\n"); return 2; }
     if (!lights.empty() && !have_floor) { fprintf(stderr, "--light needs --floor: glass is not lit by lights\n"); return 2; }
+    if (have_shadow_steps && (!have_floor || lights.empty())) { fprintf(stderr, "--transparent-shadows K needs --floor and --light: a shadow falls on the floor, from a light\n"); return 2; }
     if (gpus > 0 && rank < 0) return launch_ranks(argc, argv, gpus);
     if (gpus > 0) {         // one rank of a sharded run
         unsigned char id[128];
@@ -247,6 +256,10 @@ int main(int argc, char** argv)
     }
     if (have_floor && (rc = RefractionDemo::setFloorAndLights(floor_albedo, floor_specular, lights.data(), (int)lights.size())) != RR_OK) {
         fprintf(stderr, "setFloorAndLights failed (%d): %s\n", rc, RefractionDemo::lastError());
+        return 1;
+    }
+    if (have_shadow_steps && (rc = rr_set_shadow_steps(RefractionDemo::context(), (uint32_t)shadow_steps)) != RR_OK) {
+        fprintf(stderr, "rr_set_shadow_steps failed (%d): %s\n", rc, rr_last_error(RefractionDemo::context()));
         return 1;
     }
     if (have_soft && (rc = RefractionDemo::setLightSoftness(soft)) != RR_OK) {

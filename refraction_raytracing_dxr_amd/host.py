@@ -851,6 +851,20 @@ class Renderer:
         amb = None if ambient is None else np.ascontiguousarray(ambient, np.float32).reshape(3)
         self._ck(self._L.rr_set_lights(self._h, t.ctypes.data if len(t) else None, len(t), None if amb is None else amb.ctypes.data), "rr_set_lights")
 
+    def set_shadow_steps(self, k):
+        """Transparent shadows (rr_set_shadow_steps): 0, the default, leaves every shadow ray a first-hit ray that any instance stops,
+        glass included.  With 1 <= k <= SHADOW_MAX_STEPS the shadow ray of an opaque hit walks straight through the glass between
+        the hit and the light, k closest-hit calls at most (each counted in the ray counts): every stretch inside a medium dims it
+        by that medium's sigma_a, only an opaque row stops it, and a walk the cap ends counts as occluded.  Read by
+        shade_rays_surfaces, render_surfaces and render_lit; set_lights, set_surfaces and set_materials leave it alone."""
+        self._ck(self._L.rr_set_shadow_steps(self._h, int(k)), "rr_set_shadow_steps")
+
+    def shadow_steps(self):
+        """the setting of set_shadow_steps in force"""
+        k = C.c_uint32(0)
+        self._ck(self._L.rr_get_shadow_steps(self._h, C.byref(k)), "rr_get_shadow_steps")
+        return int(k.value)
+
     def shade_rays_surfaces(self, rays, params=None, rgba8=False, ray_counts=False):
         """shade_rays_nested with opaque hit groups (rr_shade_rays_surfaces): the same rays, material table, outputs and stream
         order.  A hit on an instance whose row of the surface table is opaque is, after the absorption of the medium crossed, lit by

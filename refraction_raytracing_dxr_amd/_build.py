@@ -14,8 +14,7 @@ DEMO = os.path.join(PKG, "rrdemo")
 DEVICE_SOURCES = ["rr_bvh_build.hip", "rr_render_fused.hip", "rr_render_paths.hip", "rr_render_lds.hip", "rr_render_stream.hip",
                   "rr_query.hip", "rr_query_multi.hip", "rr_frame.hip", "rr_shade_rays.hip", "rr_render_samples.hip",
                   "rr_render_adaptive.hip", "rr_render_lens.hip", "rr_render_spectral.hip", "rr_render_materials.hip",
-                  "rr_render_nested.hip", "rr_render_surfaces.hip", "rr_render_composed.hip", "rr_render_shutter.hip", "rr_render_lit.hip",
-                  "rr_render_shadows.hip"]
+                  "rr_render_nested.hip", "rr_render_surfaces.hip", "rr_render_composed.hip", "rr_render_shutter.hip", "rr_render_lit.hip"]
 HOST_SOURCES = ["rr_capi.cpp", "rr_capi_build.cpp", "rr_capi_dispatch.cpp", "rr_capi_orbit.cpp", "rr_capi_query.cpp", "rr_capi_keys.cpp", "rr_capi_comm.cpp",
                 "rr_choice.cpp", "host/rr_host_camera.cpp", "host/rr_host_mesh.cpp", "host/rr_host_image.cpp", "host/rr_host_partition.cpp",
                 "host/Mesh.cpp", "host/RefractionDemo.cpp"]

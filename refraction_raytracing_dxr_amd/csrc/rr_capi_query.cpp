@@ -446,22 +446,16 @@ const RayTree kShadeNested = { "shade_rays_nested", check_nested, shade_nested }
 const FrameTree kNested = { check_nested, frame_nested };
 
 // the nested trees with the surface table and the lights (p: after check_nested).  On caller rays check_shading_params refuses
-// under the entry point's own name, unlike its three siblings.
+// under the entry point's own name, unlike its three siblings.  surface_launch: the context's table, lights and shadow_steps as the
+// launchers take them -- the cap picks the kernel there (0: the first-hit shadow ray, else the walk)
+SurfaceLaunch surface_launch(const rr_context* ctx) { return { ctx->d_surfs.get(), ctx->n_surfs, &ctx->lights, ctx->shadow_steps }; }
 hipError_t shade_surfaces(rr_context* ctx, const SceneDev& sc, const DispatchDev& a, const rr_ray_dev* d_rays, uint32_t n, const ShadeOut& out, const FusedVariant& v)
 {
-    if (ctx->shadow_steps)                                      // transparent shadows: the walk's kernels (rr_render_shadows.hip)
-        return launch_shade_rays_shadows(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->shadow_steps, inst0_material(ctx),
-                                         d_rays, n, out, v, ctx->stream);
-    return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), d_rays, n, out, v,
-                                      ctx->stream);
+    return launch_shade_rays_surfaces(sc, a, ctx->d_mats.get(), surface_launch(ctx), inst0_material(ctx), d_rays, n, out, v, ctx->stream);
 }
 hipError_t frame_surfaces(rr_context* ctx, const FrameArgs& f, const SampleOffsets& off, uint32_t n_samples, const ShadeOut& out)
 {
-    if (ctx->shadow_steps)
-        return launch_render_shadows(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->shadow_steps,
-                                     inst0_material(ctx), n_samples, out, f.v, ctx->stream);
-    return launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, inst0_material(ctx), n_samples,
-                                  out, f.v, ctx->stream);
+    return launch_render_surfaces(f.sc, f.a, f.cam, off, ctx->d_mats.get(), surface_launch(ctx), inst0_material(ctx), n_samples, out, f.v, ctx->stream);
 }
 const RayTree kShadeSurfaces = { nullptr, check_nested, shade_surfaces };
 const FrameTree kSurfaces = { check_nested, frame_surfaces };
@@ -677,13 +671,9 @@ int lit_impl(rr_context* ctx, const LitReq& q, const LitTables& t, const ShadeOu
 {
     const ShutterFrame m = shutter_frame(ctx, q.s, t.s);
     const BandSet b = band_set(ctx);
-    const hipError_t e = ctx->shadow_steps
-        ? launch_render_lit_shadows(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
-                                    t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
-                                    ctx->shadow_steps, ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream)
-        : launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
-                            t.s.key, b.mats, ctx->n_mats, b.weights, ctx->d_surfs.get(), ctx->n_surfs, ctx->lights, ctx->light_shapes,
-                            ctx->d_env.get(), ctx->env_w, ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream);
+    const hipError_t e = launch_render_lit(ctx->d_key_scenes.get(), m.single_identity, m.f.a, m.f.cam, t.s.c.off, t.s.c.loff, t.lgt, t.s.c.lens, t.s.c.band,
+                                           t.s.key, b.mats, ctx->n_mats, b.weights, surface_launch(ctx), ctx->light_shapes, ctx->d_env.get(), ctx->env_w,
+                                           ctx->env_h, q.s.c.s.n_samples, out, m.f.v, ctx->stream);
     if (e) return fail(ctx, RR_ERR_DEVICE, q.s.c.s.who, e);
     return RR_OK;
 }

@@ -266,7 +266,7 @@ struct rr_context {
     LightsDev lights = {};
     LightShapesDev light_shapes = {};
     // transparent shadows (rr_set_shadow_steps): the cap on a shadow walk's TraceRay calls, 0 = off (any accepted hit occludes, the
-    // kernels of rr_render_surfaces.hip and rr_render_lit.hip).  Read where the surface table is read; no other setter touches it
+    // first-hit kernels of rr_render_surfaces.hip and rr_render_lit.hip).  Read where the surface table is read; no other setter touches it
     uint32_t shadow_steps = 0;
     // the band set of rr_render_composed (rr_set_material_bands): n_bands copies of the table in force, each with a column of
     // indices of its own, one behind the other at the head of d_band_mats, and three weights per band at the head of d_band_w;

@@ -109,14 +109,23 @@ hipError_t launch_render_nested(const SceneDev& sc, const DispatchDev& a, const 
                                 uint32_t mat0, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_surfaces.hip: opaque hit groups (rr_shade_rays_surfaces[_device], rr_render_surfaces[_device]): launch_shade_rays_nested
 // and launch_render_nested with the ray tree of rr_render_surfaces.h -- an instance whose row of the surface table is opaque is lit
-// by `lights` through shadow rays, emits and may continue as a mirror.  surfs: the context's table in device memory, n_surfs rows
-// (0: every row is glass, surfs may be null); rows at or beyond n_surfs are glass.  lights travels by value to the kernel
-hipError_t launch_shade_rays_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfDev* surfs, uint32_t n_surfs,
-                                      const LightsDev& lights, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, const ShadeOut& out, FusedVariant v,
-                                      hipStream_t s);
+// by `lights` through shadow rays, emits and may continue as a mirror.  What they add to a nested launch travels in SurfaceLaunch.
+// surfs: the context's table in device memory, n_surfs rows (0: every row is glass, surfs may be null); rows at or beyond n_surfs
+// are glass.  lights travels by value to the kernel.  shadow_k is the cap of transparent shadows (rr_set_shadow_steps) on this
+// launcher, launch_render_surfaces and launch_render_lit: 0 launches the first-hit kernel, 1 .. SHADOW_MAX_STEPS its _shadows twin,
+// whose shadow rays walk through glass (rr_render_shadows.h); above that is hipErrorInvalidValue
+constexpr uint32_t SHADOW_MAX_STEPS = 16;
+struct SurfaceLaunch {
+    const SurfDev* surfs; uint32_t n_surfs;
+    const LightsDev* lights;
+    uint32_t shadow_k;
+    // false is hipErrorInvalidValue.  mats: the launch's material table (the band tables, for the lit frames)
+    bool ok(const MatDev* mats) const { return mats && (!n_surfs || surfs) && lights->n <= MAX_LIGHTS && shadow_k <= SHADOW_MAX_STEPS; }
+};
+hipError_t launch_shade_rays_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfaceLaunch& su, uint32_t mat0,
+                                      const rr_ray_dev* rays, uint32_t n, const ShadeOut& out, FusedVariant v, hipStream_t s);
 hipError_t launch_render_surfaces(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
-                                  const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t mat0, uint32_t n_samples, const ShadeOut& out,
-                                  FusedVariant v, hipStream_t s);
+                                  const SurfaceLaunch& su, uint32_t mat0, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_composed.hip: composed frames (rr_render_composed[_device]): launch_render_nested with launch_render_lens' primary
 // rays (off, loff, lens; a.hx0..hy1 the lens rectangle, or the pinhole's when lens.pinhole) and launch_render_spectral's resolve.
 // Sample k is shaded under the table band_mats + b_k * n_rows (the context's band set: the bands' tables one behind the other,
@@ -147,31 +156,14 @@ hipError_t launch_render_shutter(const KeyDev* keys, bool single_identity, const
                                  const MatDev* band_mats, uint32_t n_rows, const float* band_w, const float4* env, int32_t env_w, int32_t env_h,
                                  uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_lit.hip: lit shutter frames (rr_render_lit[_device]): launch_render_shutter over the ray tree of
-// launch_render_surfaces, with the lights per sample.  surfs, n_surfs, lights: as launch_render_surfaces.  shapes: per light the two
+// launch_render_surfaces, with the lights per sample.  su: as launch_render_surfaces, the cap included.  shapes: per light the two
 // edges its position (or direction) moves along, by value; lgt: per sample the light offset (lu, lv), laid out as off -- sample k is
 // lit by light i at fmaf(lv_k, ey_i, fmaf(lu_k, ex_i, v_i)) per component, or at v_i where shapes.on == 0 (rr_render_lit.h).  That
 // every moved v is finite and no moved direction is zero the host checks
 hipError_t launch_render_lit(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
                              const SampleOffsets& loff, const SampleOffsets& lgt, const LensDev& lens, const SampleBands& band, const SampleKeys& key,
-                             const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs, uint32_t n_surfs,
-                             const LightsDev& lights, const LightShapesDev& shapes, const float4* env, int32_t env_w, int32_t env_h,
-                             uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
-// ---- rr_render_shadows.hip: transparent shadows (rr_set_shadow_steps): launch_shade_rays_surfaces, launch_render_surfaces and
-// launch_render_lit over the ray tree of rr_render_shadows.h -- an opaque hit's shadow ray walks through glass, at most shadow_k
-// closest-hit calls, takes the tint of the media it crosses and is stopped only by an opaque row.  Arguments as the twins';
-// 1 <= shadow_k <= SHADOW_MAX_STEPS (0 is hipErrorInvalidValue: with the setting at 0 the host launches the twins)
-constexpr uint32_t SHADOW_MAX_STEPS = 16;
-hipError_t launch_shade_rays_shadows(const SceneDev& sc, const DispatchDev& a, const MatDev* mats, const SurfDev* surfs, uint32_t n_surfs,
-                                     const LightsDev& lights, uint32_t shadow_k, uint32_t mat0, const rr_ray_dev* rays, uint32_t n, const ShadeOut& out,
-                                     FusedVariant v, hipStream_t s);
-hipError_t launch_render_shadows(const SceneDev& sc, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off, const MatDev* mats,
-                                 const SurfDev* surfs, uint32_t n_surfs, const LightsDev& lights, uint32_t shadow_k, uint32_t mat0, uint32_t n_samples,
-                                 const ShadeOut& out, FusedVariant v, hipStream_t s);
-hipError_t launch_render_lit_shadows(const KeyDev* keys, bool single_identity, const DispatchDev& a, const CamDev& cam, const SampleOffsets& off,
-                                     const SampleOffsets& loff, const SampleOffsets& lgt, const LensDev& lens, const SampleBands& band,
-                                     const SampleKeys& key, const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfDev* surfs,
-                                     uint32_t n_surfs, const LightsDev& lights, const LightShapesDev& shapes, uint32_t shadow_k, const float4* env,
-                                     int32_t env_w, int32_t env_h, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
+                             const MatDev* band_mats, uint32_t n_rows, const float* band_w, const SurfaceLaunch& su, const LightShapesDev& shapes,
+                             const float4* env, int32_t env_w, int32_t env_h, uint32_t n_samples, const ShadeOut& out, FusedVariant v, hipStream_t s);
 // ---- rr_render_adaptive.hip: adaptive supersampling (rr_render_adaptive[_device]): the first n_base samples for every pixel, the
 // rest up to n_max where the base samples show contrast above threshold.  Arguments as launch_render_samples; n_taken (may be null):
 // n_base or n_max per pixel; refine_groups: workgroups of the refine pass, 0 = one lane per pixel of the frame (the worst case).

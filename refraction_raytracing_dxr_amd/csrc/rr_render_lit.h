@@ -35,14 +35,15 @@ __device__ __forceinline__ LightDev moved_light(const LightsDev& lights, const L
     return m;
 }
 
-// ray_tree_surfaces, two-site form, with the lights moved to (lu, lv)
-template <bool TLAS, class E, class PK>
+// ray_tree_surfaces, two-site form, with the lights moved to (lu, lv).  WALK, K: the tree's; every walk goes towards the light as
+// moved for its sample, so a shaped light's soft shadow takes the glass's colour
+template <bool TLAS, class E, bool WALK = false, class PK>
 __device__ __forceinline__ f3 ray_tree_lit(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
                                            const LightsDev& lights, const LightShapesDev& shapes, float lu, float lv, uint32_t mat0,
-                                           RayStateNested r, E* stk, PK& park, LaneStats& st)
+                                           RayStateNested r, E* stk, PK& park, LaneStats& st, uint32_t K = 0u)
 {
-    return ray_tree_surfaces_two_site<TLAS, E>(sc, a, mats, sf, lights, [&](uint32_t i) { return moved_light(lights, shapes, i, lu, lv); }, mat0, r, stk,
-                                               park, st);
+    return ray_tree_surfaces_two_site<TLAS, E, WALK>(sc, a, mats, sf, lights, [&](uint32_t i) { return moved_light(lights, shapes, i, lu, lv); }, mat0, r,
+                                                     stk, park, st, K);
 }
 
 } // namespace rr

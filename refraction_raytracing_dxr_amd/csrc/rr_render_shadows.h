@@ -1,8 +1,9 @@
-// rr_render_shadows.h -- the ray tree of the transparent-shadow kernels (rr_render_shadows.hip): ray_tree_surfaces_two_site of
-// rr_render_surfaces.h with step b's shadow ray replaced by a straight WALK through the glass between the opaque hit and the light,
-// attenuated by what it crosses and stopped only by an opaque surface.  Opt-in: the context's shadow_steps (rr_set_shadow_steps) is
-// K, 0 <= K <= RR_SHADOW_MAX_STEPS = 16; with K == 0 the launchers run rr_render_surfaces.hip's and rr_render_lit.hip's kernels and
-// nothing here is reached.
+// rr_render_shadows.h -- the shadow ray of the transparent-shadow kernels (k_shade_rays_shadows and k_render_shadows in
+// rr_render_surfaces.hip, k_render_lit_shadows in rr_render_lit.hip): the WALK form of ray_tree_surfaces_two_site
+// (rr_render_surfaces.h) puts shadow_walk where step b's first-hit ray stands -- a straight WALK through the glass between the opaque
+// hit and the light, attenuated by what it crosses and stopped only by an opaque surface.  Opt-in: the context's shadow_steps
+// (rr_set_shadow_steps) is K, 0 <= K <= RR_SHADOW_MAX_STEPS = 16; with K == 0 the launchers run the first-hit kernels and nothing here
+// is reached.
 //
 // Everything in rr_render_surfaces.h's contract stands but the shadow ray of step b.  With K >= 1, for a light the hit faces
 // (cs > 0; Ld, far, g from light_at as before) -- one rounding per written operation, fmaf only where written:
@@ -23,7 +24,7 @@
 // misses.
 //
 // Reductions, byte for byte in colours, RGBA8 and ray counts:
-//   any K  equals ray_tree_surfaces_two_site wherever no shadow ray's first hit is glass: a first call that misses or stops on an
+//   any K  equals the tree's first-hit form wherever no shadow ray's first hit is glass: a first call that misses or stops on an
 //          opaque row is the first-hit ray's answer, and f * 1.0f == f.
 //   K = 1  equals it on every scene but for one corner, which step 4 standing before step 5 leaves: a glass hit closer than
 //          tmin_secondary to the far end of its interval ends the walk lit where the first-hit ray is occluded.
@@ -39,7 +40,7 @@
 // registers that live across the walk's traversals beside X, Nf, E and the radiance ray; DESIGN 5.17 has the code object's figures.
 // The traversal stack is free while a hit is shaded, so the walk uses the same LDS column.
 #pragma once
-#include "rr_render_lit.h"
+#include "rr_render_surfaces.h"
 
 namespace rr {
 
@@ -94,56 +95,6 @@ __device__ __forceinline__ bool shadow_walk(const SceneDev& sc, const DispatchDe
         if (!(fs > a.tmin_s)) return true;
     }
     return false;                                             // the cap
-}
-
-// ray_tree_surfaces_two_site with the walk in place of the first-hit shadow ray.  light_row(i): as there; K >= 1
-template <bool TLAS, class E, class PK, class LR>
-__device__ __forceinline__ f3 ray_tree_surfaces_transmit(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
-                                                         const LightsDev& lights, LR&& light_row, uint32_t K, uint32_t mat0, RayStateNested r, E* stk,
-                                                         PK& park, LaneStats& st)
-{
-    f3 acc = mk3(0.0f, 0.0f, 0.0f);
-    int np = 0;
-    for (;;) {
-        HitRecFace h;
-        trace_scene<false, TLAS, E, GlobalNodes>(sc, r.O, r.D, r.tmin, r.tmax, 0u, h, stk, st.cnt, Diag{ nullptr }, GlobalNodes{});
-        ++st.rays;
-        bool have_next = false;
-        if (!h.hit) {                                         // Miss
-            f3 e = env_lookup(sc, r.D);
-            acc.x = fmaf(r.w.x, e.x, acc.x); acc.y = fmaf(r.w.y, e.y, acc.y); acc.z = fmaf(r.w.z, e.z, acc.z);
-        } else if ((int)r.count < a.max_refract) {            // ClosestHit
-            const uint32_t row = hit_material<TLAS>(sc, h, mat0);
-            const uint32_t c = media_top(r.media);
-            if (c) absorb_crossed(mats, c, h.t, r.w);
-            const f3 X = mk3(fmaf(h.t, r.D.x, r.O.x), fmaf(h.t, r.D.y, r.O.y), fmaf(h.t, r.D.z, r.O.z));   // hlsl:88
-            if (row < sf.n && sf.rows[row].kind == SURFACE_OPAQUE) {
-                const f3 N = shading_normal<TLAS>(sc, h);
-                const f3 Nf = h.front ? N : neg3(N);
-                f3 Ev = mk3(lights.ambient[0], lights.ambient[1], lights.ambient[2]);
-                for (uint32_t i = 0; i < lights.n; ++i) {
-                    const LightDev& lt = light_row(i);                    // (a copy lives as long as lt)
-                    f3 Ld;
-                    float far, g;
-                    light_at(lt, a, X, Ld, far, g);
-                    const float cs = dot3(Nf, Ld);
-                    if (cs > 0.0f) {
-                        f3 T;
-                        if (shadow_walk<TLAS, E>(sc, a, mats, sf, mat0, K, TLAS ? lt.shadow_mask : (lt.shadow_mask & 1u), X, Ld, far, r.media, stk, st, T)) {
-                            const float f = cs * g;
-                            Ev.x = fmaf(lt.radiance[0], f * T.x, Ev.x); Ev.y = fmaf(lt.radiance[1], f * T.y, Ev.y);
-                            Ev.z = fmaf(lt.radiance[2], f * T.z, Ev.z);
-                        }
-                    }
-                }
-                have_next = opaque_end(a, sf.rows + row, Ev, Nf, X, r, acc);
-            } else {
-                have_next = glass_hit<TLAS>(sc, a, mats, h, row + 1u, X, r, np, park);
-            }
-        }
-        if (!have_next && !pop_parked(a, r, np, park)) break;
-    }
-    return acc;
 }
 
 } // namespace rr

@@ -37,8 +37,9 @@
 // loads; the surface row differs per lane and comes through vector loads, as mats does.
 // Not covered: environment lighting of opaque surfaces, textures, opaque rows in the composed and shutter frames, the dispatch
 // kernels and the _materials calls.  (Opaque rows over scene keys, through a lens and under lights with an area: rr_render_lit.h.
-// Shadow rays that pass glass and take its tint: rr_render_shadows.h, whose walk leaves out Fresnel loss and bending at the
-// interfaces it crosses, absorption beyond its last hit, and caustics.)
+// Shadow rays that pass glass and take its tint: the two-site tree's WALK form, which puts shadow_walk (rr_render_shadows.h, with
+// its contract) where step b's first-hit ray stands; the walk leaves out Fresnel loss and bending at the interfaces it crosses,
+// absorption beyond its last hit, and caustics.)
 #pragma once
 #include "rr_render_nested.h"
 
@@ -77,6 +78,12 @@ __device__ __forceinline__ void absorb_crossed(const MatDev* __restrict__ mats, 
     w.y = w.y * rr_expf_neg(-(sg * t));
     w.z = w.z * rr_expf_neg(-(sb * t));
 }
+
+// The walk of the tree's WALK form, defined in rr_render_shadows.h: a translation unit that instantiates that form includes it; the
+// first-hit form never names it, so this header compiles alone
+template <bool TLAS, class E>
+__device__ __forceinline__ bool shadow_walk(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf, uint32_t mat0,
+                                            uint32_t K, uint32_t mask, f3 X, f3 Ld, float far, uint32_t L, E* stk, LaneStats& st, f3& T);
 
 // steps 2-5 of the nested contract on a glass row: shade_ray_nested's text after the absorption.  True: r is the continuing ray
 template <bool TLAS, class PK>
@@ -170,11 +177,13 @@ __device__ __forceinline__ bool pop_parked(const DispatchDev& a, RayStateNested&
 
 // ray_tree_nested with the opaque hit group, two-site form: the shadow rays are traced where the hit is shaded.  light_row(i) is row
 // i of the lights as this tree sees it -- the table's row (a reference), or a copy of it moved for one sample (rr_render_lit.h); i is
-// wave-uniform.  lights itself gives the ambient term and the number of rows.  Built in either form's build: the lit frames use it
-template <bool TLAS, class E, class PK, class LR>
+// wave-uniform.  lights itself gives the ambient term and the number of rows.  Built in either form's build: the lit frames use it.
+// WALK: step b's shadow ray is shadow_walk under the cap K (1 .. SHADOW_MAX_STEPS, wave-uniform) and the light is weighted with what
+// the glass let through (rr_render_shadows.h); the first-hit form never reads K
+template <bool TLAS, class E, bool WALK = false, class PK, class LR>
 __device__ __forceinline__ f3 ray_tree_surfaces_two_site(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
                                                          const LightsDev& lights, LR&& light_row, uint32_t mat0, RayStateNested r, E* stk, PK& park,
-                                                         LaneStats& st)
+                                                         LaneStats& st, uint32_t K = 0u)
 {
     f3 acc = mk3(0.0f, 0.0f, 0.0f);
     int np = 0;
@@ -202,13 +211,22 @@ __device__ __forceinline__ f3 ray_tree_surfaces_two_site(const SceneDev& sc, con
                     light_at(lt, a, X, Ld, far, g);
                     const float cs = dot3(Nf, Ld);
                     if (cs > 0.0f) {
-                        HitRecShadow hs;
-                        trace_scene<false, TLAS, E, GlobalNodes, true, HitRecShadow>(sc, X, Ld, a.tmin_s, far, 0u, hs, stk, st.cnt, Diag{ nullptr },
-                                                                                     GlobalNodes{}, TLAS ? lt.shadow_mask : (lt.shadow_mask & 1u), true);
-                        ++st.rays;
-                        if (!hs.hit) {
-                            const float f = cs * g;
-                            Ev.x = fmaf(lt.radiance[0], f, Ev.x); Ev.y = fmaf(lt.radiance[1], f, Ev.y); Ev.z = fmaf(lt.radiance[2], f, Ev.z);
+                        if constexpr (WALK) {
+                            f3 T;
+                            if (shadow_walk<TLAS, E>(sc, a, mats, sf, mat0, K, TLAS ? lt.shadow_mask : (lt.shadow_mask & 1u), X, Ld, far, r.media, stk, st, T)) {
+                                const float f = cs * g;
+                                Ev.x = fmaf(lt.radiance[0], f * T.x, Ev.x); Ev.y = fmaf(lt.radiance[1], f * T.y, Ev.y);
+                                Ev.z = fmaf(lt.radiance[2], f * T.z, Ev.z);
+                            }
+                        } else {
+                            HitRecShadow hs;
+                            trace_scene<false, TLAS, E, GlobalNodes, true, HitRecShadow>(sc, X, Ld, a.tmin_s, far, 0u, hs, stk, st.cnt, Diag{ nullptr },
+                                                                                         GlobalNodes{}, TLAS ? lt.shadow_mask : (lt.shadow_mask & 1u), true);
+                            ++st.rays;
+                            if (!hs.hit) {
+                                const float f = cs * g;
+                                Ev.x = fmaf(lt.radiance[0], f, Ev.x); Ev.y = fmaf(lt.radiance[1], f, Ev.y); Ev.z = fmaf(lt.radiance[2], f, Ev.z);
+                            }
                         }
                     }
                 }
@@ -224,20 +242,27 @@ __device__ __forceinline__ f3 ray_tree_surfaces_two_site(const SceneDev& sc, con
 
 #ifndef RR_SURFACES_ONE_SITE
 // the surface kernels' tree: the lights are the table's rows
-template <bool TLAS, class E, class PK>
+template <bool TLAS, class E, bool WALK = false, class PK>
 __device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
-                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st)
+                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st,
+                                                uint32_t K = 0u)
 {
-    return ray_tree_surfaces_two_site<TLAS, E>(sc, a, mats, sf, lights, [&](uint32_t i) -> const LightDev& { return lights.l[i]; }, mat0, r, stk, park, st);
+    return ray_tree_surfaces_two_site<TLAS, E, WALK>(sc, a, mats, sf, lights, [&](uint32_t i) -> const LightDev& { return lights.l[i]; }, mat0, r, stk,
+                                                     park, st, K);
 }
 #else
 // ray_tree_nested with the opaque hit group, one trace site: a lane's trip is a radiance ray or, while it shades an opaque hit, the
 // shadow ray of light `li`.  Every loop over the lights runs over the whole table with a per-lane condition, so its index stays
 // wave-uniform; between two of a hit's shadow rays the lane keeps X, Nf, E, li, f and the row, and recomputes the rest.
-template <bool TLAS, class E, class PK>
+// The walk has the two-site tree only: WALK forwards to it, as the other build does
+template <bool TLAS, class E, bool WALK = false, class PK>
 __device__ __forceinline__ f3 ray_tree_surfaces(const SceneDev& sc, const DispatchDev& a, const MatDev* __restrict__ mats, const SurfArgs& sf,
-                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st)
+                                                const LightsDev& lights, uint32_t mat0, RayStateNested r, E* stk, PK& park, LaneStats& st,
+                                                uint32_t K = 0u)
 {
+    if constexpr (WALK)
+        return ray_tree_surfaces_two_site<TLAS, E, true>(sc, a, mats, sf, lights, [&](uint32_t i) -> const LightDev& { return lights.l[i]; }, mat0, r, stk,
+                                                         park, st, K);
     f3 acc = mk3(0.0f, 0.0f, 0.0f);
     int np = 0;
     bool shadow = false;                                      // this trip is a shadow ray
